@@ -5,11 +5,16 @@
                                                       entry point does with mp.spawn, ref pretrain/lxmert_pretrain.py:865)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full ...                       (also: host enqueue time, the instrumented GEMM step (roofline), the other
+                                                      gradient-exchange variants (N>1), the SURVEY 8f workloads, the CPU baseline)
+    python bench.py --dump-outputs DIR ...           (the last timed step's outputs as DIR/<name>.npy, for output-for-output
+                                                      comparison of two builds: same arguments, same inputs; the step then runs
+                                                      in its bit-reproducible configuration, bit_reproducible_step in the line)
 
 One step = forward + backward + gradient all-reduce (N>1) + clip + AdamW of the full X-LXMERT encoder
 (9 language / 5 visual / 5 cross layers, d=768) with the 10k-codebook head, per-GPU batch 256 of
 (20 text tokens x 64 visual tokens), bf16 operands / fp32 accumulate, synthetic inputs resident in HBM.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  Without --full the run sets up, warms up, times the K steps and prints the headline.
 """
 import argparse
 import json
@@ -301,6 +306,24 @@ def exchange_sweep(cfg, B, local, rank, world, args, host_batches, headline):
     return out
 
 
+def dump_outputs(path, losses, store, n_sample=1 << 21):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy -- the loss buffer it returned
+    ([obj_loss, feat_loss, 0, 0]) and the fp32 parameters and AdamW moments it updated in place.  Those buffers hold ~0.8 GB
+    each at the default size, so the same 2M positions of the used range (seeded, sorted) are written from each: 24 MB in all.
+    Inputs, weights and dropout masks are the same in every run, and with --dump-outputs the step runs bit-reproducibly (see
+    main): parameters and moments come out bit-identical; the loss scalars (one fp32 atomic per block) agree to rounding."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    n = store.n_used
+    g = torch.Generator().manual_seed(20241016)
+    idx = torch.randint(0, n, (min(n, n_sample),), generator=g).sort().values.to(store.master.device)
+    arrays = {"losses": losses, "params_sample": store.master[idx],
+              "adam_exp_avg_sample": store.exp_avg[idx], "adam_exp_avg_sq_sample": store.exp_avg_sq[idx]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -308,8 +331,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)          # >= 100 timed steps after >= 20 warm-up steps
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (reference --batchSize, param.py:70)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the SURVEY 8f workloads (VQA / NLVR2 / word_mask / matched / sampler)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure: host enqueue time per step, the instrumented "
+                    "GEMM step (roofline), the other gradient-exchange variants (N > 1), the SURVEY 8f workloads, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="time the step in its bit-reproducible configuration and write "
+                    "what the last timed step computed (its losses and a fixed, seeded sample of the fp32 parameters and AdamW moments "
+                    "it updated) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the SURVEY 8f workloads (VQA / NLVR2 / word_mask / matched / sampler)")
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--no-dropout", action="store_true", help="eval-parity mode (the reference trains with p=0.1)")
     ap.add_argument("--single-stream", action="store_true", help="no language/visual stream overlap (profiling)")
@@ -324,7 +352,7 @@ def main():
                     "replicated AdamW (default) or reduce-scatter -> shard-local AdamW -> all-gather (trainer.PretrainStep collective)")
     ap.add_argument("--gather", default=None, choices=["fp32", "bf16"], help="rs+ag: what the all-gather moves -- the fp32 master slices "
                     "(default) or the bf16 compute copy + a sparse fp32 side car (half the bytes; trainer.PretrainStep gather)")
-    ap.add_argument("--no-exchange-sweep", action="store_true", help="N > 1: skip the 10-step timings of the other gradient-exchange variants")
+    ap.add_argument("--no-exchange-sweep", action="store_true", help="--full, N > 1: skip the 10-step timings of the other gradient-exchange variants")
     ap.add_argument("--resident-inputs", action="store_true", help="minibatches resident in HBM before the timed region (default: "
                     "pinned host memory, uploaded inside the timed step on a copy stream, one step ahead)")
     args = ap.parse_args()
@@ -392,6 +420,14 @@ def main():
                       bucket_mb=float(os.environ.get("XL_BUCKET_MB", "64")),
                       plan=(not args.eager and not args.single_stream), drop_grads=True,
                       overlap_optimizer=not (args.no_opt_overlap or args.single_stream), collective=args.collective, gather=args.gather)
+    # A plain run times the library defaults.  --dump-outputs times the step in its bit-reproducible configuration instead (two
+    # switches of this trainer's library context, recorded in the result line): K-split weight gradients summed in slabs in slice
+    # order rather than with fp32 atomics, and no K split of the head's last round of tiles (its slices meet in arrival order).
+    # With the defaults, two runs' dumps differ by far more than rounding (profiles/dump_reproducibility.txt).
+    reproducible = args.dump_outputs is not None
+    if reproducible:
+        tr.ops.set_gemm_wgrad_slabs(1)
+        tr.ops.set_gemm_tail_split(0, 4096)
     if args.single_stream:
         tr.engine.side = None
     g = torch.Generator().manual_seed(9595)
@@ -456,43 +492,48 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = tmax.item()
     loss_val = losses[0].item()
+    if rank == 0 and args.dump_outputs:       # before any later step overwrites the loss buffer and the parameters
+        dump_outputs(args.dump_outputs, losses, tr.store)
 
-    # one extra, instrumented step (not in the timed region).  It runs single-stream so that every GEMM launch is
-    # timed alone (in the timed region language-stream kernels overlap visual-stream kernels on a second stream,
-    # which lengthens individual kernels while shortening the step).
-    # host time to enqueue ONE step on an empty queue (the timed loop above runs the host into the runtime's queue
-    # back-pressure: its per-step enqueue time says how far ahead of the GPU the host got, not what a step costs it)
-    host_ms = []
-    for i in range(6):
+    if args.full:
+        # host time to enqueue ONE step on an empty queue (the timed loop above runs the host into the runtime's queue
+        # back-pressure: its per-step enqueue time says how far ahead of the GPU the host got, not what a step costs it)
+        host_ms = []
+        for i in range(6):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            tr.step(get(i))
+            host_ms.append((time.perf_counter() - h0) * 1e3)
         torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        tr.step(get(i))
-        host_ms.append((time.perf_counter() - h0) * 1e3)
-    torch.cuda.synchronize()
-    host_ms = sorted(host_ms)[len(host_ms) // 2]
-    side, tr.engine.side = tr.engine.side, None
-    planned, tr.plan_mode = tr.plan_mode, False
-    with GemmTimer(tr.ops) as gt:
-        tr.step(get(0))
-    tr.engine.side, tr.plan_mode = side, planned
-    # what the event pair itself adds to every timed launch: the same start / end markers around a one-wave kernel (a 64-element cast);
-    # reported next to the roofline figures, never subtracted from them
-    probe, probe_o = torch.zeros(64, device="cuda"), torch.zeros(64, device="cuda", dtype=torch.bfloat16)
-    pairs = []
-    if hasattr(torch.cuda, "_sleep"):
-        torch.cuda._sleep(40000000)           # (the stream stays busy while the 200 triplets are queued: no host latency in the intervals)
-    for _ in range(200):
-        s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_.record(); tr.ops.cast_from_f32(probe, probe_o, 64); e_.record()
-        pairs.append((s_, e_))
-    torch.cuda.synchronize()
-    ev_floor = sorted(a.elapsed_time(b) for a, b in pairs)[100] * 1e3
-    traffic, traffic_src = None, None
-    try:        # HBM bytes per GEMM launch from the committed PMC profile of this build (cannot be collected live)
-        tj = json.load(open(os.path.join(ROOT, "profiles", "gemm_traffic.json")))
-        traffic, traffic_src = round(tj["bytes_per_launch"]), tj.get("source")
-    except Exception:
-        pass
+        host_ms = sorted(host_ms)[len(host_ms) // 2]
+    if args.full or args.gemm_table or args.gemm_list:
+        # one extra, instrumented step (not in the timed region).  It runs single-stream so that every GEMM launch is
+        # timed alone (in the timed region language-stream kernels overlap visual-stream kernels on a second stream,
+        # which lengthens individual kernels while shortening the step).
+        side, tr.engine.side = tr.engine.side, None
+        planned, tr.plan_mode = tr.plan_mode, False
+        with GemmTimer(tr.ops) as gt:
+            tr.step(get(0))
+        tr.engine.side, tr.plan_mode = side, planned
+    if args.full:
+        # what the event pair itself adds to every timed launch: the same start / end markers around a one-wave kernel (a 64-element cast);
+        # reported next to the roofline figures, never subtracted from them
+        probe, probe_o = torch.zeros(64, device="cuda"), torch.zeros(64, device="cuda", dtype=torch.bfloat16)
+        pairs = []
+        if hasattr(torch.cuda, "_sleep"):
+            torch.cuda._sleep(40000000)           # (the stream stays busy while the 200 triplets are queued: no host latency in the intervals)
+        for _ in range(200):
+            s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s_.record(); tr.ops.cast_from_f32(probe, probe_o, 64); e_.record()
+            pairs.append((s_, e_))
+        torch.cuda.synchronize()
+        ev_floor = sorted(a.elapsed_time(b) for a, b in pairs)[100] * 1e3
+        traffic, traffic_src = None, None
+        try:        # HBM bytes per GEMM launch from the committed PMC profile of this build (cannot be collected live)
+            tj = json.load(open(os.path.join(ROOT, "profiles", "gemm_traffic.json")))
+            traffic, traffic_src = round(tj["bytes_per_launch"]), tj.get("source")
+        except Exception:
+            pass
     if rank == 0 and args.gemm_list:
         json.dump([{"key": list(key), "bytes": _b, "block": _t, "us": s_.elapsed_time(e_) * 1e3, "flops": f_}
                    for s_, e_, f_, key, _b, _t in gt.rec], open(args.gemm_list, "w"))
@@ -506,7 +547,6 @@ def main():
         ms = dt / args.steps * 1e3
         value = B * world * args.steps / dt
         plans = list(tr._plans.values())
-        gemm_tflops = gt.flops / (gt.total_ms * 1e-3) / 1e12
         out = {
             "metric": "pretrain examples/sec (20 text tok x 64 vis tok, bs=256)", "value": round(value, 1),
             "unit": "examples/s", "n_gpus": 1 if share_gpu else world, "steps": args.steps, "warmup": args.warmup,
@@ -517,7 +557,11 @@ def main():
             "ms_per_step_series": [round(x, 2) for x in series[:32]],          # in issue order: what the first steps after the sync() cost
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "configs[1]+[2]: full X-LXMERT encoder 9L/5R/5X d=768 + obj_predict_head over 10k codebook, "
+            "bit_reproducible_step": reproducible,
+            "config": {"reductions": ("bit-reproducible (--dump-outputs): K-split weight gradients summed in slabs, no tail split of "
+                                      "the head contraction" if reproducible else
+                                      "library defaults: fp32 atomics for K-split weight gradients, tail split of the head contraction"),
+                       "workload":"configs[1]+[2]: full X-LXMERT encoder 9L/5R/5X d=768 + obj_predict_head over 10k codebook, "
                                    "masked-visual-token step fwd+bwd+clip+AdamW", "per_gpu_batch": B, "global_batch": B * world,
                        "text_len": 20, "visual_tokens": 64, "parallelism": f"dp{world}",
                        "prewarm": (f"{n_pre} free-running untimed training steps before the {args.warmup} warm-up steps: the first time the host "
@@ -544,36 +588,40 @@ def main():
                        "vis_mask": "--vis_mask_predict masks, n ~ U{1..64} per image (ref lxmert_data.py:414-419)",
                        "head_rows": "codebook head + both losses on the masked rows only (exact: the reference's losses read "
                                     "nothing else); all rows with XL_COMPACT_HEAD=0"},
-            "host_enqueue_ms_per_step": round(host_ms, 3),
-            "host_enqueue_note": "median host time of tr.step() on an empty queue (6 steps after the timed region, device "
-                                 "synchronised before each); inside the timed loop the host ran "
-                                 f"{round(t_enqueue / args.steps * 1e3, 2)} ms per step, i.e. up to the runtime's queue back-pressure",
-            # whole-step MFMA utilisation from the dense-contraction FLOPs actually EXECUTED in a step (the head runs on the
-            # masked rows only, so this is below the contract figure 50.782 GFLOP/example x batch)
-            "step_mfma_frac": round(gt.flops / (ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12), 4),
-            "roofline": {"bound": "mfma", "kernel": "gemm_bf16_pp_kernel + gemm_bf16_mfma_kernel (all dense contractions of one step, grouped weight gradients included)",
-                         "achieved": round(gemm_tflops, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4),
-                         # the WHOLE STEP's executed dense-contraction FLOPs over the step time and the peak (= step_mfma_frac): the
-                         # contract figure 50.782 GFLOP/example credits head rows the step does not compute (masked-row head), so
-                         # value x 50.782 GFLOP / peak would overstate it -- this one takes no such credit
-                         "frac_contract_uncredited": round(gt.flops / (ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12), 4),
-                         # informational, NOT the contract's peak: what a register-only bf16 MFMA loop sustains on all 256 CUs with
-                         # non-trivial operand bits (the 2.5 PFLOP/s figure is reached on zero operands only: the chip clocks to its
-                         # power limit) -- tools/probes/clock_probe.hip, profiles/r05c/clock_probe.txt
-                         "peak_real_data_measured": {"value": 1850.0, "unit": "TFLOP/s", "frac": round(gemm_tflops / 1850.0, 4),
-                                                     "source": "profiles/r05c/clock_probe.txt"},
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": round(gt.bytes / gt.launches),
-                         "algorithmic_bytes_per_step": int(gt.bytes),
-                         "blocks": gt.by_block(PEAK_BF16_TFLOPS),
-                         "launches_per_step": gt.launches, "avg_launch_us": round(gt.total_ms * 1e3 / gt.launches, 2),
-                         "gemm_ms_per_step": round(gt.total_ms, 3),
-                         "event_pair_floor_us": round(ev_floor, 2),     # start/end markers around a one-wave kernel: part of every avg_launch_us
-
-                         "algorithmic_gflop_per_step": round(gt.flops / 1e9, 1),
-                         "contract_gflop_per_step": round(GFLOP_PER_EXAMPLE * B, 1)},
         }
+        if args.full:
+            gemm_tflops = gt.flops / (gt.total_ms * 1e-3) / 1e12
+            out.update({
+                "host_enqueue_ms_per_step": round(host_ms, 3),
+                "host_enqueue_note": "median host time of tr.step() on an empty queue (6 steps after the timed region, device "
+                                     "synchronised before each); inside the timed loop the host ran "
+                                     f"{round(t_enqueue / args.steps * 1e3, 2)} ms per step, i.e. up to the runtime's queue back-pressure",
+                # whole-step MFMA utilisation from the dense-contraction FLOPs actually EXECUTED in a step (the head runs on the
+                # masked rows only, so this is below the contract figure 50.782 GFLOP/example x batch)
+                "step_mfma_frac": round(gt.flops / (ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12), 4),
+                "roofline": {"bound": "mfma", "kernel": "gemm_bf16_pp_kernel + gemm_bf16_mfma_kernel (all dense contractions of one step, grouped weight gradients included)",
+                             "achieved": round(gemm_tflops, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4),
+                             # the WHOLE STEP's executed dense-contraction FLOPs over the step time and the peak (= step_mfma_frac): the
+                             # contract figure 50.782 GFLOP/example credits head rows the step does not compute (masked-row head), so
+                             # value x 50.782 GFLOP / peak would overstate it -- this one takes no such credit
+                             "frac_contract_uncredited": round(gt.flops / (ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12), 4),
+                             # informational, NOT the contract's peak: what a register-only bf16 MFMA loop sustains on all 256 CUs with
+                             # non-trivial operand bits (the 2.5 PFLOP/s figure is reached on zero operands only: the chip clocks to its
+                             # power limit) -- tools/probes/clock_probe.hip, profiles/r05c/clock_probe.txt
+                             "peak_real_data_measured": {"value": 1850.0, "unit": "TFLOP/s", "frac": round(gemm_tflops / 1850.0, 4),
+                                                         "source": "profiles/r05c/clock_probe.txt"},
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": round(gt.bytes / gt.launches),
+                             "algorithmic_bytes_per_step": int(gt.bytes),
+                             "blocks": gt.by_block(PEAK_BF16_TFLOPS),
+                             "launches_per_step": gt.launches, "avg_launch_us": round(gt.total_ms * 1e3 / gt.launches, 2),
+                             "gemm_ms_per_step": round(gt.total_ms, 3),
+                             "event_pair_floor_us": round(ev_floor, 2),     # start/end markers around a one-wave kernel: part of every avg_launch_us
+
+                             "algorithmic_gflop_per_step": round(gt.flops / 1e9, 1),
+                             "contract_gflop_per_step": round(GFLOP_PER_EXAMPLE * B, 1)},
+            })
         if share_gpu:
             # N ranks on ONE device (test rig for the exchange with a real second rank; RCCL refuses it, gloo does not): this is
             # NOT a scaling result -- every rank competes for the same GPU
@@ -602,7 +650,7 @@ def main():
             out["config"]["gradient_exchange"]["default_rationale"] = (
                 "fp32 all-reduce = what DDP moves for the reference's fp32 parameters (lxmert_pretrain.py:694-700); predicted step time per "
                 "variant and N in DESIGN.md section 7 -- the `exchanges` key of this line holds the other variants measured in this run")
-    if world > 1 and not args.no_exchange_sweep and (not share_gpu or os.environ.get("XL_BENCH_SWEEP_SHARED") == "1"):
+    if args.full and world > 1 and not args.no_exchange_sweep and (not share_gpu or os.environ.get("XL_BENCH_SWEEP_SHARED") == "1"):
         # every rank takes part (collectives); rank 0 reports
         hn = ("rs+ag_" + ("bf16" if tr.gather_bf16 else "fp32") + "_gather") if tr.sharded else \
              ("allreduce_bf16_buckets" if tr.comm_buf is not None else "allreduce_fp32")
@@ -631,11 +679,11 @@ def main():
         if rank == 0:
             out["exchanges"] = {"headline": hn, "headline_ms_per_step": out["ms_per_step"], **sweep}
     if rank == 0:
-        if not args.no_extra and world == 1 and not args.single_stream:
+        if args.full and not args.no_extra and world == 1 and not args.single_stream:
             del tr, batches
             torch.cuda.empty_cache()
             out["other_workloads"] = other_workloads(cfg, f"cuda:{local}")
-        if not args.no_cpu_baseline and world == 1:           # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1:           # reported at N = 1 only (rank 0's host cores)
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_batch)
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if grouped:

@@ -1259,7 +1259,7 @@ def test_bench_two_ranks_sharing_the_gpu_end_to_end(tmp_path, sweep_deadline):
     #  would wait for it -- the launcher's own exit is what ends the run)
     with open(tmp_path / "out", "w") as fo, open(tmp_path / "err", "w") as fe:
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4",
-                            "--warmup", "3", "--batch", "64", "--no-extra", "--no-cpu-baseline", "--prewarm-steps", "0"], env=env, stdout=fo, stderr=fe,
+                            "--warmup", "3", "--batch", "64", "--full", "--no-extra", "--no-cpu-baseline", "--prewarm-steps", "0"], env=env, stdout=fo, stderr=fe,
                            stdin=subprocess.DEVNULL, timeout=600)
     stdout, stderr = (tmp_path / "out").read_text(), (tmp_path / "err").read_text()
     assert r.returncode == 0, stderr[-6000:]
@@ -1282,6 +1282,57 @@ def test_bench_two_ranks_sharing_the_gpu_end_to_end(tmp_path, sweep_deadline):
         assert sw[name]["ms_per_step"] > 0 and sw[name]["exposed_comm_ms_per_step"] >= 0.0
     assert sw["allreduce_bf16_buckets"]["bytes_per_step"] * 2 == ex["bytes_per_step"]
     print("2 ranks on one GPU:", out["ms_per_step"], "ms/step, host", out["host_enqueue_ms_per_step"], ex, sw)
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full: ONE JSON line with the headline keys, one step timing per timed step (--steps) and nothing
+    of what --full adds; a plain run times the library defaults.  --dump-outputs times the bit-reproducible step (recorded in the
+    line) and writes the last timed step's losses and parameter / AdamW-moment samples as float32 .npy, the same in two runs with
+    the same arguments (seeded inputs, weights and dropout)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, XL_BENCH_FAULT_TIMEOUT="300")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "XL_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(3):
+        d = tmp_path / f"dump{run}" if run else None        # run 0: plain
+        steps = 3 if run else 5
+        with open(tmp_path / "out", "w") as fo, open(tmp_path / "err", "w") as fe:
+            r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                                "--prewarm-steps", "0"] + (["--dump-outputs", str(d)] if d else []), env=env, stdout=fo, stderr=fe,
+                               stdin=subprocess.DEVNULL, timeout=400)
+        stdout, stderr = (tmp_path / "out").read_text(), (tmp_path / "err").read_text()
+        assert r.returncode == 0, stderr[-6000:]
+        lines = [ln for ln in stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["unit"] == "examples/s" and out["higher_is_better"] is True and out["dtype"] == "bf16" and out["steps"] == steps
+        assert len(out["ms_per_step_series"]) == steps and all(t > 0 for t in out["ms_per_step_series"])   # one mark per timed step
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and abs(out["value"] - 256 * 1e3 / out["ms_per_step"]) < 0.01 * out["value"]
+        for k in ("roofline", "host_enqueue_ms_per_step", "other_workloads", "cpu_baseline", "exchanges"):
+            assert k not in out, k
+        assert out["bit_reproducible_step"] is (d is not None)
+        assert out["config"]["reductions"].startswith("bit-reproducible" if d else "library defaults")
+        if d is None:
+            continue
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrays) == {"losses", "params_sample", "adam_exp_avg_sample", "adam_exp_avg_sq_sample"}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        for name, a in arrays.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), name
+        assert arrays["losses"].shape == (4,) and arrays["losses"][0] > 0
+        assert abs(arrays["losses"][0] - out["config"]["loss"]) < 1e-3
+        assert (arrays["adam_exp_avg_sq_sample"] >= 0).all() and arrays["adam_exp_avg_sq_sample"].max() > 0
+        dumps.append(arrays)
+    # the bit-reproducible step (K-split weight gradients through slabs, no tail split): parameters and moments bit-identical;
+    # the loss scalars are summed by one fp32 atomic per block
+    for name in ("params_sample", "adam_exp_avg_sample", "adam_exp_avg_sq_sample"):
+        assert np.array_equal(dumps[0][name], dumps[1][name]), (name, np.abs(dumps[0][name] - dumps[1][name]).max())
+    assert np.allclose(dumps[0]["losses"], dumps[1]["losses"], rtol=1e-5, atol=1e-7), (dumps[0]["losses"], dumps[1]["losses"])
 
 
 def test_two_library_contexts_interleaved_in_one_process():

@@ -195,7 +195,7 @@ def test_bench_two_gpus_end_to_end(tmp_path, collective):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "XL_BENCH_SHARE_GPU", "XL_COMM"):
         env.pop(k, None)
     with open(tmp_path / "out", "w") as fo, open(tmp_path / "err", "w") as fe:
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "4", "--no-extra",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "4", "--full", "--no-extra",
                             "--no-cpu-baseline", "--collective", collective], env=env, stdout=fo, stderr=fe,
                            stdin=subprocess.DEVNULL, timeout=500)
     stdout, stderr = (tmp_path / "out").read_text(), (tmp_path / "err").read_text()

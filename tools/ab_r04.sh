@@ -3,7 +3,7 @@ out=$1; shift
 mkdir -p $out
 for spec in "$@"; do
   set -- $spec; name=$1; shift
-  env "$@" python bench.py --steps 60 --warmup 15 --no-extra --no-cpu-baseline > $out/ab_$name.json 2> $out/ab_$name.err
+  env "$@" python bench.py --steps 60 --warmup 15 --full --no-extra --no-cpu-baseline > $out/ab_$name.json 2> $out/ab_$name.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ replayed plan (tools/overlap_probe.py, no tracer) show both pairs starting withi
 durations and per-queue totals from the trace are sound; cross-queue ORDER is not.
 wall time, GPU-busy union, concurrency histogram, per-kernel totals, largest idle gaps.
 Usage: python tools/timeline.py <results.db> [n_gaps] [step]   (step: index of the optimizer step to analyse, counted over the whole
-trace by its sumsq kernel; default -2 = the last complete one -- with bench.py that is one of the host-enqueue probe steps, which
+trace by its sumsq kernel; default -2 = the last complete one -- with bench.py --full that is one of the host-enqueue probe steps, which
 run against an EMPTY queue; pick one inside the timed loop, e.g. warmup + 3)"""
 import re
 import sqlite3
