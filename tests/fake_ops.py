@@ -53,8 +53,12 @@ def dropout_keep_matrix(seed, n_problems, nq_cap, n_rows, n_cols, p_drop):
 
 
 class FakeOps:
-    def __init__(self, dtype):
+    def __init__(self, dtype, compute=torch.float32):
+        """compute: the element type of the arithmetic (fp32 by default; torch.float64 turns this restatement into the
+        high-precision reference of tests/bounds.py).  Tensors may live on any one device: every index / mask tensor made
+        here is made on the device of the operands."""
         self.dtype = dtype
+        self.compute = compute
         self.calls = []
         self.step_seed = None
 
@@ -77,45 +81,45 @@ class FakeOps:
     def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1,
              out_f32=False, epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
         self.calls.append(("gemm", M, N, K, a_kmajor, b_kmajor, epilogue))
-        a = (v2(A, M, K, lda) if a_kmajor else v2(A, K, M, lda).t()).float()
-        b = (v2(B, N, K, ldb) if b_kmajor else v2(B, K, N, ldb).t()).float()
+        a = (v2(A, M, K, lda) if a_kmajor else v2(A, K, M, lda).t()).to(self.compute)
+        b = (v2(B, N, K, ldb) if b_kmajor else v2(B, K, N, ldb).t()).to(self.compute)
         acc = alpha * (a @ b.t())
         if bias is not None:
-            acc = acc + torch.as_strided(bias, (N,), (1,)).float()[None, :]
+            acc = acc + torch.as_strided(bias, (N,), (1,)).to(self.compute)[None, :]
         if epilogue == EPI_GELU:
             v2(aux, M, N, ldx).copy_(acc)
             acc = torch.nn.functional.gelu(acc)
         elif epilogue == EPI_RESIDUAL:
             if p_drop > 0:
-                acc = acc * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop)
-            acc = acc + v2(residual, M, N, ldr).float()
+                acc = acc * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop).to(acc.device)
+            acc = acc + v2(residual, M, N, ldr).to(self.compute)
         elif epilogue == EPI_DGELU:
-            acc = acc * gelu_grad(v2(aux, M, N, ldx).float())
+            acc = acc * gelu_grad(v2(aux, M, N, ldx).to(self.compute))
         elif epilogue == EPI_TANH:
             acc = torch.tanh(acc)
         elif epilogue == EPI_GELU_DG:         # the derivative is saved instead of the pre-activation
             v2(aux, M, N, ldx).copy_(gelu_grad(acc))
             acc = torch.nn.functional.gelu(acc)
         elif epilogue == EPI_MULAUX:
-            acc = acc * v2(aux, M, N, ldx).float()
+            acc = acc * v2(aux, M, N, ldx).to(self.compute)
         elif epilogue == EPI_ROWMAX:           # no C: per row and 64-column segment {max, sum exp(x - max), argmax bits, 0} -> aux
             assert N % 64 == 0
             seg = acc.view(M, N // 64, 64)
             mx, am = seg.max(-1)
             se = torch.exp(seg - mx[..., None]).sum(-1)
-            idx = (am + torch.arange(N // 64)[None, :] * 64).to(torch.int32)
+            idx = (am + torch.arange(N // 64, device=am.device)[None, :] * 64).to(torch.int32)
             rec = torch.stack([mx, se, idx.view(torch.float32), torch.zeros_like(mx)], -1)     # [M, nseg, 4]
             aux.view(-1)[:(N // 64) * M * 4].copy_(rec.permute(1, 0, 2).reshape(-1))
             return
         c = v2(C, M, N, ldc)
         if out_f32:
-            assert C.dtype == torch.float32
+            assert C.dtype in (torch.float32, self.compute)
         if accumulate:
             c.add_(acc)
         else:
             c.copy_(acc)
         if colsum is not None:
-            torch.as_strided(colsum, (N,), (1,)).add_(c.float().sum(0))
+            torch.as_strided(colsum, (N,), (1,)).add_(c.to(self.compute).sum(0))
 
     def set_deferred_reduce(self, on):
         pass                                   # the host restatement always reduces at once
@@ -155,7 +159,7 @@ class FakeOps:
         return (x - mean) * rstd * g + b, mean[:, 0], rstd[:, 0]
 
     def layernorm_fwd(self, x, gamma, beta, y, mean, rstd, M, N, eps):
-        o, m, r = self._ln(v2(x, M, N, N).float(), gamma.float(), beta.float(), eps)
+        o, m, r = self._ln(v2(x, M, N, N).to(self.compute), gamma.to(self.compute), beta.to(self.compute), eps)
         v2(y, M, N, N).copy_(o)
         mean[:M].copy_(m)
         rstd[:M].copy_(r)
@@ -174,18 +178,19 @@ class FakeOps:
 
     def layernorm_bwd(self, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dbias_prev, M, N, ws=None, dx_dropped=None,
                       p_drop=0.0, seed=0):
-        d, dg, db = self._ln_bwd(v2(dy, M, N, N).float(), v2(x, M, N, N).float(), gamma.float(), mean[:M], rstd[:M])
+        d, dg, db = self._ln_bwd(v2(dy, M, N, N).to(self.compute), v2(x, M, N, N).to(self.compute), gamma.to(self.compute),
+                                 mean[:M], rstd[:M])
         v2(dx, M, N, N).copy_(d)
         dgamma.add_(dg)
         dbeta.add_(db)
         if dx_dropped is not None and p_drop > 0:
-            d = d * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop)                         # the kernel masks the fp32 value, then rounds
+            d = d * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop).to(d.device)                         # the kernel masks the fp32 value, then rounds
             v2(dx_dropped, M, N, N).copy_(d)
         if dbias_prev is not None:
             dbias_prev.add_(d.sum(0))
 
     def visn_ln_fwd(self, xv, pos, wbox, bbox, gv, bv, gb, bb, y, mean_v, rstd_v, mean_b, rstd_b, M, N, P, eps):
-        a, mv, rv = self._ln(v2(xv, M, N, N).float(), gv, bv, eps)
+        a, mv, rv = self._ln(v2(xv, M, N, N).to(self.compute), gv, bv, eps)
         box = pos.view(M, P) @ wbox.view(N, P).t() + bbox
         b, mb, rb = self._ln(box, gb, bb, eps)
         v2(y, M, N, N).copy_((a + b) / 2)
@@ -193,8 +198,8 @@ class FakeOps:
 
     def visn_ln_bwd(self, dy, xv, pos, wbox, bbox, gv, gb, mean_v, rstd_v, mean_b, rstd_b, dxv, dgv, dbv, dgb, dbb,
                     dwbox, dbbox, dbias_visn, M, N, P, ws=None):
-        dh = v2(dy, M, N, N).float() * 0.5
-        d1, dg1, db1 = self._ln_bwd(dh, v2(xv, M, N, N).float(), gv, mean_v, rstd_v)
+        dh = v2(dy, M, N, N).to(self.compute) * 0.5
+        d1, dg1, db1 = self._ln_bwd(dh, v2(xv, M, N, N).to(self.compute), gv, mean_v, rstd_v)
         box = pos.view(M, P) @ wbox.view(N, P).t() + bbox
         d2, dg2, db2 = self._ln_bwd(dh, box, gb, mean_b, rstd_b)
         v2(dxv, M, N, N).copy_(d1)
@@ -206,15 +211,16 @@ class FakeOps:
 
     def embed_ln_fwd(self, ids, tt, word, pos, type_, gamma, beta, y, pre, mean, rstd, B, L, N, eps):
         M = B * L
-        p = (word[ids.view(-1)].float() + pos[torch.arange(L).repeat(B)].float() + type_[tt.view(-1)].float())
+        p = (word[ids.view(-1)].to(self.compute) + pos[torch.arange(L, device=pos.device).repeat(B)].to(self.compute)
+             + type_[tt.view(-1)].to(self.compute))
         v2(pre, M, N, N).copy_(p)
-        o, m, r = self._ln(v2(pre, M, N, N).float(), gamma, beta, eps)
+        o, m, r = self._ln(v2(pre, M, N, N).to(self.compute), gamma, beta, eps)
         v2(y, M, N, N).copy_(o)
         mean.copy_(m); rstd.copy_(r)
 
     def embed_bwd(self, dpre, ids, tt, dword, dpos, dtype_tab, B, L, N, order=None, n_types=2):
         M = B * L
-        d = v2(dpre, M, N, N).float()
+        d = v2(dpre, M, N, N).to(self.compute)
         if order is not None:              # the loader's stable argsort of the ids: rows sorted by (id, row)
             key = ids.view(-1)[order.long()]
             assert sorted(order.tolist()) == list(range(M)) and bool((key[1:] >= key[:-1]).all())
@@ -222,36 +228,36 @@ class FakeOps:
             assert bool((order[1:][same] > order[:-1][same]).all())
         idf = ids.view(-1)
         ttf = tt.view(-1) if tt is not None else torch.zeros_like(idf)
-        lf = torch.arange(L).repeat(B)
+        lf = torch.arange(L, device=d.device).repeat(B)
         dword.index_add_(0, idf[idf != 0], d[idf != 0])
         dpos.index_add_(0, lf[lf != 0], d[lf != 0])
         dtype_tab.index_add_(0, ttf[ttf != 0], d[ttf != 0])
 
     def codebook_gather(self, cluster_ids, vis_mask, centroids, mask_feat, feats, M, F):
-        f = centroids[cluster_ids.view(-1)].float()
+        f = centroids[cluster_ids.view(-1)].to(self.compute)
         if vis_mask is not None:
             f = torch.where(vis_mask.view(-1, 1) != 0, mask_feat.view(1, -1), f)
         v2(feats, M, F, F).copy_(f)
 
     def masked_colsum(self, x, mask, out, M, N, ldx, ws=None):
-        xx = v2(x, M, N, ldx).float()
+        xx = v2(x, M, N, ldx).to(self.compute)
         out[:N].add_((xx * (mask.view(-1, 1) != 0)).sum(0))
 
     def colsum(self, x, out, M, N, ldx, ws=None):
-        torch.as_strided(out, (N,), (1,)).add_(v2(x, M, N, ldx).float().sum(0))
+        torch.as_strided(out, (N,), (1,)).add_(v2(x, M, N, ldx).to(self.compute).sum(0))
 
     def dropout(self, x, y, M, N, ldx, ldy, p_drop, seed):
-        v2(y, M, N, ldy).copy_(v2(x, M, N, ldx).float() * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop))
+        v2(y, M, N, ldy).copy_(v2(x, M, N, ldx).to(self.compute) * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop).to(x.device))
 
     def gelu_bwd(self, dy, pre, dx, n):
-        dx.view(-1)[:n].copy_(dy.reshape(-1)[:n].float() * gelu_grad(pre.reshape(-1)[:n].float()))
+        dx.view(-1)[:n].copy_(dy.reshape(-1)[:n].to(self.compute) * gelu_grad(pre.reshape(-1)[:n].to(self.compute)))
 
     def tanh_bwd(self, dy, y, dx, n):
-        yf = y.reshape(-1)[:n].float()
-        dx.view(-1)[:n].copy_(dy.reshape(-1)[:n].float() * (1.0 - yf * yf))
+        yf = y.reshape(-1)[:n].to(self.compute)
+        dx.view(-1)[:n].copy_(dy.reshape(-1)[:n].to(self.compute) * (1.0 - yf * yf))
 
     def bce_logits_fwd_bwd(self, logits, targets, dlogits, loss, M, N, ld_logits, ld_targets, ld_dlogits):
-        x, t = v2(logits, M, N, ld_logits).float(), v2(targets, M, N, ld_targets).float()
+        x, t = v2(logits, M, N, ld_logits).to(self.compute), v2(targets, M, N, ld_targets).to(self.compute)
         loss[0] += torch.nn.functional.binary_cross_entropy_with_logits(x, t)
         if dlogits is not None:
             d = v2(dlogits, M, ld_dlogits, ld_dlogits)
@@ -287,20 +293,21 @@ class FakeOps:
         return torch.as_strided(t, (B, H, n, dh), (n * ld, dh, ld, 1))
 
     @staticmethod
-    def _pmask(B, H, nq, nk, p_drop, seed):
+    def _pmask(B, H, nq, nk, p_drop, seed, device=None):
         if p_drop == 0:
             return 1.0
         row = torch.arange(B * H * nq).view(B, H, nq, 1)                # (b*H+h)*nq+q
-        return keep_scale(seed, row, torch.arange(nk).view(1, 1, 1, nk), p_drop)
+        return keep_scale(seed, row, torch.arange(nk).view(1, 1, 1, nk), p_drop).to(device)
 
     # packed rows (include/xlxmert_hip.h xl_sdpa_*: q_rowoff / k_rowoff): unpack into the dense [B, H, n, dh] layout (zeros beyond
     # an example's length), compute as ever with the missing keys masked, store the real rows back, zero the pad tail
     def _load(self, t, B, n, H, dh, ld, off):
         if off is None:
-            return self._heads(t, B, n, H, dh, ld).float(), None
+            return self._heads(t, B, n, H, dh, ld).to(self.compute), None
         off = [int(x) for x in off.view(-1)[:B + 1]]
-        mat = torch.as_strided(t, (off[B], H * dh), (ld, 1)).float()
-        out, valid = torch.zeros(B, n, H * dh), torch.zeros(B, n, dtype=torch.bool)
+        mat = torch.as_strided(t, (off[B], H * dh), (ld, 1)).to(self.compute)
+        out = torch.zeros(B, n, H * dh, dtype=self.compute, device=t.device)
+        valid = torch.zeros(B, n, dtype=torch.bool, device=t.device)
         for b_ in range(B):
             m = min(n, off[b_ + 1] - off[b_])
             out[b_, :m] = mat[off[b_]:off[b_] + m]
@@ -333,7 +340,7 @@ class FakeOps:
         if kv is not None:
             s = s.masked_fill(~kv.view(B, 1, 1, nk), float("-inf"))
         lse.view(B, H, nq).copy_(torch.logsumexp(s, -1))
-        out = (torch.softmax(s, -1) * self._pmask(B, H, nq, nk, p_drop, self._seed(seed))) @ V_
+        out = (torch.softmax(s, -1) * self._pmask(B, H, nq, nk, p_drop, self._seed(seed), s.device)) @ V_
         self._store(o, out, B, nq, H, dh, ldo, q_off, q_pad)
 
     def attn_probs(self, q, k, key_mask, lse, probs, B, H, nq, nk, dh, ldq, ldk, scale, p_drop=0.0, seed=0, q_off=None, k_off=None):
@@ -346,7 +353,7 @@ class FakeOps:
         if qv is not None:
             p = p.masked_fill(~qv.view(B, 1, nq, 1), 0.0)
         p = torch.nan_to_num(p, nan=0.0, posinf=0.0)
-        probs.view(B, H, nq, nk).copy_(p * self._pmask(B, H, nq, nk, p_drop, self._seed(seed)))
+        probs.view(B, H, nq, nk).copy_(p * self._pmask(B, H, nq, nk, p_drop, self._seed(seed), p.device))
 
     def sdpa_bwd(self, q, k, v, key_mask, dout, lse, dq, dk, dv, B, H, nq, nk, dh, ldq, ldk, ldv, ldo, lddq, lddk,
                  lddv, scale, p_drop=0.0, seed=0, bias_grad=None, ws=None, q_off=None, k_off=None, q_pad=0, k_pad=0, keep_bits=None):
@@ -361,7 +368,7 @@ class FakeOps:
         if qv is not None:                                   # queries beyond an example's length do not exist
             p = p.masked_fill(~qv.view(B, 1, nq, 1), 0.0)
         p = torch.nan_to_num(p, nan=0.0, posinf=0.0)
-        msk = self._pmask(B, H, nq, nk, p_drop, self._seed(seed))
+        msk = self._pmask(B, H, nq, nk, p_drop, self._seed(seed), p.device)
         dp = (dO @ V_.transpose(-1, -2)) * msk
         delta = (p * dp).sum(-1, keepdim=True)
         ds = p * (dp - delta) * scale
@@ -376,8 +383,8 @@ class FakeOps:
                 bias_grad[i * HD:(i + 1) * HD] += g.sum(dim=(0, 2)).reshape(HD)       # [B,H,n,dh] -> [H*dh]
 
     def mask_counts(self, labels, vis_mask, counts, nmask, B, V):
-        counts[0] = (labels != -100).sum().float()
-        nmask.copy_((vis_mask.view(B, V) != 0).sum(1).float())
+        counts[0] = (labels != -100).sum().to(self.compute)
+        nmask.copy_((vis_mask.view(B, V) != 0).sum(1).to(self.compute))
 
     def ce_fwd_bwd(self, logits, labels, counts, dlogits, loss_out, row_lse, row_argmax, row_maxprob, M, K, ldl, lddl,
                    grad_scale=1.0):
@@ -400,21 +407,21 @@ class FakeOps:
             loss_out[0] += nll.sum() / cnt
         if dlogits is not None:
             g = torch.softmax(lg, 1)
-            g[torch.arange(M), safe] -= 1.0
+            g[torch.arange(M, device=g.device), safe] -= 1.0
             g = g * valid[:, None] * (grad_scale / cnt)
             v2(dlogits, M, K, lddl).copy_(g)
 
     def featloss_fwd_bwd(self, pred, centroids, cluster_ids, vis_mask, nmask, dpred, loss_out, B, V, F, grad_scale=1.0,
                          rows=None, n_rows=0, targets=None):
-        g = torch.arange(B * V) if rows is None else rows.view(-1)[:n_rows].long()
+        g = torch.arange(B * V, device=pred.device) if rows is None else rows.view(-1)[:n_rows].long()
         pad = g < 0                      # padding entries of the row list: no loss, zero gradient row
         g = g.clamp(min=0)
         M = g.numel()
-        p = v2(pred, M, F, F).float()
-        t = (centroids[cluster_ids.view(-1)[g]] if targets is None else targets.view(B * V, F)[g]).float()
+        p = v2(pred, M, F, F).to(self.compute)
+        t = (centroids[cluster_ids.view(-1)[g]] if targets is None else targets.view(B * V, F)[g]).to(self.compute)
         d = p - t
         sl1 = torch.where(d.abs() < 1, 0.5 * d * d, d.abs() - 0.5).mean(1)
-        w = ((vis_mask.view(-1) != 0).float() / (nmask.clamp(min=1).repeat_interleave(V) * B))[g]
+        w = ((vis_mask.view(-1) != 0).to(self.compute) / (nmask.clamp(min=1).repeat_interleave(V) * B))[g]
         w = torch.where(pad, torch.zeros_like(w), w)
         if loss_out is not None:
             loss_out[0] += (w * sl1).sum()
@@ -450,7 +457,7 @@ class FakeOps:
         out.view(-1)[:n_rows].copy_(torch.where(g >= 0, labels.view(-1)[g.clamp(min=0)], torch.full_like(g, -100)))
 
     def sumsq(self, g, out, n, scratch=None):
-        out[0] += (g[:n].double() ** 2).sum().float()
+        out[0] += (g[:n].double() ** 2).sum().to(self.compute)
 
     def schedule_step(self, step, base_lr, warmup_steps, total_steps, beta1, beta2, lr_and_steps):
         step[0] += 1
@@ -466,16 +473,16 @@ class FakeOps:
         if max_norm > 0 and sumsq is not None:
             norm = math.sqrt(float(sumsq[0])) * grad_scale
             clip *= min(1.0, max_norm / (norm + 1e-6))
-        fl = decay_flags.repeat_interleave(256)[:n] if decay_flags is not None else torch.zeros(n, dtype=torch.uint8)
+        fl = decay_flags.repeat_interleave(256)[:n] if decay_flags is not None else torch.zeros(n, dtype=torch.uint8, device=p.device)
         act = (fl & 2) == 0                                    # bit 1: tensor without a gradient this step -> untouched
         gg = g[:n] * clip
         m_new = m[:n] * beta1 + gg * (1 - beta1)
         v_new = v[:n] * beta2 + gg * gg * (1 - beta2)
         if chunk_steps is not None:
             t = chunk_steps.repeat_interleave(256)[:n].double().clamp(min=1)
-            step = (lr * torch.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)).float()
+            step = (lr * torch.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)).to(self.compute)
         else:
-            step = torch.full((n,), lr * math.sqrt(bc2) / bc1)
+            step = torch.full((n,), lr * math.sqrt(bc2) / bc1, dtype=self.compute, device=p.device)
         p_new = p[:n] - step * (m_new / (v_new.sqrt() + eps))
         if weight_decay > 0:
             dec = (fl & 1) != 0

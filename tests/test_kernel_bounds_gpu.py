@@ -1,0 +1,822 @@
+"""Every numeric library call of one real bf16 training step, checked element by element against the float64 restatement
+(tests/fake_ops.FakeOps(..., compute=torch.float64), run on the device) within the bounds of tests/bounds.py.
+
+The step: the benchmarked geometry (bs 256, 20 text tokens packed, 64 grid tokens, 9/5/5 layers, d 768, 10k codebook, canonical
+visual_losses="obj"), dropout on, eager (no launch plan), optimizer in line.  Its HipOps is wrapped by a recording proxy: the first
+call of every kernel-selecting signature is run on snapshots of its operands and compared; a numeric method without a checker
+fails the test."""
+import inspect
+import time
+
+import pytest
+import torch
+
+import bounds as BD
+import lxmert_oracle as O
+from fake_ops import FakeOps, keep_scale
+
+pytestmark = pytest.mark.gpu
+
+CFG_KEYS = ("vocab_size", "hidden_size", "num_attention_heads", "intermediate_size", "max_position_embeddings",
+            "type_vocab_size", "l_layers", "x_layers", "r_layers", "visual_feat_dim", "visual_pos_dim", "num_clusters")
+
+# library calls that compute nothing a later call reads as a number of this step's result: memsets, stream / event plumbing,
+# switches, size queries, workspace registration
+NON_NUMERIC = {"zero", "stream_fork", "new_event", "event_record", "stream_wait", "set_step_seed_ptr", "set_deferred_reduce",
+               "workspace_floats", "gemm_workspace", "sumsq_scratch", "sdpa_keep_bits_bytes", "wgrad_group_one_writer",
+               "rebind", "bound", "forget_binding", "gemm_trace"}
+
+
+def _is_setter(name):
+    return name.startswith("set_")
+
+
+def _al16(t):
+    return None if t is None else t.data_ptr() % 16 == 0
+
+
+def _v2(t, r, c, ld):
+    return torch.as_strided(t, (r, c), (ld, 1))
+
+
+def gemm_kernel(M, N, K, lda, ldb, A, B, out_f32, epilogue):
+    """the kernel xl_gemm's dispatch (csrc/gemm.hip, default switches) selects for these arguments"""
+    mfma = A.dtype == torch.bfloat16 and lda % 8 == 0 and ldb % 8 == 0 and _al16(A) and _al16(B)
+    if not mfma:
+        return "generic 64x64"
+    may_split = out_f32 and epilogue == BD.EPI_NONE
+    t256 = ((M + 255) // 256) * ((N + 255) // 256)
+    blocks = t256 * max(1, min(256 // t256, K // 512)) if (may_split and t256 < 256 and K >= 1024) else t256
+    pp = K % 8 == 0 and blocks >= 48
+    tile = 256 if pp else 128
+    tiles = ((M + tile - 1) // tile) * ((N + tile - 1) // tile)
+    want = 256 if pp else 768
+    split = max(1, min(want // tiles if pp else (want + tiles - 1) // tiles, K // 512)) if (may_split and tiles < want and K >= 1024) else 1
+    name = "ping-pong 256x256" if pp else "MFMA 128x128 / duo 128x192"
+    if split > 1:
+        name += f" split-K {split}"
+    if pp and K >= 4096 and not may_split:
+        name += " (tail split eligible)"
+    if (M % tile or N % tile):
+        name += " + scalar edge epilogue"
+    return name
+
+
+class Recorder:
+    """stands in for the step's HipOps: forwards every attribute, checks the first call of each signature"""
+
+    def __init__(self, ops):
+        object.__setattr__(self, "_ops", ops)
+        object.__setattr__(self, "_ref", FakeOps(ops.dtype, compute=torch.float64))
+        object.__setattr__(self, "_seen", set())
+        object.__setattr__(self, "rows", [])
+        object.__setattr__(self, "called", set())
+        object.__setattr__(self, "unchecked", set())
+        object.__setattr__(self, "failures", [])
+
+    def __setattr__(self, k, v):
+        setattr(self._ops, k, v)
+
+    def __getattr__(self, name):
+        attr = getattr(self._ops, name)
+        if not callable(attr) or name.startswith("_"):
+            return attr
+        if name == "set_step_seed_ptr":
+            def fwd(step_seed):
+                self._ref.set_step_seed_ptr(step_seed)
+                return attr(step_seed)
+            return fwd
+        if name in NON_NUMERIC or _is_setter(name):
+            return attr
+        if name == "gemm_pair":
+            def pair(c0, c1):
+                self.gemm(*c0.a, **c0.kw)
+                self.gemm(*c1.a, **c1.kw)
+            return pair
+        chk = getattr(self, "chk_" + name, None)
+
+        def call(*args, **kw):
+            self.called.add(name)
+            if chk is None:
+                self.unchecked.add(name)
+                return attr(*args, **kw)
+            sig = inspect.signature(attr)
+            ba = sig.bind(*args, **kw)
+            ba.apply_defaults()
+            a = dict(ba.arguments)
+            key = self._signature(name, a)
+            if key in self._seen:
+                return attr(*args, **kw)
+            self._seen.add(key)
+            torch.cuda.synchronize()
+            cache = {}
+            s = {k: self._snap(v, cache) for k, v in a.items()}
+
+            ran = []
+
+            def run():
+                ran.append(1)
+                r = attr(*args, **kw)
+                torch.cuda.synchronize()
+                return r
+            try:
+                res = chk(a, s, run)
+            except Exception as e:          # (a checker that fails still leaves the call done: the step goes on)
+                if not ran:
+                    run()
+                self.failures.append(f"{name} {self._short(a)}: {type(e).__name__}: {e}")
+                print(f"FAILED {self.failures[-1]}", flush=True)
+                return None
+            for what, ratio, kernel in res:
+                self.rows.append((name, what, self._short(a), kernel, ratio))
+            print(f"checked {name} {self._short(a)}", flush=True)
+            return None
+        return call
+
+    # -- snapshots: every tensor operand's whole storage, float64 for floating types (aliasing between operands is kept)
+    def _snap(self, v, cache):
+        if isinstance(v, torch.Tensor):
+            st = v.untyped_storage()
+            key = (st.data_ptr(), v.dtype)
+            if key not in cache:
+                n = st.nbytes() // v.element_size()
+                base = torch.tensor([], dtype=v.dtype, device=v.device).set_(st, 0, (n,), (1,))
+                cache[key] = base.double() if v.is_floating_point() else base.clone()
+            return torch.as_strided(cache[key], v.shape, v.stride(), v.storage_offset())
+        if isinstance(v, (list, tuple)):
+            return type(v)(self._snap(x, cache) for x in v)
+        return v
+
+    @staticmethod
+    def _signature(name, a):
+        def one(v):
+            if isinstance(v, torch.Tensor):
+                return ("T", v.dtype, _al16(v))
+            if isinstance(v, float):
+                return v > 0
+            if isinstance(v, (list, tuple)):
+                return tuple(one(x) for x in v)
+            if v is None:
+                return None
+            return v
+        skip = {"seed", "alpha", "scale", "base_lr", "eps", "grad_scale", "beta1", "beta2", "weight_decay", "max_norm"}
+        return (name,) + tuple((k, one(v)) for k, v in a.items() if k not in skip)
+
+    @staticmethod
+    def _short(a):
+        keys = ("M", "N", "K", "B", "H", "nq", "nk", "n", "V", "L", "n_rows", "epilogue", "accumulate")
+        return " ".join(f"{k}={a[k]}" for k in keys if k in a and not isinstance(a[k], torch.Tensor))
+
+    # ------------------------------------------------------------------------------------------------ contractions
+    def _gemm_pre(self, s, M, N, K):
+        A = (_v2(s["A"], M, K, s["lda"]) if s["a_kmajor"] else _v2(s["A"], K, M, s["lda"]).t())
+        B = (_v2(s["B"], N, K, s["ldb"]) if s["b_kmajor"] else _v2(s["B"], K, N, s["ldb"]).t())
+        al = float(s["alpha"])
+        pre = al * (A @ B.t())
+        absprod = abs(al) * (A.abs() @ B.abs().t())
+        if s["bias"] is not None:
+            b = torch.as_strided(s["bias"], (N,), (1,))
+            pre, absprod = pre + b[None, :], absprod + b.abs()[None, :]
+        return pre, absprod
+
+    def chk_gemm(self, a, s, run):
+        M, N, K, epi = a["M"], a["N"], a["K"], a["epilogue"]
+        assert epi != BD.EPI_ROWMAX, "the training step does not issue the ROWMAX epilogue"
+        pre, absprod = self._gemm_pre(s, M, N, K)
+        prev = _v2(s["C"], M, N, a["ldc"]).clone() if a["accumulate"] else None
+        aux_in = _v2(s["aux"], M, N, a["ldx"]).clone() if epi in (BD.EPI_DGELU, BD.EPI_MULAUX) else None
+        cs_prev = torch.as_strided(s["colsum"], (N,), (1,)).clone() if a["colsum"] is not None else None
+        keep = None
+        if epi == BD.EPI_RESIDUAL and a["p_drop"] > 0:
+            keep = keep_scale(self._ref._seed(a["seed"]), torch.arange(M)[:, None], torch.arange(N)[None, :], a["p_drop"])
+            keep = keep.to(pre.device).double()
+        run()
+        self._ref.gemm(**{k: v for k, v in s.items()})
+        out_dt = torch.float32 if a["out_f32"] else a["C"].dtype
+        ref_c = _v2(s["C"], M, N, a["ldc"])
+        ref_aux = _v2(s["aux"], M, N, a["ldx"]) if epi in (BD.EPI_GELU, BD.EPI_GELU_DG) else None
+        bc, ba = BD.gemm_bounds(pre, absprod, K, epi, out_dt, ref_c, aux_in=aux_in, ref_aux=ref_aux, keep=keep,
+                                aux_dtype=a["C"].dtype)
+        if prev is not None:
+            bc = bc + BD.SLACK * BD.U32 * (prev.abs() + ref_c.abs())
+        kern = gemm_kernel(M, N, K, a["lda"], a["ldb"], a["A"], a["B"], a["out_f32"], epi)
+        res = [("C", BD.check(_v2(a["C"], M, N, a["ldc"]), ref_c, bc, "gemm C"), kern)]
+        if ba is not None:
+            res.append(("aux", BD.check(_v2(a["aux"], M, N, a["ldx"]), ref_aux, ba, "gemm aux"), kern))
+        if a["colsum"] is not None:
+            ref_cs = torch.as_strided(s["colsum"], (N,), (1,))
+            bcs = BD.colsum_bound(bc, ref_c, cs_prev)
+            res.append(("colsum", BD.check(torch.as_strided(a["colsum"], (N,), (1,)), ref_cs, bcs, "gemm colsum"), kern))
+        return res
+
+    def chk_gemm_wgrad_group(self, a, s, run):
+        probs, mask = s["problems"], a["overwrite_mask"]
+        pre = []
+        for i, (A, B, C, M, N, K, lda, ldb, ldc) in enumerate(probs):
+            p, ab = self._gemm_pre(dict(A=A, B=B, lda=lda, ldb=ldb, a_kmajor=0, b_kmajor=0, alpha=1.0, bias=None), M, N, K)
+            prev = None if (mask >> i) & 1 else _v2(C, M, N, ldc).clone()
+            pre.append((p, ab, prev))
+        run()
+        self._ref.gemm_wgrad_group(probs, mask)
+        res = []
+        for i, ((A, B, C, M, N, K, lda, ldb, ldc), (p, ab, prev)) in enumerate(zip(probs, pre)):
+            ref_c = _v2(C, M, N, ldc)
+            bc, _ = BD.gemm_bounds(p, ab, K, BD.EPI_NONE, torch.float32, ref_c)
+            if prev is not None:
+                bc = bc + BD.SLACK * BD.U32 * (prev.abs() + ref_c.abs())
+            kern = gemm_kernel(M, N, K, lda, ldb, a["problems"][i][0], a["problems"][i][1], True, 0)
+            res.append((f"dW[{i}] {M}x{N}x{K}" + (" overwrite" if prev is None else ""),
+                        BD.check(_v2(a["problems"][i][2], M, N, ldc), ref_c, bc, f"wgrad problem {i}"), "grouped " + kern))
+        return res
+
+    # ------------------------------------------------------------------------------------------------ attention
+    def _att(self, s, a):
+        return BD.attention_inputs(self._ref, s["q"], s["k"], s["v"], s["key_mask"], a["B"], a["H"], a["nq"], a["nk"], a["dh"],
+                                   a["ldq"], a["ldk"], a["ldv"], a["p_drop"], a["seed"], s["q_off"], s["k_off"])
+
+    def chk_sdpa_fwd(self, a, s, run):
+        B, H, nq, nk, dh = a["B"], a["H"], a["nq"], a["nk"], a["dh"]
+        Q, K, V, valid, keep = self._att(s, a)
+        run()
+        self._ref.sdpa_fwd(**s)
+        # an example whose keys are all masked: a softmax over no key (NaN in the restatement); the kernels' convention is a zero
+        # row (and lse = -inf), which the bound below (P' = 0 there) holds to within TINY
+        BD.attention_rows(self._ref, s["o"], B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"]).nan_to_num_(0.0)
+        O_, _ = self._ref._load(s["o"], B, nq, H, dh, a["ldo"], s["q_off"])
+        lse = s["lse"].reshape(-1)[:B * H * nq].view(B, H, nq)
+        bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, a["scale"], O_, lse)
+        rows = lambda t: BD.attention_rows(self._ref, t, B, nq, H, dh, a["ldo"], a["q_off"], a["q_pad"])   # noqa: E731
+        ref_rows = BD.attention_rows(self._ref, s["o"], B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"])
+        bO = BD.attention_scatter(self._ref, bO, B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"])[:ref_rows.shape[0]]
+        exist = valid.any(-1).expand(B, H, nq)
+        kern = f"sdpa_fwd_mfma{' + dropout' if a['p_drop'] > 0 else ''}{' packed' if a['q_off'] is not None else ''}"
+        got_l = a["lse"].reshape(-1)[:B * H * nq].view(B, H, nq)
+        return [("O", BD.check(rows(a["o"]), ref_rows, bO, "sdpa_fwd O"), kern),
+                ("lse", BD.check(got_l[exist], lse[exist], bl[exist], "sdpa_fwd lse"), kern)]
+
+    def chk_sdpa_bwd(self, a, s, run):
+        B, H, nq, nk, dh = a["B"], a["H"], a["nq"], a["nk"], a["dh"]
+        Q, K, V, valid, keep = self._att(s, a)
+        dO, _ = self._ref._load(s["dout"], B, nq, H, dh, a["ldo"], s["q_off"])
+        lse = s["lse"].reshape(-1)[:B * H * nq].view(B, H, nq).clone()
+        bias_prev = s["bias_grad"].clone() if a["bias_grad"] is not None else None
+        run()
+        self._ref.sdpa_bwd(**s)
+        sides = (("dq", nq, "lddq", "q_off", "q_pad"), ("dk", nk, "lddk", "k_off", "k_pad"), ("dv", nk, "lddv", "k_off", "k_pad"))
+        dense = [self._ref._load(s[nm], B, n, H, dh, a[ld], s[off])[0] for nm, n, ld, off, _ in sides]
+        bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, a["scale"], lse, *dense)
+        kern = f"sdpa_bwd_mfma{' + dropout' if a['p_drop'] > 0 else ''}{' keep_bits' if a['keep_bits'] is not None else ''}" \
+               f"{' packed' if a['q_off'] is not None else ''}"
+        res = []
+        HD = H * dh
+        for (nm, n, ld, off, pad), b, t in zip(sides, bounds, terms):
+            ref_rows = BD.attention_rows(self._ref, s[nm], B, n, H, dh, a[ld], s[off], a[pad])
+            got_rows = BD.attention_rows(self._ref, a[nm], B, n, H, dh, a[ld], a[off], a[pad])
+            bb = BD.attention_scatter(self._ref, b, B, n, H, dh, a[ld], s[off], a[pad])[:ref_rows.shape[0]]
+            res.append((nm, BD.check(got_rows, ref_rows, bb, f"sdpa_bwd {nm}"), kern))
+            if bias_prev is not None:
+                i = "dq dk dv".split().index(nm)
+                tt = BD.attention_scatter(self._ref, t, B, n, H, dh, a[ld], s[off], a[pad])[:ref_rows.shape[0]]
+                ref_b = s["bias_grad"][i * HD:(i + 1) * HD]
+                bnd = BD.SLACK * tt.sum(0) + BD.SLACK * (ref_rows.shape[0] + 1) * BD.U32 * (ref_rows.abs().sum(0)
+                                                                                        + bias_prev[i * HD:(i + 1) * HD].abs()) \
+                    + BD.U32 * ref_b.abs() + BD.TINY
+                res.append((f"bias {nm}", BD.check(a["bias_grad"][i * HD:(i + 1) * HD], ref_b, bnd, f"sdpa_bwd bias {nm}"), kern))
+        return res
+
+    # ------------------------------------------------------------------------------------------------ LayerNorm family
+    def chk_layernorm_fwd(self, a, s, run):
+        M, N = a["M"], a["N"]
+        run()
+        self._ref.layernorm_fwd(**s)
+        x, y = _v2(s["x"], M, N, N).clone(), _v2(s["y"], M, N, N)
+        by, bm, br = BD.ln_fwd_bounds(x, s["gamma"].double(), y, s["mean"][:M], s["rstd"][:M], a["y"].dtype)
+        kern = "ln_fwd_kernel"
+        return [("y", BD.check(_v2(a["y"], M, N, N), y, by, "layernorm_fwd y"), kern),
+                ("mean", BD.check(a["mean"][:M], s["mean"][:M], bm, "layernorm_fwd mean"), kern),
+                ("rstd", BD.check(a["rstd"][:M], s["rstd"][:M], br, "layernorm_fwd rstd"), kern)]
+
+    def chk_layernorm_bwd(self, a, s, run):
+        M, N = a["M"], a["N"]
+        dy, x = _v2(s["dy"], M, N, N).clone(), _v2(s["x"], M, N, N).clone()
+        mean, rstd = s["mean"][:M].clone(), s["rstd"][:M].clone()
+        prev = {k: s[k].clone() for k in ("dgamma", "dbeta", "dbias_prev") if s[k] is not None}
+        assert "dgamma" in prev and "dbeta" in prev
+        keep = None
+        if a["dx_dropped"] is not None and a["p_drop"] > 0:
+            keep = keep_scale(self._ref._seed(a["seed"]), torch.arange(M)[:, None], torch.arange(N)[None, :], a["p_drop"])
+            keep = keep.to(dy.device).double()
+        run()
+        self._ref.layernorm_bwd(**s)
+        dx = _v2(s["dx"], M, N, N)
+        bdx, t, bdg, bdb = BD.ln_bwd_bounds(dy, x, s["gamma"].double(), mean, rstd, dx, a["dx"].dtype)
+        kern = "ln_bwd_dma_kernel" if (M >= 16384 and N == 768) else "ln_bwd_kernel"
+        res = [("dx", BD.check(_v2(a["dx"], M, N, N), dx, bdx, "layernorm_bwd dx"), kern),
+               ("dgamma", BD.check(a["dgamma"], s["dgamma"], bdg + BD.U32 * (s["dgamma"].abs() + prev["dgamma"].abs()),
+                                   "layernorm_bwd dgamma"), kern),
+               ("dbeta", BD.check(a["dbeta"], s["dbeta"], bdb + BD.U32 * (s["dbeta"].abs() + prev["dbeta"].abs()),
+                                  "layernorm_bwd dbeta"), kern)]
+        if keep is not None:
+            dd = _v2(s["dx_dropped"], M, N, N)
+            bdd = BD.U16 * dd.abs() + BD.SLACK * keep * t + BD.TINY
+            res.append(("dx_dropped", BD.check(_v2(a["dx_dropped"], M, N, N), dd, bdd, "layernorm_bwd dx_dropped"), kern))
+            if a["dbias_prev"] is not None:
+                ref = s["dbias_prev"]
+                bb = (BD.U16 * dd.abs() + BD.SLACK * keep * t).sum(0) + BD.SLACK * (M + 1) * BD.U32 * (
+                    dd.abs().sum(0) + prev["dbias_prev"].abs()) + BD.U32 * ref.abs() + BD.TINY
+                res.append(("dbias_prev", BD.check(a["dbias_prev"], ref, bb, "layernorm_bwd dbias_prev"), kern))
+        return res
+
+    def _box(self, s, M, N, P):
+        pos, w, b = s["pos"].reshape(-1)[:M * P].view(M, P), s["wbox"].reshape(-1)[:N * P].view(N, P), s["bbox"].reshape(-1)[:N]
+        box = pos @ w.t() + b
+        err = (P + 1) * BD.U32 * (pos.abs() @ w.abs().t() + b.abs())
+        return box, err, pos
+
+    def chk_visn_ln_fwd(self, a, s, run):
+        M, N, P = a["M"], a["N"], a["P"]
+        xv = _v2(s["xv"], M, N, N).clone()
+        box, berr, _ = self._box(s, M, N, P)
+        run()
+        self._ref.visn_ln_fwd(**s)
+        ya, mv, rv = FakeOps._ln(xv, s["gv"].double(), s["bv"].double(), a["eps"])
+        yb, mb, rb = FakeOps._ln(box, s["gb"].double(), s["bb"].double(), a["eps"])
+        y = _v2(s["y"], M, N, N)
+        b1, bmv, brv = BD.ln_fwd_bounds(xv, s["gv"].double(), ya, mv, rv, torch.float64)
+        b2, bmb, brb = BD.ln_fwd_bounds(box, s["gb"].double(), yb, mb, rb, torch.float64, x_err=berr)
+        by = BD.unit(a["y"].dtype) * y.abs() + 0.5 * (b1 + b2) + BD.SLACK * BD.U32 * y.abs()
+        kern = "visn_ln_fwd"
+        return [("y", BD.check(_v2(a["y"], M, N, N), y, by, "visn_ln_fwd y"), kern),
+                ("mean_v", BD.check(a["mean_v"][:M], s["mean_v"][:M], bmv, "visn mean_v"), kern),
+                ("rstd_v", BD.check(a["rstd_v"][:M], s["rstd_v"][:M], brv, "visn rstd_v"), kern),
+                ("mean_b", BD.check(a["mean_b"][:M], s["mean_b"][:M], bmb + BD.SLACK * berr.amax(-1), "visn mean_b"), kern),
+                ("rstd_b", BD.check(a["rstd_b"][:M], s["rstd_b"][:M],
+                                    brb + BD.SLACK * 2 * rb.abs() ** 3 * berr.amax(-1) * (box - mb[:, None]).abs().amax(-1),
+                                    "visn rstd_b"), kern)]
+
+    def chk_visn_ln_bwd(self, a, s, run):
+        M, N, P = a["M"], a["N"], a["P"]
+        dh = _v2(s["dy"], M, N, N).clone() * 0.5
+        xv = _v2(s["xv"], M, N, N).clone()
+        box, berr, pos = self._box(s, M, N, P)
+        pos = pos.clone()
+        mean_v, rstd_v, mean_b, rstd_b = (s[k][:M].clone() for k in ("mean_v", "rstd_v", "mean_b", "rstd_b"))
+        names = ("dgv", "dbv", "dgb", "dbb", "dwbox", "dbbox", "dbias_visn")
+        prev = {k: s[k].clone() for k in names if s[k] is not None}
+        run()
+        self._ref.visn_ln_bwd(**s)
+        d1, _, _ = FakeOps._ln_bwd(dh, xv, s["gv"].double(), mean_v, rstd_v)
+        d2, _, _ = FakeOps._ln_bwd(dh, box, s["gb"].double(), mean_b, rstd_b)
+        b1, t1, bg1, bb1 = BD.ln_bwd_bounds(dh, xv, s["gv"].double(), mean_v, rstd_v, d1, a["dxv"].dtype)
+        _, t2, bg2, bb2 = BD.ln_bwd_bounds(dh, box, s["gb"].double(), mean_b, rstd_b, d2, torch.float64, x_err=berr)
+        t2 = BD.SLACK * t2
+        kern = "visn_ln_bwd"
+
+        def acc(k, bnd):
+            ref = s[k].reshape(-1)
+            return BD.check(a[k].reshape(-1), ref, bnd.reshape(-1) + BD.U32 * (ref.abs() + prev[k].reshape(-1).abs()), f"visn {k}")
+        dw_terms = (d2.abs().t() @ pos.abs())
+        res = [("dxv", BD.check(_v2(a["dxv"], M, N, N), _v2(s["dxv"], M, N, N), b1, "visn_ln_bwd dxv"), kern),
+               ("dgv", acc("dgv", bg1), kern), ("dbv", acc("dbv", bb1), kern), ("dgb", acc("dgb", bg2), kern),
+               ("dbb", acc("dbb", bb2), kern),
+               ("dwbox", acc("dwbox", t2.t() @ pos.abs() + BD.SLACK * (M + 1) * BD.U32 * dw_terms), kern),
+               ("dbbox", acc("dbbox", t2.sum(0) + BD.SLACK * (M + 1) * BD.U32 * d2.abs().sum(0)), kern)]
+        if a["dbias_visn"] is not None:
+            res.append(("dbias_visn", acc("dbias_visn", (BD.U16 * d1.abs() + BD.SLACK * t1).sum(0)
+                                          + BD.SLACK * (M + 1) * BD.U32 * d1.abs().sum(0)), kern))
+        return res
+
+    def chk_embed_ln_fwd(self, a, s, run):
+        B, L, N = a["B"], a["L"], a["N"]
+        M = B * L
+        run()
+        self._ref.embed_ln_fwd(**s)
+        pre = _v2(s["pre"], M, N, N)
+        wsum = (s["word"][s["ids"].reshape(-1).long()].abs() + s["pos"][torch.arange(L, device=pre.device).repeat(B)].abs()
+                + s["type_"][s["tt"].reshape(-1).long()].abs())
+        bpre = BD.unit(a["pre"].dtype) * pre.abs() + BD.SLACK * 2 * BD.U32 * wsum + BD.TINY
+        kern = "embed_ln_fwd"
+        res = [("pre", BD.check(_v2(a["pre"], M, N, N), pre, bpre, "embed pre"), kern)]
+        gpre = _v2(a["pre"], M, N, N).double()              # the kernel normalises the STORED sum (csrc/rowops.hip)
+        y, m, r = FakeOps._ln(gpre, s["gamma"].double(), s["beta"].double(), a["eps"])
+        by, bm, br = BD.ln_fwd_bounds(gpre, s["gamma"].double(), y, m, r, a["y"].dtype)
+        res += [("y", BD.check(_v2(a["y"], M, N, N), y, by, "embed y"), kern),
+                ("mean", BD.check(a["mean"][:M], m, bm, "embed mean"), kern),
+                ("rstd", BD.check(a["rstd"][:M], r, br, "embed rstd"), kern)]
+        return res
+
+    def chk_embed_bwd(self, a, s, run):
+        B, L, N = a["B"], a["L"], a["N"]
+        M = B * L
+        tabs = ("dword", "dpos", "dtype_tab")
+        absd = {k: s[k].abs() for k in tabs}                 # |prev| + sum of |terms| (the same scatter on absolute values)
+        sa = dict(s, dpre=_v2(s["dpre"], M, N, N).abs().contiguous(), **absd)
+        run()
+        self._ref.embed_bwd(**sa)
+        self._ref.embed_bwd(**s)
+        return [(k, BD.check(a[k], s[k], BD.U32 * s[k].abs() + BD.SLACK * (M + 1) * BD.U32 * sa[k] + BD.TINY, f"embed_bwd {k}"),
+                 "embed_bwd (sorted rows)" if a["order"] is not None else "embed_bwd (scan)") for k in tabs]
+
+    # ------------------------------------------------------------------------------------------------ elementwise / copies
+    def chk_codebook_gather(self, a, s, run):
+        M, F = a["M"], a["F"]
+        run()
+        self._ref.codebook_gather(**s)
+        ref = _v2(s["feats"], M, F, F)
+        return [("feats", BD.check(_v2(a["feats"], M, F, F), ref, BD.unit(a["feats"].dtype) * ref.abs() + BD.TINY, "codebook"),
+                 "codebook_gather")]
+
+    def chk_dropout(self, a, s, run):
+        M, N = a["M"], a["N"]
+        run()
+        self._ref.dropout(**s)
+        ref = _v2(s["y"], M, N, a["ldy"])
+        return [("y", BD.check(_v2(a["y"], M, N, a["ldy"]), ref, BD.scaled_copy_bound(ref, a["y"].dtype), "dropout"), "dropout")]
+
+    def chk_gelu_bwd(self, a, s, run):
+        n = a["n"]
+        dy, pre = s["dy"].reshape(-1)[:n].clone(), s["pre"].reshape(-1)[:n].clone()
+        run()
+        self._ref.gelu_bwd(**s)
+        ref = s["dx"].reshape(-1)[:n]
+        return [("dx", BD.check(a["dx"].reshape(-1)[:n], ref, BD.gelu_bwd_bound(dy, pre, ref, a["dx"].dtype), "gelu_bwd"),
+                 "gelu_bwd (A-S erf)")]
+
+    def chk_tanh_bwd(self, a, s, run):
+        n = a["n"]
+        dy, y = s["dy"].reshape(-1)[:n].clone(), s["y"].reshape(-1)[:n].clone()
+        run()
+        self._ref.tanh_bwd(**s)
+        ref = s["dx"].reshape(-1)[:n]
+        return [("dx", BD.check(a["dx"].reshape(-1)[:n], ref, BD.tanh_bwd_bound(dy, y, ref, a["dx"].dtype), "tanh_bwd"), "tanh_bwd")]
+
+    def _colsum_like(self, name, a, s, run):
+        M, N = a["M"], a["N"]
+        sa = dict(s, x=_v2(s["x"], M, N, a["ldx"]).abs().contiguous(), ldx=N, out=s["out"].abs())
+        run()
+        getattr(self._ref, name)(**sa)
+        getattr(self._ref, name)(**s)
+        ref = s["out"][:N]
+        bnd = BD.U32 * ref.abs() + BD.SLACK * (M + 1) * BD.U32 * sa["out"][:N] + BD.TINY
+        return [("out", BD.check(a["out"][:N], ref, bnd, name), name + " (two-stage)")]
+
+    def chk_colsum(self, a, s, run):
+        return self._colsum_like("colsum", a, s, run)
+
+    def chk_masked_colsum(self, a, s, run):
+        return self._colsum_like("masked_colsum", a, s, run)
+
+    def _cast(self, name, a, s, run):
+        n = a["n"]
+        run()
+        getattr(self._ref, name)(**s)
+        ref = s["dst"].reshape(-1)[:n]
+        return [("dst", BD.check(a["dst"].reshape(-1)[:n], ref, BD.unit(a["dst"].dtype) * ref.abs() + BD.TINY, name), name)]
+
+    def chk_cast_from_f32(self, a, s, run):
+        return self._cast("cast_from_f32", a, s, run)
+
+    def chk_cast_to_f32(self, a, s, run):
+        return self._cast("cast_to_f32", a, s, run)
+
+    def chk_gather_rows(self, a, s, run):
+        n, N = a["n_rows"], a["N"]
+        run()
+        self._ref.gather_rows(**s)
+        return [("dst", BD.check_exact(_v2(a["dst"], n, N, a["ld_dst"]).double(), _v2(s["dst"], n, N, a["ld_dst"]), "gather_rows"),
+                 "gather_rows")]
+
+    def chk_scatter_rows(self, a, s, run):
+        n, N = a["n_rows"], a["N"]
+        rows = int(a["rows"].reshape(-1)[:n].max()) + 1
+        run()
+        self._ref.scatter_rows(**s)
+        return [("dst", BD.check_exact(_v2(a["dst"], rows, N, a["ld_dst"]).double(), _v2(s["dst"], rows, N, a["ld_dst"]),
+                                       "scatter_rows"), "scatter_rows")]
+
+    def chk_gather_labels(self, a, s, run):
+        n = a["n_rows"]
+        run()
+        self._ref.gather_labels(**s)
+        return [("out", BD.check_exact(a["out"].reshape(-1)[:n], s["out"].reshape(-1)[:n], "gather_labels"), "gather_labels")]
+
+    def chk_mask_counts(self, a, s, run):
+        B, V = a["B"], a["V"]
+        run()
+        self._ref.mask_counts(**s)
+        return [("counts", BD.check_exact(a["counts"][:1].double(), s["counts"][:1], "mask_counts"), "mask_counts"),
+                ("nmask", BD.check_exact(a["nmask"][:B].double(), s["nmask"][:B], "mask_counts nmask"), "mask_counts")]
+
+    # ------------------------------------------------------------------------------------------------ losses
+    def chk_ce_fwd_bwd(self, a, s, run):
+        M, K = a["M"], a["K"]
+        lg = _v2(s["logits"], M, K, a["ldl"]).clone()
+        loss_prev = s["loss_out"].clone() if a["loss_out"] is not None else None
+        run()
+        self._ref.ce_fwd_bwd(**s)
+        lab = s["labels"].reshape(-1)[:M].long() if a["labels"] is not None else None
+        valid = (lab != -100).double() if lab is not None else torch.zeros(M, dtype=torch.float64, device=lg.device)
+        cnt = float(s["counts"][0].clamp(min=1)) if a["counts"] is not None else 1.0
+        lse = torch.logsumexp(lg, 1)
+        dl = _v2(s["dlogits"], M, K, a["lddl"]) if a["dlogits"] is not None else torch.zeros_like(lg)
+        blse, bdl = BD.ce_bounds(lg, valid, a["grad_scale"] / cnt, lse, dl, a["dlogits"].dtype if a["dlogits"] is not None
+                                 else torch.float32)
+        kern = "ce_fwd_bwd"
+        res = []
+        if a["dlogits"] is not None:
+            res.append(("dlogits", BD.check(_v2(a["dlogits"], M, K, a["lddl"]), dl, bdl, "ce dlogits"), kern))
+        if a["row_lse"] is not None:
+            res.append(("row_lse", BD.check(a["row_lse"][:M], s["row_lse"][:M], blse, "ce row_lse"), kern))
+        if a["row_argmax"] is not None:
+            got = a["row_argmax"][:M].long()
+            mx = lg.amax(1)
+            res.append(("row_argmax", BD.check_exact(lg.gather(1, got[:, None])[:, 0], mx, "ce row_argmax (value at the index)"), kern))
+            unique = (lg == mx[:, None]).sum(1) == 1
+            res.append(("row_argmax idx", BD.check_exact(got[unique], s["row_argmax"][:M].long()[unique], "ce row_argmax"), kern))
+        if a["row_maxprob"] is not None:
+            ref = s["row_maxprob"][:M]
+            res.append(("row_maxprob", BD.check(a["row_maxprob"][:M], ref, BD.SLACK * ref.abs() * (blse + 2 * BD.U32) + BD.U32 * ref.abs()
+                                                + BD.TINY, "ce row_maxprob"), kern))
+        if a["loss_out"] is not None and lab is not None:
+            ref = s["loss_out"][0]
+            bl = BD.ce_loss_bound(lg, lab, valid, cnt, blse, float(ref)) + BD.U32 * float(loss_prev[0].abs())
+            res.append(("loss", BD.check(a["loss_out"][:1], s["loss_out"][:1], bl, "ce loss"), kern))
+        return res
+
+    def chk_featloss_fwd_bwd(self, a, s, run):
+        B, V, F = a["B"], a["V"], a["F"]
+        n = B * V if a["rows"] is None else a["n_rows"]
+        run()
+        self._ref.featloss_fwd_bwd(**s)
+        g = torch.arange(B * V, device=s["pred"].device) if a["rows"] is None else s["rows"].reshape(-1)[:n].long()
+        pad = g < 0
+        g = g.clamp(min=0)
+        pred = _v2(s["pred"], n, F, F)
+        tgt = (s["centroids"][s["cluster_ids"].reshape(-1)[g].long()] if a["targets"] is None else s["targets"].view(B * V, F)[g])
+        w = ((s["vis_mask"].reshape(-1) != 0).double() / (s["nmask"].clamp(min=1).repeat_interleave(V) * B))[g]
+        w = torch.where(pad, torch.zeros_like(w), w)
+        dref = _v2(s["dpred"], n, F, F) if a["dpred"] is not None else torch.zeros_like(pred)
+        lb, bd = BD.featloss_bounds(pred, tgt, w, F, dref, float(s["loss_out"][0]) if a["loss_out"] is not None else 0.0,
+                                    a["dpred"].dtype if a["dpred"] is not None else torch.float32)
+        res = []
+        if a["dpred"] is not None:
+            res.append(("dpred", BD.check(_v2(a["dpred"], n, F, F), dref, bd, "featloss dpred"), "featloss_fwd_bwd"))
+        if a["loss_out"] is not None:
+            res.append(("loss", BD.check(a["loss_out"][:1], s["loss_out"][:1], lb, "featloss loss"), "featloss_fwd_bwd"))
+        return res
+
+    # ------------------------------------------------------------------------------------------------ optimizer
+    def chk_sumsq(self, a, s, run):
+        n = a["n"]
+        prev = float(s["out"][0])
+        run()
+        self._ref.sumsq(**s)
+        ref = s["out"][:1]
+        bnd = BD.sumsq_bound(s["g"][:n], float(ref)) + BD.U32 * abs(prev)
+        return [("out", BD.check(a["out"][:1], ref, bnd, "sumsq"), f"sumsq_kernel ({n} elements)")]
+
+    def chk_schedule_step(self, a, s, run):
+        run()
+        self._ref.schedule_step(**s)
+        ref = s["lr_and_steps"][:4]
+        t = float(ref[3])
+        scale = torch.tensor([abs(float(ref[0])), a["beta1"] ** t, a["beta2"] ** t, 0.0], dtype=torch.float64, device=ref.device)
+        bnd = BD.SLACK * 4 * BD.U32 * scale + BD.U32 * ref.abs() + BD.TINY
+        return [("step", BD.check_exact(a["step"][:1], s["step"][:1], "schedule step"), "schedule_step"),
+                ("lr_and_steps", BD.check(a["lr_and_steps"][:4], ref, bnd, "schedule lr_and_steps"), "schedule_step")]
+
+    def chk_adamw(self, a, s, run):
+        n = a["n"]
+        g0, m0, v0 = (s[k][:n].clone() for k in ("g", "m", "v"))
+        lrs = [float(x) for x in s["lr_and_steps"][:3]]
+        clip = a["grad_scale"]
+        if a["max_norm"] > 0 and a["sumsq"] is not None:
+            norm = float(s["sumsq"][0]) ** 0.5 * a["grad_scale"]
+            clip *= min(1.0, a["max_norm"] / (norm + 1e-6))
+        assert a["chunk_steps"] is None
+        step = lrs[0] * lrs[2] ** 0.5 / lrs[1]
+        run()
+        self._ref.adamw(**s)
+        bp, bm, bv = BD.adamw_bounds(s["p"][:n], s["m"][:n], s["v"][:n], g0, m0, v0, step, clip, a["beta1"], a["beta2"], a["eps"],
+                                     lrs[0], a["weight_decay"])
+        del g0, m0, v0
+        res = [("p", BD.check(a["p"][:n], s["p"][:n], bp, "adamw p"), "adamw"),
+               ("m", BD.check(a["m"][:n], s["m"][:n], bm, "adamw m"), "adamw"),
+               ("v", BD.check(a["v"][:n], s["v"][:n], bv, "adamw v"), "adamw")]
+        if a["p_compute"] is not None and a["p_compute"].data_ptr() != a["p"].data_ptr():
+            ref = s["p_compute"][:n]
+            res.append(("p_compute", BD.check(a["p_compute"][:n], ref, BD.unit(a["p_compute"].dtype) * ref.abs() + bp, "adamw p_compute"),
+                        "adamw"))
+        if a["zero_grad"]:
+            ref = s["g"][:n]
+            kept = torch.isnan(ref)                  # the restatement poisons the chunks the kernel leaves alone
+            res.append(("g cleared", BD.check_exact(a["g"][:n][~kept].double(), ref[~kept], "adamw zero_grad"), "adamw"))
+        return res
+
+
+def _table(rows, seconds):
+    print(f"\n{'op':<22} {'output':<22} {'shape':<52} {'kernel':<44} {'headroom':>9}")
+    for name, what, shape, kern, ratio in rows:
+        head = "exact" if ratio == 0 else f"{1.0 / ratio:9.1f}x"
+        print(f"{name:<22} {what[:22]:<22} {shape[:52]:<52} {kern[:44]:<44} {head:>9}")
+    print(f"{len(rows)} outputs checked in {seconds:.1f} s")
+
+
+def test_every_numeric_call_of_a_bf16_training_step_is_within_its_bound(monkeypatch):
+    """one training step (forward, backward, clip + AdamW) of the benchmarked geometry with dropout on; every numeric method the
+    step calls is checked at the first call of each signature (method, shapes, leading dimensions, layouts, epilogue, output type,
+    accumulate, dropout on / off, column sums / workspace present, 16-byte alignment)"""
+    t0 = time.time()
+    monkeypatch.setenv("XL_DEFER_REDUCE", "0")             # column sums complete at their own call
+    from xlxmert_amd.config import XLxmertConfig
+    from xlxmert_amd.ops import HipOps
+    from xlxmert_amd.params import ParamStore
+    from xlxmert_amd.trainer import PretrainStep, synthetic_batch
+    cfg = XLxmertConfig()
+    oc = O.OracleConfig(**{k: getattr(cfg, k) for k in CFG_KEYS})
+    sd = O.make_state_dict(oc, 2718)
+    B = 256
+    store = ParamStore(cfg, "cuda", torch.bfloat16)
+    store.load_named(sd)
+    rec = Recorder(HipOps(torch.bfloat16))
+    tr = PretrainStep(cfg, B, 20, 64, dtype=torch.bfloat16, device="cuda", store=store, lr=1e-4, total_steps=1000, warmup_ratio=0.0,
+                      plan=False,
+                      drop_grads=False, overlap_optimizer=False, train_dropout=True, ops=rec)
+    batch = synthetic_batch(cfg, B, 20, 8, seed=31)
+    dev = {k: v.cuda() for k, v in batch.items()}
+    losses = tr.step(dev)
+    tr.sync()
+    torch.cuda.synchronize()
+    assert tr.engine.packed, "the language rows ran dense: the packed attention paths were not exercised"
+    assert all(torch.isfinite(torch.as_tensor(x)).all() for x in losses if x is not None)
+    _table(rec.rows, time.time() - t0)
+    assert not rec.unchecked, f"numeric methods without a checker: {sorted(rec.unchecked)}"
+    assert not rec.failures, "\n".join(rec.failures)
+    for must in ("gemm", "gemm_wgrad_group", "sdpa_fwd", "sdpa_bwd", "layernorm_fwd", "layernorm_bwd", "ce_fwd_bwd", "sumsq", "adamw"):
+        assert must in rec.called, must
+    print(f"methods called: {sorted(rec.called)}; run time {time.time() - t0:.1f} s")
+
+
+# ---------------------------------------------------------------------------------------------------------------- edge cases
+# The same checkers on random bf16 data at what the step does not reach.  Every call below is a new signature, so every one is
+# checked; the test fails on any bound exceeded.
+def _rec():
+    from xlxmert_amd.ops import HipOps
+    return Recorder(HipOps(torch.bfloat16))
+
+
+def _done(rec, t0, n_min):
+    _table(rec.rows, time.time() - t0)
+    assert not rec.unchecked, sorted(rec.unchecked)
+    assert not rec.failures, "\n".join(rec.failures)
+    assert len(rec.rows) >= n_min, len(rec.rows)
+
+
+def _rn(g, *shape, scale=1.0):
+    return (torch.randn(*shape, generator=g, device="cuda") * scale).to(torch.bfloat16)
+
+
+@pytest.mark.parametrize("pingpong", [1, 2], ids=["default_dispatch", "pingpong_forced"])
+def test_gemm_ragged_tiles_padded_ld_and_short_k_within_bounds(pingpong):
+    """M, N off the tile grid, leading dimensions padded by 8 elements, K not a multiple of 64, every fast epilogue (the ragged
+    edge tiles take the scalar erff epilogue, the interior the A-S one: both inside one output), pre-activations spread to |x| ~ 10"""
+    t0 = time.time()
+    rec = _rec()
+    rec.set_gemm_pingpong(pingpong)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    for M, N, K in ((300, 264, 200), (520, 776, 840)):
+        lda = ldb = K + 8
+        ldc = N + 8
+        A, W = _rn(g, M, lda, scale=3.0), _rn(g, N, ldb, scale=1.0 / K ** 0.5)
+        bias = torch.randn(N, generator=g, device="cuda") * 0.5
+        res, aux_in = _rn(g, M, ldc), _rn(g, M, ldc, scale=3.0)
+        for epi, p in ((BD.EPI_NONE, 0.0), (BD.EPI_GELU, 0.0), (BD.EPI_RESIDUAL, 0.1), (BD.EPI_DGELU, 0.0), (BD.EPI_GELU_DG, 0.0),
+                       (BD.EPI_TANH, 0.0), (BD.EPI_MULAUX, 0.0)):
+            C = torch.zeros(M, ldc, dtype=torch.bfloat16, device="cuda")
+            aux = aux_in.clone()
+            rec.gemm(A, W, C, bias, res, aux, M, N, K, lda, ldb, ldc, ldr=ldc, ldx=ldc, epilogue=epi, p_drop=p, seed=11)
+        C = torch.randn(M, ldc, generator=g, device="cuda")
+        rec.gemm(A, W, C, None, None, None, M, N, K, lda, ldb, ldc, out_f32=True, accumulate=1)
+        C = torch.zeros(M, ldc, dtype=torch.bfloat16, device="cuda")
+        cs, ws = torch.zeros(N, device="cuda"), torch.zeros(rec.workspace_floats(N), device="cuda")
+        rec.gemm(A, W, C, bias, None, None, M, N, K, lda, ldb, ldc, colsum=cs, ws=ws)
+    _done(rec, t0, 24)
+
+
+def test_gelu_bwd_tails_within_bound():
+    t0 = time.time()
+    rec = _rec()
+    g = torch.Generator(device="cuda").manual_seed(6)
+    n = 10008                               # (a multiple of the kernel's 8-element vector; not of its block)
+    pre = (torch.linspace(-10, 10, n, device="cuda") + torch.randn(n, generator=g, device="cuda") * 0.1).to(torch.bfloat16)
+    dy = _rn(g, n)
+    rec.gelu_bwd(dy, pre, torch.zeros(n, dtype=torch.bfloat16, device="cuda"), n)
+    _done(rec, t0, 1)
+
+
+@pytest.mark.parametrize("nq,nk", [(1, 33), (33, 1), (33, 33), (1, 1), (64, 33)])
+def test_attention_short_sides_and_an_all_masked_example_within_bounds(nq, nk):
+    """dense attention with nq or nk of 1 and 33, dropout on, example 1's keys all masked (kernel convention: zero output rows,
+    zero gradients), forward and backward (saved keep bits where the geometry has them)"""
+    t0 = time.time()
+    rec = _rec()
+    g = torch.Generator(device="cuda").manual_seed(7)
+    B, H, dh = 4, 12, 64
+    ld = 3 * H * dh
+    qkv = _rn(g, B * max(nq, nk), ld)
+    q, k, v = qkv, qkv[:, H * dh:], qkv[:, 2 * H * dh:]
+    km = (torch.rand(B, nk, generator=g, device="cuda") > 0.3).to(torch.uint8)
+    km[:, 0] = 1
+    km[1] = 0
+    o = torch.zeros(B * nq, H * dh, dtype=torch.bfloat16, device="cuda")
+    lse = torch.zeros(B * H * nq, device="cuda")
+    kbn = rec.sdpa_keep_bits_bytes(B, H, nq, nk, dh)
+    kb = torch.zeros(max(kbn, 4) // 4, dtype=torch.int32, device="cuda") if kbn else None
+    rec.sdpa_fwd(q, k, v, km, o, lse, B, H, nq, nk, dh, ld, ld, ld, H * dh, 0.125, p_drop=0.1, seed=3, keep_bits=kb)
+    dout = _rn(g, B * nq, H * dh)
+    dq, dk, dv = (torch.zeros(B * n, H * dh, dtype=torch.bfloat16, device="cuda") for n in (nq, nk, nk))
+    bg = torch.zeros(3 * H * dh, device="cuda")
+    rec.sdpa_bwd(q, k, v, km, dout, lse, dq, dk, dv, B, H, nq, nk, dh, ld, ld, ld, H * dh, H * dh, H * dh, H * dh, 0.125,
+                 p_drop=0.1, seed=3, bias_grad=bg, keep_bits=kb)
+    _done(rec, t0, 5)
+
+
+def test_attention_packed_with_one_token_examples_within_bounds():
+    t0 = time.time()
+    rec = _rec()
+    g = torch.Generator(device="cuda").manual_seed(8)
+    B, H, dh, n = 5, 12, 64, 20
+    lens = torch.tensor([1, 20, 7, 1, 13])
+    off = torch.zeros(B + 1, dtype=torch.int32)
+    off[1:] = torch.cumsum(lens, 0)
+    off = off.cuda()
+    rows, pad = int(off[-1]), 64
+    ld = 3 * H * dh
+    qkv = torch.zeros(pad, ld, dtype=torch.bfloat16, device="cuda")
+    qkv[:rows] = _rn(g, rows, ld)
+    q, k, v = qkv, qkv[:, H * dh:], qkv[:, 2 * H * dh:]
+    o = torch.zeros(pad, H * dh, dtype=torch.bfloat16, device="cuda")
+    lse = torch.zeros(B * H * n, device="cuda")
+    kbn = rec.sdpa_keep_bits_bytes(B, H, n, n, dh)
+    kb = torch.zeros(max(kbn, 4) // 4, dtype=torch.int32, device="cuda") if kbn else None
+    rec.sdpa_fwd(q, k, v, None, o, lse, B, H, n, n, dh, ld, ld, ld, H * dh, 0.125, p_drop=0.1, seed=4, q_off=off, k_off=off,
+                 q_pad=pad, k_pad=pad, keep_bits=kb)
+    dout = torch.zeros(pad, H * dh, dtype=torch.bfloat16, device="cuda")
+    dout[:rows] = _rn(g, rows, H * dh)
+    dq, dk, dv = (torch.zeros(pad, H * dh, dtype=torch.bfloat16, device="cuda") for _ in range(3))
+    rec.sdpa_bwd(q, k, v, None, dout, lse, dq, dk, dv, B, H, n, n, dh, ld, ld, ld, H * dh, H * dh, H * dh, H * dh, 0.125,
+                 p_drop=0.1, seed=4, q_off=off, k_off=off, q_pad=pad, k_pad=pad, keep_bits=kb)
+    _done(rec, t0, 5)
+
+
+@pytest.mark.parametrize("M", [300, 16384], ids=["ragged_rows", "dma_variant"])
+def test_layernorm_rows_with_mean_100x_std_within_bounds(M):
+    """pins the two-pass statistics: E[x^2] - E[x]^2 in fp32 loses every digit of the variance on these rows"""
+    t0 = time.time()
+    rec = _rec()
+    g = torch.Generator(device="cuda").manual_seed(9)
+    N = 768
+    x = (100.0 + torch.randn(M, N, generator=g, device="cuda")).to(torch.bfloat16)
+    gamma = 1 + 0.1 * torch.randn(N, generator=g, device="cuda")
+    beta = 0.1 * torch.randn(N, generator=g, device="cuda")
+    y = torch.zeros(M, N, dtype=torch.bfloat16, device="cuda")
+    mean, rstd = torch.zeros(M, device="cuda"), torch.zeros(M, device="cuda")
+    rec.layernorm_fwd(x, gamma, beta, y, mean, rstd, M, N, 1e-12)
+    dy = _rn(g, M, N)
+    dx, dxd = (torch.zeros(M, N, dtype=torch.bfloat16, device="cuda") for _ in range(2))
+    dg, db, dbp = (torch.zeros(N, device="cuda") for _ in range(3))
+    ws = torch.zeros(rec.workspace_floats(N), device="cuda")
+    rec.layernorm_bwd(dy, x, gamma, mean, rstd, dx, dg, db, dbp, M, N, ws=ws, dx_dropped=dxd, p_drop=0.1, seed=5)
+    _done(rec, t0, 8)
+
+
+def test_cross_entropy_10k_classes_padded_stride_logits_to_80_within_bounds():
+    t0 = time.time()
+    rec = _rec()
+    g = torch.Generator(device="cuda").manual_seed(10)
+    M, K, ld = 300, 10000, 10016
+    logits = (torch.rand(M, ld, generator=g, device="cuda") * 160 - 80).to(torch.bfloat16).float()
+    labels = torch.randint(0, K, (M,), generator=g, device="cuda")
+    labels[::7] = -100
+    counts = torch.tensor([float((labels != -100).sum())], device="cuda")
+    dl = torch.zeros(M, ld, dtype=torch.bfloat16, device="cuda")
+    loss, lse, mp = torch.zeros(1, device="cuda"), torch.zeros(M, device="cuda"), torch.zeros(M, device="cuda")
+    am = torch.zeros(M, dtype=torch.int32, device="cuda")
+    rec.ce_fwd_bwd(logits, labels, counts, dl, loss, lse, am, mp, M, K, ld, ld)
+    _done(rec, t0, 5)
+
+
+def test_featloss_not_in_the_canonical_recipe_within_bounds():
+    t0 = time.time()
+    rec = _rec()
+    g = torch.Generator(device="cuda").manual_seed(11)
+    B, V, F, K = 8, 64, 2048, 500
+    pred = _rn(g, B * V, F)
+    cent = _rn(g, K, F)
+    cid = torch.randint(0, K, (B, V), generator=g, device="cuda")
+    vm = (torch.rand(B, V, generator=g, device="cuda") < 0.15).to(torch.uint8)
+    nm = vm.sum(1).float()
+    dpred = torch.zeros(B * V, F, dtype=torch.bfloat16, device="cuda")
+    loss = torch.zeros(1, device="cuda")
+    rec.featloss_fwd_bwd(pred, cent, cid, vm, nm, dpred, loss, B, V, F)
+    _done(rec, t0, 2)
