@@ -345,3 +345,217 @@ def attention_scatter(ref, dense, B, n, H, dh, ld, off, pad):
     dst = torch.zeros(rows * ld + H * dh, dtype=torch.float64, device=dense.device)
     ref._store(dst, dense, B, n, H, dh, ld, off, pad)
     return attention_rows(ref, dst, B, n, H, dh, ld, off, pad)
+
+
+# ------------------------------------------------------------------------------------------------------------------ sampler head
+# Transcendental constants (not derivable; the places this file already takes them from): v_exp_f32 2 ulp (ERF_ABS above, as in
+# sdpa_fwd_bounds), v_rcp_f32 / an IEEE division 1 ulp (csrc/common.h, the comment at the A-S erf's __builtin_amdgcn_rcpf),
+# logf / __logf on a sum >= 1: 2 U32 |log| + 2^-21 (ce_bounds).  __expf(x) is v_exp_f32(x log2 e): the scaling of the argument
+# rounds once more, U32 |x| relative to the result.
+EXP_ULP = 2.0
+RCP_ULP = 1.0
+LOG_ABS = 2.0 ** -21
+
+
+def rowmax_logit_error(pre, absdot, bias_abs, K):
+    """per-logit error e of the XL_EPI_ROWMAX accumulator, as gemm_bounds has it: K U32 (|alpha||A||B|^T + |bias|) + 2 U32 |pre| --
+    except where the contraction has no non-zero product (absdot == 0: an all-zero operand row, the zero rows that pad the
+    codebook): 0 alpha + bias is exact there, e = 0.  So a padded column (bias -1e30) carries no error allowance at all."""
+    e = K * U32 * (absdot + bias_abs) + 2 * U32 * pre.abs()
+    return torch.where(absdot == 0, torch.zeros_like(e), e)
+
+
+def rowmax_record_bounds(pre, e):
+    """records of the XL_EPI_ROWMAX epilogue, aux[(n/64) M + m] = {max, sum exp(x - max), argmax bits, 0} per row and 64-column
+    segment; pre [M, N] float64 logits (bias added), e from rowmax_logit_error.  With E = max of e over the segment:
+      max       the maximum of perturbed values is within the largest perturbation of the true maximum: SLACK E + U32 |max|
+      sum exp   every exponent x_n - max moves by at most 2 E (first order: 2 E relative in that term); its rounding and the
+                __expf scaling add 2 U32 t_n, t_n = max - x_n, relative in the term (the partial maxima of the 8-column lanes and
+                of the three butterfly levels telescope to the same t_n); four exp (4 EXP_ULP U32), three multiplies and <= 11
+                additions on a term's way to the segment sum: (4 EXP_ULP + 14) U32.  Sum over the terms w_n = exp(-t_n):
+                U32 sum + SLACK ((2 E + (4 EXP_ULP + 14) U32) sum + 2 U32 sum_n t_n w_n)
+    A padded column has t_n = 1e30 next to any real column: w_n = 0 exactly, in the reference and -- exp underflows -- in fp32.
+    Returns (ref max, ref sum, E, bound of max, bound of sum), each [M, N / 64]."""
+    M, N = pre.shape
+    x, ee = pre.view(M, N // 64, 64), e.view(M, N // 64, 64)
+    mx, E = x.amax(-1), ee.amax(-1)
+    t = mx[..., None] - x
+    w = torch.exp(-t)
+    sm = w.sum(-1)
+    b_max = SLACK * E + U32 * mx.abs() + TINY
+    b_sum = U32 * sm + SLACK * ((2 * E + (4 * EXP_ULP + 14) * U32) * sm + 2 * U32 * (t * w).sum(-1)) + TINY
+    return mx, sm, E, b_max, b_sum
+
+
+def argmax_admissible(x, got, E):
+    """the admissible-argmax rule, no position exempted.  x [R, n] float64 logits of R rows (a 64-column segment or a whole row),
+    got [R] indices into the n columns, E [R] the largest logit error of the row.  An index is admissible iff
+        0 <= got < n  and  x[got] >= max x - 2 SLACK E
+    (the kernel's value of the true maximum and of its own choice are each within SLACK E of the float64 ones), and, where the
+    row is exact (E == 0: ties of exact values, the documented rule), iff it is the LOWEST index of the maximum.
+    A padded column (-1e30, e = 0) is 1e30 below any real one: never admissible beside a real column.
+    Returns the bool [R] of admissible rows and the number of admissible columns per row (the rule's sharpness)."""
+    R, n = x.shape
+    g = got.long()
+    inside = (g >= 0) & (g < n)
+    mx = x.amax(-1)
+    thr = mx - 2 * SLACK * E
+    val = x.gather(1, g.clamp(0, n - 1)[:, None])[:, 0]
+    ok = inside & (val >= thr)
+    first = (x == mx[:, None]).double().argmax(-1)
+    ok = torch.where(E == 0, inside & (g == first), ok)
+    return ok, (x >= thr[:, None]).sum(-1)
+
+
+def check_admissible(x, got, E, what):
+    ok, n_adm = argmax_admissible(x, got, E)
+    if not bool(ok.all()):
+        i = int((~ok).nonzero()[0])
+        g = int(got[i])
+        v = float(x[i, g]) if 0 <= g < x.shape[1] else float("nan")
+        raise AssertionError(f"{what}: {int((~ok).sum())} of {ok.numel()} argmax indices not admissible; first at row {i}: got "
+                             f"index {g} (logit {v:.9g}), row maximum {float(x[i].max()):.9g} at {int(x[i].argmax())}, "
+                             f"acceptance width {float(2 * SLACK * E[i]):.3g}")
+    return n_adm
+
+
+def rowmax_combine_bounds(mx, se, n_seg):
+    """xl_rowmax_combine on the kernel's OWN records mx, se [n_seg, M] (float64 copies of the fp32 values): gmx = max_s mx (exact),
+    tot = sum_s se_s exp(mx_s - gmx).  A segment's term passes through at most n_seg merges (each: one exp of its running factor,
+    one multiply, one addition: (EXP_ULP + 2) U32) and its exponents telescope to d_s = gmx - mx_s (2 U32 d_s: subtraction and
+    __expf scaling):  |dtot| <= n_seg (EXP_ULP + 3) U32 tot + 2 U32 sum_s d_s se_s exp(-d_s).
+      row_lse = gmx + log(tot)   U32 |lse| + SLACK (dtot / tot + 2 U32 |log tot| + LOG_ABS)
+      row_maxprob = 1 / tot      U32 |p| + SLACK p (dtot / tot + RCP_ULP U32)
+    Returns (ref lse, ref maxprob, bound of lse, bound of maxprob, dtot / tot)."""
+    gmx = mx.amax(0)
+    d = gmx[None, :] - mx
+    term = se * torch.exp(-d)
+    tot = term.sum(0)
+    rel = n_seg * (EXP_ULP + 3) * U32 + 2 * U32 * (d * term).sum(0) / tot
+    lse, p = gmx + torch.log(tot), 1.0 / tot
+    b_lse = U32 * lse.abs() + SLACK * (rel + 2 * U32 * torch.log(tot).abs() + LOG_ABS) + TINY
+    b_p = U32 * p + SLACK * p * (rel + RCP_ULP * U32) + TINY
+    return lse, p, b_lse, b_p, rel
+
+
+def rowmax_composed_bounds(pre, e, n_seg):
+    """GEMM epilogue + combine against the float64 logits of the whole row: a perturbation of every logit by at most E_row = max_n
+    e moves the log-sum-exp by at most E_row and the largest probability exp(max - lse) by at most 2 E_row relative; the fp32
+    arithmetic of both kernels adds r = (n_seg (EXP_ULP + 3) + 4 EXP_ULP + 14) U32 + 4 U32 sum_n t_n w_n / sum_n w_n  (t_n = max -
+    x_n, w_n = exp(-t_n): the terms' exponent roundings of rowmax_record_bounds and rowmax_combine_bounds together):
+      row_lse      U32 |lse| + SLACK (E_row + r + 2 U32 |lse - max| + LOG_ABS) + U32 |max|
+      row_maxprob  U32 p + SLACK p (2 E_row + r + RCP_ULP U32)
+    Returns (ref lse, ref maxprob, E_row, bound of lse, bound of maxprob)."""
+    mx = pre.amax(-1)
+    E = e.amax(-1)
+    t = mx[:, None] - pre
+    w = torch.exp(-t)
+    tot = w.sum(-1)
+    r = (n_seg * (EXP_ULP + 3) + 4 * EXP_ULP + 14) * U32 + 4 * U32 * (t * w).sum(-1) / tot
+    lse, p = mx + torch.log(tot), 1.0 / tot
+    b_lse = U32 * lse.abs() + SLACK * (E + r + 2 * U32 * torch.log(tot).abs() + LOG_ABS) + U32 * mx.abs() + TINY
+    b_p = U32 * p + SLACK * p * (2 * E + r + RCP_ULP * U32) + TINY
+    return lse, p, E, b_lse, b_p
+
+
+# ------------------------------------------------------------------------------------------------------------------ BCE
+def bce_bounds(x, t, M, N, dl_ref, loss_ref, loss_prev, out_dtype):
+    """xl_bce_logits_fwd_bwd on fp32 logits x and soft targets t [M, N], scale = 1 / (M N) (fp32: 2 U32 relative).
+    e = __expf(-|x|): (EXP_ULP + |x|) U32 relative; sigma = 1 / (1 + e) (x >= 0) or e / (1 + e): d sigma / sigma = (1 - sigma) de / e
+    in both branches, plus the addition and the division (2 + RCP_ULP) U32:
+      dlogits = (sigma - t) scale    u_out |ref| + SLACK scale (sigma (1 - sigma) (EXP_ULP + |x|) U32 + 3 U32 sigma) + SLACK 4 U32 |ref|
+                (the subtraction, the scale and its own rounding: 4 U32); columns N .. ld_dlogits are exactly 0 (bound TINY)
+      loss += scale sum_mn l,  l = max(x, 0) - x t + log1p(e) >= 0: every term carries U32 (2 max(x, 0) + 2 |x t| + 4 log1p(e)) +
+                (EXP_ULP + |x|) U32 e of its own (the pieces may cancel: absolute, not relative to l), and the sum of the M N
+                terms in any order is sum_bound(sum l, M N): wave and block trees, one fp32 atomic per row.
+    Returns the bounds of dlogits [M, N] and of the loss."""
+    sg = torch.sigmoid(x)
+    e = torch.exp(-x.abs())
+    scale = 1.0 / (M * N)
+    b_dl = unit(out_dtype) * dl_ref.abs() + SLACK * scale * (sg * (1 - sg) * (EXP_ULP + x.abs()) * U32 + 3 * U32 * sg) \
+        + SLACK * 4 * U32 * dl_ref.abs() + TINY
+    l = x.clamp(min=0) - x * t + torch.log1p(e)
+    l_err = U32 * (2 * x.clamp(min=0) + 2 * (x * t).abs() + 4 * torch.log1p(e)) + (EXP_ULP + x.abs()) * U32 * e
+    b_loss = sum_bound(float(l.abs().sum()) * scale, M * N, torch.as_tensor(float(loss_ref), dtype=torch.float64)) \
+        + SLACK * scale * float(l_err.sum()) + SLACK * 2 * U32 * abs(float(loss_ref)) + U32 * abs(float(loss_prev))
+    return b_dl, float(b_loss)
+
+
+# ------------------------------------------------------------------------------------------------------------------ attn_probs
+def attn_probs_bound(Q, K, V_unused, valid, keep, scale, lse, ref):
+    """xl_attn_probs: probs = exp(s - lse) keep from the forward's saved lse (the reference reads the same lse), fp32 out, a serial
+    dh-deep fma chain per score.  With attention_parts' per-row score error e_S (the dh-deep contraction and the rounding of the
+    exponent) every probability moves by p (e_S + U32 |s - lse| (subtraction + expf scaling: 2) + EXP_ULP U32), the dropout scale
+    is one more multiply:  U32 |ref| + SLACK |ref| (e_S + 2 U32 |s - lse| + (EXP_ULP + 2) U32).
+    No bf16 rounding of P here: the designed U16 |P'| of sdpa_fwd_bounds belongs to the PV MFMA, which this kernel does not have.
+    Invalid pairs (masked keys, rows / keys beyond a packed example's length) are exactly 0."""
+    s, _, _, eS = attention_parts(Q, K, Q[..., :1, :], valid, keep, scale)
+    arg = (s - lse[..., None]).abs().masked_fill(~valid, 0.0).nan_to_num(0.0, posinf=0.0)
+    return U32 * ref.abs() + SLACK * ref.abs() * (eS + 2 * U32 * arg + (EXP_ULP + 2) * U32) + TINY
+
+
+# ------------------------------------------------------------------------------------------------------------------ sampler checks
+# The comparisons themselves, shared by the host proofs (tests/test_bounds_cpu.py) and the recorder of the GPU tests: each returns
+# [(output name, worst |err| / bound)] and raises on the first output beyond its bound.
+def rowmax_records(aux, n_seg, M):
+    """the fp32 record buffer as (max, sum exp) in float64 and the argmax (an int32 bit pattern in the third float) as int64"""
+    rec = aux.reshape(-1)[:n_seg * M * 4].view(n_seg, M, 4)
+    assert rec.dtype == torch.float32
+    return rec[..., 0].double(), rec[..., 1].double(), rec[..., 2].contiguous().view(torch.int32).long(), rec[..., 3]
+
+
+def check_rowmax_records(aux, pre, e, what="gemm ROWMAX"):
+    """every record of the epilogue against the float64 logits pre [M, N]: max, sum exp, an admissible segment argmax (global
+    column index), the fourth float 0.  Returns the rows of the headroom table and the admissible-column counts [M, n_seg]."""
+    M, N = pre.shape
+    n_seg = N // 64
+    mx, se, idx, zero = rowmax_records(aux, n_seg, M)
+    ref_mx, ref_se, E, b_mx, b_se = rowmax_record_bounds(pre, e)
+    res = [("max", check(mx.t(), ref_mx, b_mx, f"{what} segment max")),
+           ("sum exp", check(se.t(), ref_se, b_se, f"{what} segment sum exp"))]
+    local = idx.t() - torch.arange(n_seg, device=idx.device)[None, :] * 64
+    n_adm = check_admissible(pre.reshape(M * n_seg, 64), local.reshape(-1), E.reshape(-1), f"{what} segment argmax")
+    res.append(("argmax admissible", 0.0))
+    res.append(("pad float", check_exact(zero, torch.zeros_like(zero), f"{what} fourth float")))
+    return res, n_adm.view(M, n_seg)
+
+
+def check_rowmax_rows(pre, e, n_seg, got_p, got_idx, got_lse, what="ROWMAX + combine"):
+    """the composed result of epilogue and combine against the float64 logits: admissible row argmax, row_lse, row_maxprob.
+    Returns the table rows and the admissible-column count per row."""
+    lse, p, E, b_lse, b_p = rowmax_composed_bounds(pre, e, n_seg)
+    n_adm = check_admissible(pre, got_idx, E, f"{what} row argmax")
+    res = [("row argmax admissible", 0.0)]
+    if got_p is not None:
+        res.append(("row_maxprob", check(got_p, p, b_p, f"{what} row_maxprob")))
+    if got_lse is not None:
+        res.append(("row_lse", check(got_lse, lse, b_lse, f"{what} row_lse")))
+    return res, n_adm
+
+
+def check_rowmax_combine(ref_ops, ws, n_seg, M, got_p, got_idx, got_lse, what="rowmax_combine"):
+    """xl_rowmax_combine on the records `ws` it read (fp32, the kernel's own) against ref_ops.rowmax_combine in float64: the argmax
+    exact (lowest index among the segments that hold the global maximum), row_lse and row_maxprob within rowmax_combine_bounds"""
+    dev = ws.device
+    rp, rl = (torch.zeros(M, dtype=torch.float64, device=dev) for _ in range(2))
+    ri = torch.zeros(M, dtype=torch.int32, device=dev)
+    ref_ops.rowmax_combine(ws, n_seg, M, rp, ri, rl)
+    mx, se, _, _ = rowmax_records(ws, n_seg, M)
+    lse, p, b_lse, b_p, _ = rowmax_combine_bounds(mx, se, n_seg)
+    res = []
+    if got_idx is not None:
+        res.append(("row_argmax", check_exact(got_idx[:M].long(), ri.long(), f"{what} row_argmax")))
+    if got_p is not None:
+        res.append(("row_maxprob", check(got_p[:M], rp, b_p, f"{what} row_maxprob")))
+    if got_lse is not None:
+        res.append(("row_lse", check(got_lse[:M], rl, b_lse, f"{what} row_lse")))
+    return res
+
+
+def sharpness(n_adm):
+    """the two figures of the admissible-argmax rule's sharpness: share of rows with more than one admissible column, and the
+    largest number of admissible columns in a row"""
+    return float((n_adm > 1).double().mean()), int(n_adm.max())
+
+
+MAX_SHARE_AMBIGUOUS, MAX_ADMISSIBLE = 0.15, 4     # caps of the sharpness condition (tests/test_bounds_cpu.py pins them on the oracle)

@@ -25,10 +25,14 @@ def gelu_grad(x):
 def keep_scale(seed, row, col, p_drop):
     """Host restatement of csrc/common.h dropout_draw16()/dropout_scale(): one 32-bit multiply-xorshift mix of
     (row, col >> 1, seed) gives two 16-bit draws (even / odd column); keep iff draw >= p * 2^16.
-    row, col: broadcastable int64 tensors.  Returns float32 0 or 1/(1-p)."""
+    row, col: broadcastable int64 tensors.  Returns float32 0 or 1/(1-p), on the device of `row` (index tensors that live on an
+    accelerator are hashed there, by the same arithmetic in int64 masked to 32 bits: the float64 reference of a recorded step
+    draws a dozen 12-million-element masks)."""
     import numpy as np
     u32 = np.uint32
     row, col = torch.broadcast_tensors(torch.as_tensor(row), torch.as_tensor(col))
+    if row.device.type != "cpu":
+        return keep_scale_torch(seed, row, col, p_drop)
     r = (row.numpy().astype(np.uint64) & np.uint64(0xFFFFFFFF)).astype(u32)
     c = (col.numpy().astype(np.uint64) & np.uint64(0xFFFFFFFF)).astype(u32)
     s_lo, s_hi = u32(seed & 0xFFFFFFFF), u32((seed >> 32) & 0xFFFFFFFF)
@@ -42,6 +46,25 @@ def keep_scale(seed, row, col, p_drop):
     thr = u32(int(np.float32(p_drop) * np.float32(65536.0)))
     keep = (draw >= thr).astype(np.float32) * np.float32(1.0 / (1.0 - p_drop))
     return torch.from_numpy(keep)
+
+
+def keep_scale_torch(seed, row, col, p_drop):
+    """keep_scale in torch integer arithmetic (any device); tests/test_bounds_cpu.py holds it bit-equal to the numpy statement"""
+    import numpy as np
+    m32 = 0xFFFFFFFF
+    r, c = row.to(torch.int64) & m32, col.to(torch.int64) & m32
+    mix = (seed & m32) ^ ((((seed >> 32) & m32) * 0xC2B2AE3D) & m32)
+    h = ((r * 0x9E3779B1) & m32) ^ (((c >> 1) * 0x85EBCA77) & m32) ^ mix
+    h = h ^ (h >> 16); h = (h * 0x7FEB352D) & m32
+    h = h ^ (h >> 15); h = (h * 0x846CA68B) & m32
+    h = h ^ (h >> 16)
+    draw = torch.where((c & 1) != 0, h >> 16, h & 0xFFFF)
+    thr = int(np.float32(p_drop) * np.float32(65536.0))
+    return (draw >= thr).to(torch.float32) * float(np.float32(1.0 / (1.0 - p_drop)))
+
+
+def _rc(M, N, device):
+    return torch.arange(M, device=device)[:, None], torch.arange(N, device=device)[None, :]
 
 
 def dropout_keep_matrix(seed, n_problems, nq_cap, n_rows, n_cols, p_drop):
@@ -91,7 +114,7 @@ class FakeOps:
             acc = torch.nn.functional.gelu(acc)
         elif epilogue == EPI_RESIDUAL:
             if p_drop > 0:
-                acc = acc * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop).to(acc.device)
+                acc = acc * keep_scale(self._seed(seed), *_rc(M, N, acc.device), p_drop)
             acc = acc + v2(residual, M, N, ldr).to(self.compute)
         elif epilogue == EPI_DGELU:
             acc = acc * gelu_grad(v2(aux, M, N, ldx).to(self.compute))
@@ -184,7 +207,7 @@ class FakeOps:
         dgamma.add_(dg)
         dbeta.add_(db)
         if dx_dropped is not None and p_drop > 0:
-            d = d * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop).to(d.device)                         # the kernel masks the fp32 value, then rounds
+            d = d * keep_scale(self._seed(seed), *_rc(M, N, d.device), p_drop)                # the kernel masks the fp32 value, then rounds
             v2(dx_dropped, M, N, N).copy_(d)
         if dbias_prev is not None:
             dbias_prev.add_(d.sum(0))
@@ -247,7 +270,7 @@ class FakeOps:
         torch.as_strided(out, (N,), (1,)).add_(v2(x, M, N, ldx).to(self.compute).sum(0))
 
     def dropout(self, x, y, M, N, ldx, ldy, p_drop, seed):
-        v2(y, M, N, ldy).copy_(v2(x, M, N, ldx).to(self.compute) * keep_scale(self._seed(seed), torch.arange(M)[:, None], torch.arange(N)[None, :], p_drop).to(x.device))
+        v2(y, M, N, ldy).copy_(v2(x, M, N, ldx).to(self.compute) * keep_scale(self._seed(seed), *_rc(M, N, x.device), p_drop))
 
     def gelu_bwd(self, dy, pre, dx, n):
         dx.view(-1)[:n].copy_(dy.reshape(-1)[:n].to(self.compute) * gelu_grad(pre.reshape(-1)[:n].to(self.compute)))
@@ -267,7 +290,7 @@ class FakeOps:
     def remask_lowest(self, prob, vis_mask, B, V, n_mask):
         p = prob.reshape(B, V)
         order = torch.argsort(p, dim=1, stable=True)           # ascending, ties -> lower index first
-        m = torch.zeros(B, V, dtype=torch.uint8)
+        m = torch.zeros(B, V, dtype=torch.uint8, device=p.device)
         if n_mask > 0:
             m.scatter_(1, order[:, :n_mask], 1)
         vis_mask.view(B, V).copy_(m)
@@ -279,12 +302,12 @@ class FakeOps:
     def sampler_ar_update(self, prob, pred_ids, visited, vis_mask, code_ids, B, V, fixed_pos=-1):
         p, pr = prob.reshape(B, V), pred_ids.reshape(B, V)
         if fixed_pos >= 0:
-            pos = torch.full((B,), fixed_pos, dtype=torch.long)
+            pos = torch.full((B,), fixed_pos, dtype=torch.long, device=p.device)
         else:
             q = p.masked_fill(visited.view(B, V) != 0, -10000.0)
             pos = (q == q.max(1, keepdim=True).values).float().argmax(1)          # first index of the maximum
-            visited.view(B, V)[torch.arange(B), pos] = 1
-        r = torch.arange(B)
+            visited.view(B, V)[torch.arange(B, device=p.device), pos] = 1
+        r = torch.arange(B, device=p.device)
         code_ids.view(B, V)[r, pos] = pr[r, pos].to(code_ids.dtype)
         vis_mask.view(B, V)[r, pos] = 0
 
@@ -296,8 +319,8 @@ class FakeOps:
     def _pmask(B, H, nq, nk, p_drop, seed, device=None):
         if p_drop == 0:
             return 1.0
-        row = torch.arange(B * H * nq).view(B, H, nq, 1)                # (b*H+h)*nq+q
-        return keep_scale(seed, row, torch.arange(nk).view(1, 1, 1, nk), p_drop).to(device)
+        row = torch.arange(B * H * nq, device=device).view(B, H, nq, 1)                # (b*H+h)*nq+q
+        return keep_scale(seed, row, torch.arange(nk, device=device).view(1, 1, 1, nk), p_drop)
 
     # packed rows (include/xlxmert_hip.h xl_sdpa_*: q_rowoff / k_rowoff): unpack into the dense [B, H, n, dh] layout (zeros beyond
     # an example's length), compute as ever with the missing keys masked, store the real rows back, zero the pad tail
@@ -440,8 +463,8 @@ class FakeOps:
         torch.as_strided(dst, (int(g.max()) + 1, N), (ld_dst, 1))[g[keep]] = v2(src, n_rows, N, ld_src)[keep]
 
     def rowmax_combine(self, ws, n_seg, M, row_maxprob, row_argmax, row_lse=None):
-        rec = ws.view(-1)[:n_seg * M * 4].view(n_seg, M, 4)
-        mx, se, idx = rec[..., 0], rec[..., 1], rec[..., 2].contiguous().view(torch.int32)
+        rec = ws.view(-1)[:n_seg * M * 4].view(n_seg, M, 4)        # fp32 records (the argmax is an int32 bit pattern)
+        mx, se, idx = rec[..., 0].to(self.compute), rec[..., 1].to(self.compute), rec[..., 2].contiguous().view(torch.int32)
         gmx = mx.max(0).values
         tot = (se * torch.exp(mx - gmx[None, :])).sum(0)
         cand = torch.where(mx == gmx[None, :], idx, torch.full_like(idx, 2 ** 31 - 1))

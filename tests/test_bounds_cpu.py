@@ -332,3 +332,332 @@ def test_bounds_reject_plausible_kernel_faults(fault):
         must_reject(bf(dx32), dx, bdx, fault)
     else:
         raise AssertionError(fault)
+
+
+# ------------------------------------------------------------------------------------------------------------------ sampler head
+# The fused sampler head (XL_EPI_ROWMAX records + xl_rowmax_combine), BCE, attn_probs and the sampler's index kernels: an fp32
+# emulation of each kernel's arithmetic passes; every fault of SAMPLER_FAULTS, built into that emulation, is rejected.
+N_REAL, N_PAD, K_HEAD = 300, 512, 256
+
+
+def rowmax_case(seed=13, M=64):
+    """300 real codes padded to 512 (segment 4: 44 real + 20 padded columns, segments 5..7 all padded: zero operand rows, bias
+    -1e30).  Row 0 of A is all zero: its logits are the biases, exactly, and bias 10 == bias 12 == bias 200 is the largest -- an
+    exact tie inside segment 0 and between segments 0 and 3.  Row 1's maximum is forced into the last real column."""
+    g = _gen(seed)
+    A = bf(torch.randn(M, K_HEAD, generator=g))
+    W = torch.zeros(N_PAD, K_HEAD, dtype=torch.bfloat16)
+    W[:N_REAL] = bf(torch.randn(N_REAL, K_HEAD, generator=g) * (2.0 / math.sqrt(K_HEAD)))
+    bias = torch.full((N_PAD,), -1e30)
+    bias[:N_REAL] = torch.randn(N_REAL, generator=g)
+    bias[[10, 12, 200]] = 4.0
+    A[0] = 0
+    W[N_REAL - 1] = A[1] * 0.5
+    return dict(A=A, W=W, bias=bias, M=M)
+
+
+def rowmax_reference(c):
+    A, W, b = c["A"].double(), c["W"].double(), c["bias"].double()
+    pre = A @ W.t() + b
+    e = BD.rowmax_logit_error(pre, A.abs() @ W.abs().t(), b.abs()[None, :], K_HEAD)
+    return pre, e
+
+
+def rowmax_emulate(c, fault=None):
+    """fp32 emulation of the epilogue and the combine: records [n_seg, M, 4] and (maxprob, argmax, lse)"""
+    M, n_seg = c["M"], N_PAD // 64
+    bias = c["bias"].clone()
+    if fault == "padded_column_wins":
+        bias[N_REAL:] = 1e30                       # the sign of the padding bias lost
+    if fault == "padded_column_adds_to_sum":
+        bias[N_REAL:] = 0.0                        # the padding bias not applied: 212 logits of 0 join the sums
+    acc = c["A"].float() @ c["W"].float().t()
+    x = acc + bias
+    seg = x.view(M, n_seg, 64)
+    if fault == "bias_added_after_maximum":
+        am = acc.view(M, n_seg, 64).argmax(-1)
+        mx = seg.gather(-1, am[..., None])[..., 0]
+    else:
+        mx = seg.amax(-1)
+        tie = seg == mx[..., None]
+        am = (tie.float().argmax(-1) if fault != "argmax_highest_index_on_tie" else 63 - tie.flip(-1).float().argmax(-1))
+    se = torch.exp(seg - mx[..., None]).sum(-1)
+    idx = (am + torch.arange(n_seg)[None, :] * 64).to(torch.int32)
+    rec = torch.stack([mx, se, idx.view(torch.float32), torch.zeros_like(mx)], -1).permute(1, 0, 2).contiguous()   # [n_seg, M, 4]
+    mxs, ses, ids = rec[..., 0], rec[..., 1], idx.t()
+    if fault == "segment_left_out_of_combine":
+        mxs, ses, ids = mxs[1:], ses[1:], ids[1:]
+    gmx = mxs.amax(0)
+    if fault == "segment_sums_combined_as_if_against_the_row_maximum":
+        tot = ses.sum(0)
+    else:
+        tot = (ses * torch.exp(mxs - gmx[None, :])).sum(0)
+    hold = mxs == gmx[None, :]
+    if fault == "argmax_highest_index_on_tie":
+        arg = torch.where(hold, ids, torch.full_like(ids, -1)).amax(0)
+    else:
+        arg = torch.where(hold, ids, torch.full_like(ids, 2 ** 31 - 1)).amin(0)
+    return rec, 1.0 / tot, arg.to(torch.int32), gmx + torch.log(tot)
+
+
+def rowmax_check_all(c, rec, p, arg, lse):
+    pre, e = rowmax_reference(c)
+    n_seg = N_PAD // 64
+    BD.check_rowmax_records(rec, pre, e)
+    BD.check_rowmax_combine(R64, rec, n_seg, c["M"], p, arg, lse)
+    _, n_adm = BD.check_rowmax_rows(pre, e, n_seg, p, arg, lse)
+    return n_adm
+
+
+def test_rowmax_honest_result_passes_with_exact_ties_and_padding():
+    c = rowmax_case()
+    rec, p, arg, lse = rowmax_emulate(c)
+    n_adm = rowmax_check_all(c, rec, p, arg, lse)
+    assert int(arg[0]) == 10 and int(arg[1]) == N_REAL - 1          # the tie goes to the lowest index; the last real column can win
+    assert int(n_adm.max()) < 8
+    # the float64 restatement of the combine rounded to fp32 passes as well
+    pr, lr, ir = torch.zeros(c["M"], dtype=torch.float64), torch.zeros(c["M"], dtype=torch.float64), torch.zeros(c["M"], dtype=torch.int32)
+    R64.rowmax_combine(rec, N_PAD // 64, c["M"], pr, ir, lr)
+    rowmax_check_all(c, rec, pr.float(), ir, lr.float())
+
+
+# ------------------------------------------------------------------------------------------------------------------ BCE
+def bce_case(seed=17, M=6, N=3129, ld=3136):
+    g = _gen(seed)
+    x = torch.randn(M, N, generator=g) * 4
+    t = (torch.rand(M, N, generator=g) < 0.3).float() * torch.rand(M, N, generator=g).round()      # sparse soft targets, many 1.0
+    return x, t, M, N, ld
+
+
+def bce_emulate(x, t, M, N, ld, dtype, fault=None):
+    xs = x.to(torch.bfloat16).float() if fault == "sigmoid_of_bf16_rounded_logit" else x
+    e = torch.exp(-xs.abs())
+    sg = torch.where(xs >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    scale = 1.0 / M if fault == "bce_gradient_divided_by_M" else 1.0 / (M * N)
+    d = torch.full((M, ld), float("nan"))                          # (the checked buffer starts as NaN: unwritten elements show)
+    d[:, :N] = (sg - t) * torch.tensor(scale, dtype=torch.float32)
+    if fault != "padded_dlogits_columns_unwritten":
+        d[:, N:] = 0
+    loss = ((x.clamp(min=0) - x * t + torch.log1p(torch.exp(-x.abs()))).sum() * torch.tensor(1.0 / (M * N))).float()
+    return d.to(dtype), loss
+
+
+def bce_reference(x, t, M, N, ld, dtype):
+    dl = torch.zeros(M, ld, dtype=torch.float64)
+    loss = torch.zeros(1, dtype=torch.float64)
+    R64.bce_logits_fwd_bwd(x, t, dl, loss, M, N, N, N, ld)
+    b_dl, b_loss = BD.bce_bounds(x.double(), t.double(), M, N, dl[:, :N], float(loss), 0.0, dtype)
+    bound = torch.full((M, ld), BD.TINY, dtype=torch.float64)
+    bound[:, :N] = b_dl
+    return dl, loss, bound, b_loss
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+def test_bce_honest_result_passes(dtype):
+    c = bce_case()
+    dl, loss, bound, b_loss = bce_reference(*c, dtype)
+    d, l = bce_emulate(*c, dtype)
+    BD.check(d, dl, bound, "bce dlogits")
+    BD.check(l.reshape(1), loss, b_loss, "bce loss")
+
+
+# ------------------------------------------------------------------------------------------------------------------ attn_probs
+def attn_probs_run(ops, c, lse, dtype, seed=None):
+    B, n = c["B"], c["n"]
+    probs = torch.zeros(B, H, n, n, dtype=dtype)
+    ops.attn_probs(c["q"], c["k"], c["key_mask"], lse, probs, B, H, n, n, DH, H * DH, H * DH, 0.125, p_drop=c["p_drop"],
+                   seed=c["seed"] if seed is None else seed, q_off=c["off"], k_off=c["off"])
+    return probs
+
+
+def attn_probs_ref(c):
+    B, n, off = c["B"], c["n"], c["off"]
+    _, lse = attn_fwd(R32, c, torch.float32)                        # the lse a forward kernel saved (fp32)
+    P = attn_probs_run(R64, c, lse.double(), torch.float64)
+    Q, K, V, valid, keep = BD.attention_inputs(R64, c["q"], c["k"], c["v"], c["key_mask"], B, H, n, n, DH, H * DH, H * DH, H * DH,
+                                               c["p_drop"], c["seed"], off, off)
+    lse3 = lse.double().view(B, H, n)
+    return lse, P, BD.attn_probs_bound(Q, K, V, valid, keep, 0.125, lse3, P), keep
+
+
+@pytest.mark.parametrize("packed", [False, True], ids=["dense", "packed"])
+@pytest.mark.parametrize("p_drop", [0.0, 0.1], ids=["no_dropout", "dropout"])
+def test_attn_probs_honest_result_passes(packed, p_drop):
+    c = attn_case(packed, p_drop)
+    lse, P, bound, _ = attn_probs_ref(c)
+    BD.check(attn_probs_run(R32, c, lse, torch.float32), P, bound, "attn_probs")
+
+
+# ------------------------------------------------------------------------------------------------------------------ index kernels
+def sampler_state(seed=19, B=16, V=64):
+    g = _gen(seed)
+    prob = torch.rand(B, V, generator=g)
+    prob[3] = 0.25                                                  # a row of all-equal confidences
+    prob[4, 7] = prob[4, 50] = prob[4].min() / 2                    # a tie at the bottom
+    pred = torch.randint(0, 10000, (B, V), generator=g, dtype=torch.int32)
+    ids = torch.randint(0, 10000, (B, V), generator=g)
+    return prob, pred, ids, B, V
+
+
+def test_sampler_index_kernels_reference_rules():
+    """what check_exact compares the kernels with: stable ascending order, exactly n_mask per row, first index of the maximum"""
+    prob, pred, ids, B, V = sampler_state()
+    for n_mask in (0, 1, 16, 48, V):
+        m = torch.zeros(B, V, dtype=torch.uint8)
+        R64.remask_lowest(prob.double(), m, B, V, n_mask)
+        assert bool((m.sum(1) == n_mask).all())
+        if 0 < n_mask < V:
+            assert m[3, :n_mask].all() and not m[3, n_mask:].any()
+        if n_mask == 1:
+            assert m[4, 7] == 1 and m[4, 50] == 0
+    visited, vm = torch.zeros(B, V, dtype=torch.uint8), torch.ones(B, V, dtype=torch.uint8)
+    p2 = prob.clone()
+    p2[5, 9] = p2[5, 33] = 2.0
+    R64.sampler_ar_update(p2.double(), pred, visited, vm, ids.clone(), B, V, -1)
+    assert visited[5, 9] == 1 and visited[5, 33] == 0 and visited[3, 0] == 1 and int(visited.sum()) == B
+
+
+SAMPLER_FAULTS = ["argmax_highest_index_on_tie", "segment_left_out_of_combine", "padded_column_wins", "padded_column_adds_to_sum",
+                  "bias_added_after_maximum", "segment_sums_combined_as_if_against_the_row_maximum",
+                  "sigmoid_of_bf16_rounded_logit", "bce_gradient_divided_by_M", "padded_dlogits_columns_unwritten",
+                  "remask_highest_instead_of_lowest", "remask_one_too_many", "remask_one_too_few",
+                  "sampler_update_writes_unmasked_positions", "sampler_ar_update_chooses_a_visited_position",
+                  "attn_probs_dropout_mask_of_the_neighbouring_head", "take_f32_keeps_values_outside_the_owned_range"]
+
+
+def _rejected(fn, what):
+    try:
+        fn()
+    except AssertionError:
+        return
+    pytest.fail(f"{what}: the checks are too loose -- the faulty result passes")
+
+
+@pytest.mark.parametrize("fault", SAMPLER_FAULTS)
+def test_sampler_and_task_bounds_reject_plausible_kernel_faults(fault):
+    if fault in SAMPLER_FAULTS[:6]:
+        c = rowmax_case()
+        out = rowmax_emulate(c, fault)
+        _rejected(lambda: rowmax_check_all(c, *out), fault)
+    elif fault in SAMPLER_FAULTS[6:9]:
+        dtype = torch.float32 if fault == "sigmoid_of_bf16_rounded_logit" else torch.bfloat16
+        c = bce_case()
+        dl, _, bound, _ = bce_reference(*c, dtype)
+        d, _ = bce_emulate(*c, dtype, fault)
+        must_reject(d, dl, bound, fault)
+    elif fault.startswith("remask"):
+        prob, _, _, B, V = sampler_state()
+        ref = torch.zeros(B, V, dtype=torch.uint8)
+        R64.remask_lowest(prob.double(), ref, B, V, 16)
+        bad = torch.zeros(B, V, dtype=torch.uint8)
+        if fault == "remask_highest_instead_of_lowest":
+            R64.remask_lowest(-prob.double(), bad, B, V, 16)
+        else:
+            R64.remask_lowest(prob.double(), bad, B, V, 17 if fault == "remask_one_too_many" else 15)
+        _rejected(lambda: BD.check_exact(bad, ref, fault), fault)
+        if fault != "remask_highest_instead_of_lowest":            # (that one masks the right number of wrong positions)
+            _rejected(lambda: BD.check_exact(bad.sum(1), torch.full((B,), 16), fault + " (per-row count)"), fault)
+    elif fault == "sampler_update_writes_unmasked_positions":
+        prob, pred, ids, B, V = sampler_state()
+        vm = (prob < 0.5).to(torch.uint8)
+        ref = ids.clone()
+        R64.sampler_update(pred, vm, ref, B * V)
+        _rejected(lambda: BD.check_exact(pred.long(), ref, fault), fault)
+    elif fault == "sampler_ar_update_chooses_a_visited_position":
+        prob, pred, ids, B, V = sampler_state()
+        visited = torch.zeros(B, V, dtype=torch.uint8)
+        visited[torch.arange(B), prob.argmax(1)] = 1                # every row's most confident position is taken already
+        ref_v, ref_m, ref_i = visited.clone(), torch.ones(B, V, dtype=torch.uint8), ids.clone()
+        R64.sampler_ar_update(prob.double(), pred, ref_v, ref_m, ref_i, B, V, -1)
+        bad_v, bad_m, bad_i = torch.zeros(B, V, dtype=torch.uint8), torch.ones(B, V, dtype=torch.uint8), ids.clone()
+        R64.sampler_ar_update(prob.double(), pred, bad_v, bad_m, bad_i, B, V, -1)       # (as if nothing had been visited)
+        _rejected(lambda: BD.check_exact(bad_m, ref_m, fault), fault)
+        _rejected(lambda: BD.check_exact(bad_i, ref_i, fault), fault)
+    elif fault == "attn_probs_dropout_mask_of_the_neighbouring_head":
+        c = attn_case(False, 0.1)
+        lse, P, bound, keep = attn_probs_ref(c)
+        clean = attn_probs_run(R32, dict(c, p_drop=0.0), lse, torch.float32)
+        must_reject(clean * torch.roll(keep, 1, 1).float(), P, bound, fault)
+    elif fault == "take_f32_keeps_values_outside_the_owned_range":
+        src = torch.arange(1.0, 101.0)
+        idx = torch.tensor([0, 5, 40, 41, 99, 60], dtype=torch.int32)
+        ref = torch.zeros(6, dtype=torch.float64)
+        R64.take_f32(src.double(), idx, 5, 60, ref)
+        assert ref.tolist() == [0.0, 6.0, 41.0, 42.0, 0.0, 0.0]
+        _rejected(lambda: BD.check_exact(src[idx.long()].double(), ref, fault), fault)
+    else:
+        raise AssertionError(fault)
+
+
+# ------------------------------------------------------------------------------------------------------------------ sharpness
+def test_admissible_argmax_rule_is_sharp_on_the_oracle_sampler_step():
+    """The admissible-argmax rule accepts every column within 2 SLACK E of the float64 maximum; it says nothing if many columns
+    are.  On the float64 oracle (full-size model, make_state_dict(oc, 19), make_inputs(oc, 23, 8), all 64 grid positions masked =
+    sampler step 1, head operands rounded to bf16 as the kernel reads them) 5.1 % of the 512 rows have two admissible columns and
+    none has more (logit std 14.7, worst E 0.10).  Caps, 3x / 2x over that for other seeds and steps: at most 15 % of the rows with
+    more than one admissible column, never more than 4 in a row -- the same caps the GPU sampler test applies at every step."""
+    import lxmert_oracle as O
+    oc = O.OracleConfig()
+    sd = O.make_state_dict(oc, 19, dtype=torch.float64)
+    inp = O.make_inputs(oc, 23, 8)
+    B, V = 8, 64
+    code = sd["mask_feat"].view(1, 1, -1).expand(B, V, -1)
+    with torch.no_grad():
+        _, vis, _ = O.lxmert_model(sd, oc, inp["input_ids"], code, inp["visual_pos"].double(), inp["input_ids"] > 0)
+        feat, _ = O.visual_obj_head(sd, oc, vis)
+    A = feat.reshape(B * V, -1).to(torch.bfloat16).double()
+    W = sd["vis_emb.weight"].to(torch.bfloat16).double()
+    b = sd["obj_predict_head.out_cluster.bias"].double()
+    pre = A @ W.t() + b
+    e = BD.rowmax_logit_error(pre, A.abs() @ W.abs().t(), b.abs()[None, :], A.shape[1])
+    E = e.amax(-1)
+    _, n_adm = BD.argmax_admissible(pre, pre.argmax(-1), E)
+    share, most = BD.sharpness(n_adm)
+    top2 = pre.topk(2, -1).values
+    print(f"\nsharpness: {int((n_adm > 1).sum())} of {n_adm.numel()} rows ({100 * share:.1f} %) with more than one admissible column, "
+          f"at most {most} in a row; logit std {float(pre.std()):.1f}, worst E {float(E.max()):.2f}, median top-1/top-2 gap "
+          f"{float(((top2[:, 0] - top2[:, 1]) / (2 * BD.SLACK * E)).median()):.1f} x the acceptance width")
+    assert share <= BD.MAX_SHARE_AMBIGUOUS and most <= BD.MAX_ADMISSIBLE, (share, most)
+
+
+# ------------------------------------------------------------------------------------------------------------------ recorder
+TINY = dict(vocab_size=200, hidden_size=128, num_attention_heads=2, intermediate_size=256, max_position_embeddings=32,
+            visual_feat_dim=64, num_clusters=96, l_layers=2, x_layers=2, r_layers=2)
+
+
+@pytest.mark.parametrize("workload", ["nar_sampler", "ar_sampler", "vqa", "nlvr2", "word_mask", "matched", "output_attentions"])
+def test_recorded_workloads_pass_over_the_host_restatement(workload):
+    """the recording proxy, every checker and the "must have called" sets of tests/test_workload_bounds_gpu.py, driven here by the
+    fp32 host restatement on bf16 storage at a tiny geometry: an honest implementation of every op is inside every bound, and the
+    GPU tests' own code runs wherever the suite runs"""
+    import lxmert_oracle as O
+    import test_workload_bounds_gpu as W
+    cfg, oc = W._cfgs(**TINY)
+    ops = FakeOps(torch.bfloat16)
+    if workload == "nar_sampler":
+        rec = W.nar_sampler(cfg, oc, O.make_state_dict(oc, 19), 4, 4, "cpu", ops)
+        assert len(rec.sharp) == 4
+    elif workload == "ar_sampler":
+        for mode in ("confidence", "tlbr"):
+            W.ar_sampler(cfg, oc, O.make_state_dict(oc, 19), 4, mode, 3, "cpu", FakeOps(torch.bfloat16))
+    elif workload == "vqa":
+        W.vqa_step(cfg, O.make_vqa_state_dict(oc, 29, 41), 4, 29, "cpu", ops)
+    elif workload == "nlvr2":
+        W.nlvr2_step(cfg, O.make_nlvr2_state_dict(oc, 41), 4, "cpu", ops)
+    elif workload in ("word_mask", "matched"):
+        W.lang_step(cfg, O.make_cls_state_dict(oc, 41), workload, 4, "cpu", ops)
+    else:
+        W.attentions_forward(cfg, oc, O.make_state_dict(oc, 19), 4, "cpu", ops)
+
+
+def test_dropout_mask_restatement_in_torch_integers_equals_the_numpy_statement():
+    """fake_ops.keep_scale hashes index tensors that live on an accelerator with keep_scale_torch: the same mask, bit for bit"""
+    from fake_ops import keep_scale_torch
+    g = _gen(29)
+    for seed in (0, 3, 5 + 7 * 1000003, (1 << 40) + 12345, (1 << 63) - 1):
+        row = torch.randint(0, 1 << 31, (257, 1), generator=g)
+        col = torch.randint(0, 70000, (1, 130), generator=g)
+        for p_drop in (0.1, 0.5, 0.013):
+            assert torch.equal(keep_scale(seed, row, col, p_drop), keep_scale_torch(seed, *torch.broadcast_tensors(row, col), p_drop))
+    assert torch.equal(keep_scale(9, torch.arange(300)[:, None], torch.arange(64)[None, :], 0.1),
+                       keep_scale_torch(9, torch.arange(300)[:, None], torch.arange(64)[None, :], 0.1))

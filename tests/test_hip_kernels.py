@@ -761,7 +761,10 @@ def test_gemm_wgrad_group(rows, dtype, slab_ws):
 def test_gemm_rowmax_epilogue(M, N, K, n_real):
     """XL_EPI_ROWMAX + xl_rowmax_combine: argmax / max softmax probability / log-sum-exp of x = A B^T + bias per row without C in
     memory, against the same contraction written out in fp32 (same kernel, same accumulation order: identical argmax) and
-    softmax on the host; columns >= n_real are padding (zero operand rows, bias -1e30)."""
+    softmax on the host; columns >= n_real are padding (zero operand rows, bias -1e30).
+    This is the bit-identity test between the two epilogues of one kernel: a fault both share passes here.  The independent check
+    -- segment records, combine and composed row results against float64 logits, admissible argmax with no position exempted --
+    lives in tests/test_kernel_bounds_gpu.py / tests/test_workload_bounds_gpu.py (bounds: tests/bounds.py)."""
     g = torch.Generator().manual_seed(M + N)
     ops = hip(torch.bfloat16)
     A = rnd(g, M, K, dtype=torch.bfloat16).cuda()

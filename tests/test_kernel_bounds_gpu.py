@@ -4,7 +4,20 @@
 The step: the benchmarked geometry (bs 256, 20 text tokens packed, 64 grid tokens, 9/5/5 layers, d 768, 10k codebook, canonical
 visual_losses="obj"), dropout on, eager (no launch plan), optimizer in line.  Its HipOps is wrapped by a recording proxy: the first
 call of every kernel-selecting signature is run on snapshots of its operands and compared; a numeric method without a checker
-fails the test."""
+fails the test.
+
+Deferred reductions.  With xl_set_deferred_reduce(1) (the default of a training step's backward) a producer's column sums are
+not final at its own call: the recorder keeps, per producing stream, a pending list of (destination, float64 contribution,
+bound) and checks every destination when flush_reductions / flush_reductions_on combines that stream; a pending entry that no
+flush covers, or a destination that also received an unrecorded contribution, fails the test (Recorder.leftover()).
+
+What the proxy switches off.  PretrainStep gates four paths on isinstance(self.ops, HipOps) (trainer.py): (1) a separate bf16
+HipOps for a bf16 gradient exchange and (2) the library's RCCL binding -- both only with more than one rank, no numeric call of
+a one-GPU step; (3) plan mode -- a recorded launch plan replays the same C-ABI calls without passing through Python, so these
+tests run with plan=False by construction; (4) the side stream of the overlapped optimizer -- with the proxy the same grouped
+sumsq / adamw calls are issued in the same order on the main stream, placement only.  None of them hides a numeric call of the
+product path, so the proxy does not pretend to be a HipOps.  Engine gates nothing on the type (fused_predict_available asks
+hasattr(ops, "rowmax_combine"), which the proxy forwards)."""
 import inspect
 import time
 
@@ -25,6 +38,19 @@ CFG_KEYS = ("vocab_size", "hidden_size", "num_attention_heads", "intermediate_si
 NON_NUMERIC = {"zero", "stream_fork", "new_event", "event_record", "stream_wait", "set_step_seed_ptr", "set_deferred_reduce",
                "workspace_floats", "gemm_workspace", "sumsq_scratch", "sdpa_keep_bits_bytes", "wgrad_group_one_writer",
                "rebind", "bound", "forget_binding", "gemm_trace"}
+
+
+# sampler ops: the signature also carries the step index (Recorder.mark), so that every refinement step is checked
+STEP_KEYED = {"rowmax_combine", "remask_lowest", "sampler_update", "sampler_ar_update"}
+# the column-sum outputs whose second stage xl_set_deferred_reduce(1) postpones to the next flush of the producing stream
+REDUCE_OUTS = {"gemm": ("colsum",), "layernorm_bwd": ("dgamma", "dbeta", "dbias_prev"), "sdpa_bwd": ("bias_grad",),
+               "visn_ln_bwd": ("dgv", "dbv", "dgb", "dbb", "dwbox", "dbbox", "dbias_visn"), "colsum": ("out",),
+               "masked_colsum": ("out",)}
+
+
+def _sync():
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
 
 
 def _is_setter(name):
@@ -73,6 +99,35 @@ class Recorder:
         object.__setattr__(self, "called", set())
         object.__setattr__(self, "unchecked", set())
         object.__setattr__(self, "failures", [])
+        object.__setattr__(self, "_tag", None)          # step index of a sampler loop (part of the signature of its ops)
+        object.__setattr__(self, "_deferred", False)
+        object.__setattr__(self, "_pending", {})        # producing stream -> entries whose second stage has not run yet
+        object.__setattr__(self, "_dirty", {})          # producing stream -> [(lo, hi, recorded)] destinations written since its flush
+        object.__setattr__(self, "uncheckable", [])     # pending sums whose destination also holds an unrecorded contribution
+        object.__setattr__(self, "_force", set())       # signatures recorded at every call from now on (see retry())
+        object.__setattr__(self, "flushes_checked", 0)
+        object.__setattr__(self, "sharp", [])           # (tag, share of rows with > 1 admissible column, most in a row)
+        object.__setattr__(self, "_rowmax", None)
+        object.__setattr__(self, "_cur", None)
+        object.__setattr__(self, "ncalls", {})          # (step tag, method) -> number of calls
+        object.__setattr__(self, "checked", [])         # (method, {argument: scalar value / None / "T" for a tensor}) of every checked call
+
+    def mark(self, tag):
+        object.__setattr__(self, "_tag", tag)
+
+    def retry(self):
+        """A destination may receive two contributions between flushes (the shared cross-attention's q / k / v bias: one sdpa_bwd
+        per direction), and the first may be a call whose signature had been checked before, which the recorder lets pass
+        unrecorded.  Such a destination cannot be checked in that step (it is listed in `uncheckable`); the signature of the
+        unrecorded call is now recorded at EVERY call, and its partner follows by the overlap rule.  Returns True when the step
+        has to be run once more for that; the list starts empty again."""
+        again = bool(self.uncheckable)
+        del self.uncheckable[:]
+        return again
+
+    def leftover(self):
+        """pending column sums that no flush has covered, and destinations that could not be checked"""
+        return [f"{e['row'][0]} {e['row'][1]} {e['row'][2]}" for v in self._pending.values() for e in v] + list(self.uncheckable)
 
     def __setattr__(self, k, v):
         setattr(self._ops, k, v)
@@ -86,6 +141,13 @@ class Recorder:
                 self._ref.set_step_seed_ptr(step_seed)
                 return attr(step_seed)
             return fwd
+        if name == "set_deferred_reduce":
+            def fwd_defer(on):
+                object.__setattr__(self, "_deferred", bool(on))
+                return attr(on)
+            return fwd_defer
+        if name in ("flush_reductions", "flush_reductions_on"):
+            return lambda *args: self._flush(name, attr, args)
         if name in NON_NUMERIC or _is_setter(name):
             return attr
         if name == "gemm_pair":
@@ -97,6 +159,7 @@ class Recorder:
 
         def call(*args, **kw):
             self.called.add(name)
+            self.ncalls[(self._tag, name)] = self.ncalls.get((self._tag, name), 0) + 1
             if chk is None:
                 self.unchecked.add(name)
                 return attr(*args, **kw)
@@ -105,10 +168,16 @@ class Recorder:
             ba.apply_defaults()
             a = dict(ba.arguments)
             key = self._signature(name, a)
-            if key in self._seen:
+            if name in STEP_KEYED or (name == "gemm" and a["epilogue"] == BD.EPI_ROWMAX):
+                key += (("step", self._tag),)
+            dests = self._dests(name, a) if self._deferred else []
+            force = self._overlaps_recorded(dests) or key in self._force
+            if key in self._seen and not force:
+                self._note_dests(dests, False, key)
                 return attr(*args, **kw)
             self._seen.add(key)
-            torch.cuda.synchronize()
+            object.__setattr__(self, "_cur", (name, self._short(a)))
+            _sync()
             cache = {}
             s = {k: self._snap(v, cache) for k, v in a.items()}
 
@@ -117,7 +186,7 @@ class Recorder:
             def run():
                 ran.append(1)
                 r = attr(*args, **kw)
-                torch.cuda.synchronize()
+                _sync()
                 return r
             try:
                 res = chk(a, s, run)
@@ -127,11 +196,89 @@ class Recorder:
                 self.failures.append(f"{name} {self._short(a)}: {type(e).__name__}: {e}")
                 print(f"FAILED {self.failures[-1]}", flush=True)
                 return None
+            self._note_dests(dests, True, key)
+            self.checked.append((name, {k: ("T" if isinstance(v, (torch.Tensor, list, tuple)) else v) for k, v in a.items()}))
             for what, ratio, kernel in res:
                 self.rows.append((name, what, self._short(a), kernel, ratio))
-            print(f"checked {name} {self._short(a)}", flush=True)
+            print(f"checked {name} {self._short(a)}" + (f" step={self._tag}" if key[-1][0] == "step" else ""), flush=True)
             return None
         return call
+
+    # -- deferred second stages of the column reductions
+    @staticmethod
+    def _stream_key():
+        return torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0
+
+    @staticmethod
+    def _range(t):
+        span = sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1 if t.numel() else 0
+        return t.data_ptr(), t.data_ptr() + span * t.element_size()
+
+    def _dests(self, name, a):
+        return [self._range(a[k]) for k in REDUCE_OUTS.get(name, ()) if a.get(k) is not None]
+
+    def _overlaps_recorded(self, dests):
+        """does a destination already hold a RECORDED pending contribution?  (then this call is recorded too, whatever its
+        signature: the flush is checked against the sum of all contributions)"""
+        dirty = self._dirty.get(self._stream_key(), ())
+        return any(lo < dhi and dlo < hi and recd for lo, hi in dests for dlo, dhi, recd, _ in dirty)
+
+    def _note_dests(self, dests, recorded, key):
+        if dests:
+            self._dirty.setdefault(self._stream_key(), []).extend((lo, hi, recorded, key) for lo, hi in dests)
+
+    def _sum_out(self, res, what, got, ref, prev, bound, kern):
+        """a column-sum output of a producer: checked at once when its call completed it, else (deferred mode, destination
+        untouched by the call) entered into the pending list of the producing stream with its float64 contribution ref - prev"""
+        if self._deferred and torch.equal(got.double(), prev.double()):
+            lo, hi = self._range(got)
+            dirty = self._dirty.get(self._stream_key(), ())
+            blind = [k for dlo, dhi, recd, k in dirty if lo < dhi and dlo < hi and not recd]
+            if blind:
+                self._force.update(blind)
+                self.uncheckable.append(f"{self._cur[0]} {what} {self._cur[1]}: destination shared with an unrecorded call")
+                return
+            bound = torch.as_tensor(bound, dtype=torch.float64, device=ref.device).expand_as(ref)
+            self._pending.setdefault(self._stream_key(), []).append(
+                dict(got=got, delta=(ref.double() - prev.double()).clone(), bound=bound.clone(), row=(self._cur[0], what, self._cur[1], kern)))
+            return
+        res.append((what, BD.check(got, ref, bound, f"{self._cur[0]} {what}"), kern))
+
+    def _flush(self, name, attr, args):
+        """flush_reductions (the current stream's pending sums) / flush_reductions_on(producer): every pending destination of
+        that stream := its content before the flush + the float64 contributions recorded for it, within the sum of their bounds"""
+        self.called.add(name)
+        key = self._stream_key() if name == "flush_reductions" else args[0].cuda_stream
+        pend = self._pending.pop(key, [])
+        self._dirty.pop(key, None)
+        if not pend:
+            return attr(*args)
+        _sync()
+        groups = {}
+        for e in pend:
+            g = e["got"]
+            groups.setdefault((g.data_ptr(), tuple(g.shape), tuple(g.stride())), []).append(e)
+        before = {k: v[0]["got"].double().clone() for k, v in groups.items()}
+        r = attr(*args)
+        _sync()
+        n = 0
+        for k, es in groups.items():
+            ref = before[k] + sum(e["delta"] for e in es)
+            bound = sum(e["bound"] for e in es) + BD.U32 * (before[k].abs() + ref.abs())
+            nm, what, short, kern = es[-1]["row"]
+            try:
+                ratio = BD.check(es[0]["got"], ref, bound, f"{nm} {what} at {name}")
+                self.rows.append((nm, what + (f" x{len(es)}" if len(es) > 1 else "") + " @flush", short, kern, ratio))
+                n += 1
+            except AssertionError as e:
+                self.failures.append(f"{name}: {e}")
+                print(f"FAILED {self.failures[-1]}", flush=True)
+                n += 1
+        if n == 0:
+            self.failures.append(f"{name}: {len(pend)} pending entries, none checked")
+        object.__setattr__(self, "flushes_checked", self.flushes_checked + 1)
+        print(f"checked {name}: {n} destinations of {len(pend)} pending entries", flush=True)
+        return r
 
     # -- snapshots: every tensor operand's whole storage, float64 for floating types (aliasing between operands is kept)
     def _snap(self, v, cache):
@@ -164,7 +311,7 @@ class Recorder:
 
     @staticmethod
     def _short(a):
-        keys = ("M", "N", "K", "B", "H", "nq", "nk", "n", "V", "L", "n_rows", "epilogue", "accumulate")
+        keys = ("M", "N", "K", "B", "H", "nq", "nk", "n", "V", "L", "n_rows", "epilogue", "accumulate", "n_seg", "n_mask", "fixed_pos")
         return " ".join(f"{k}={a[k]}" for k in keys if k in a and not isinstance(a[k], torch.Tensor))
 
     # ------------------------------------------------------------------------------------------------ contractions
@@ -181,15 +328,16 @@ class Recorder:
 
     def chk_gemm(self, a, s, run):
         M, N, K, epi = a["M"], a["N"], a["K"], a["epilogue"]
-        assert epi != BD.EPI_ROWMAX, "the training step does not issue the ROWMAX epilogue"
+        if epi == BD.EPI_ROWMAX:
+            return self._chk_gemm_rowmax(a, s, run)
         pre, absprod = self._gemm_pre(s, M, N, K)
         prev = _v2(s["C"], M, N, a["ldc"]).clone() if a["accumulate"] else None
         aux_in = _v2(s["aux"], M, N, a["ldx"]).clone() if epi in (BD.EPI_DGELU, BD.EPI_MULAUX) else None
         cs_prev = torch.as_strided(s["colsum"], (N,), (1,)).clone() if a["colsum"] is not None else None
         keep = None
         if epi == BD.EPI_RESIDUAL and a["p_drop"] > 0:
-            keep = keep_scale(self._ref._seed(a["seed"]), torch.arange(M)[:, None], torch.arange(N)[None, :], a["p_drop"])
-            keep = keep.to(pre.device).double()
+            keep = keep_scale(self._ref._seed(a["seed"]), torch.arange(M, device=pre.device)[:, None],
+                              torch.arange(N, device=pre.device)[None, :], a["p_drop"]).double()
         run()
         self._ref.gemm(**{k: v for k, v in s.items()})
         out_dt = torch.float32 if a["out_f32"] else a["C"].dtype
@@ -206,8 +354,111 @@ class Recorder:
         if a["colsum"] is not None:
             ref_cs = torch.as_strided(s["colsum"], (N,), (1,))
             bcs = BD.colsum_bound(bc, ref_c, cs_prev)
-            res.append(("colsum", BD.check(torch.as_strided(a["colsum"], (N,), (1,)), ref_cs, bcs, "gemm colsum"), kern))
+            self._sum_out(res, "colsum", torch.as_strided(a["colsum"], (N,), (1,)), ref_cs, cs_prev, bcs, kern)
         return res
+
+    def _chk_gemm_rowmax(self, a, s, run):
+        """XL_EPI_ROWMAX: no C; the segment records in aux against float64 logits (bounds.check_rowmax_records).  The logits and
+        their error stay with the recorder for the composed check at the rowmax_combine that reads these records."""
+        M, N, K = a["M"], a["N"], a["K"]
+        assert a["a_kmajor"] and a["b_kmajor"] and a["alpha"] == 1.0 and a["bias"] is not None
+        A, B = _v2(s["A"], M, K, a["lda"]), _v2(s["B"], N, K, a["ldb"])
+        b = torch.as_strided(s["bias"], (N,), (1,))
+        pre = A @ B.t() + b[None, :]
+        e = BD.rowmax_logit_error(pre, A.abs() @ B.abs().t(), b.abs()[None, :], K)
+        run()
+        kern = "ping-pong 256x256 ROWMAX epilogue"
+        res, n_adm = BD.check_rowmax_records(a["aux"], pre, e)
+        object.__setattr__(self, "_rowmax", (a["aux"].data_ptr(), pre, e))
+        return [(w, r, kern) for w, r in res]
+
+    def chk_rowmax_combine(self, a, s, run):
+        n_seg, M = a["n_seg"], a["M"]
+        ws_in = a["ws"].reshape(-1)[:n_seg * M * 4].clone()          # the records the kernel reads (fp32: the argmax is a bit pattern)
+        run()
+        kern = "rowmax_combine_kernel"
+        res = [(w, r, kern) for w, r in BD.check_rowmax_combine(self._ref, ws_in, n_seg, M, a["row_maxprob"], a["row_argmax"],
+                                                                 a["row_lse"])]
+        if self._rowmax is not None and self._rowmax[0] == a["ws"].data_ptr():
+            _, pre, e = self._rowmax
+            object.__setattr__(self, "_rowmax", None)
+            rows, n_adm = BD.check_rowmax_rows(pre, e, n_seg, a["row_maxprob"][:M] if a["row_maxprob"] is not None else None,
+                                               a["row_argmax"][:M], a["row_lse"][:M] if a["row_lse"] is not None else None)
+            res += [("composed " + w, r, "ROWMAX epilogue + combine") for w, r in rows]
+            share, most = BD.sharpness(n_adm)
+            self.sharp.append((self._tag, share, most))
+            print(f"sharpness step={self._tag}: {100 * share:.1f} % of {n_adm.numel()} rows with more than one admissible column, "
+                  f"at most {most} in a row", flush=True)
+        return res
+
+    # ------------------------------------------------------------------------------------------------ sampler index kernels
+    def chk_remask_lowest(self, a, s, run):
+        B, V, n_mask = a["B"], a["V"], a["n_mask"]
+        run()
+        self._ref.remask_lowest(s["prob"], s["vis_mask"], B, V, n_mask)
+        got = a["vis_mask"].reshape(-1)[:B * V].view(B, V)
+        cnt = torch.full((B,), n_mask, device=got.device)
+        return [("vis_mask", BD.check_exact(got.long(), s["vis_mask"].reshape(-1)[:B * V].view(B, V).long(), "remask_lowest"), "remask_lowest"),
+                ("per-row count", BD.check_exact((got != 0).sum(1), cnt, "remask_lowest count"), "remask_lowest")]
+
+    def chk_sampler_update(self, a, s, run):
+        n = a["n"]
+        run()
+        self._ref.sampler_update(s["pred_ids"], s["vis_mask"], s["code_ids"], n)
+        return [("code_ids", BD.check_exact(a["code_ids"].reshape(-1)[:n], s["code_ids"].reshape(-1)[:n], "sampler_update"), "sampler_update")]
+
+    def chk_sampler_ar_update(self, a, s, run):
+        B, V = a["B"], a["V"]
+        run()
+        self._ref.sampler_ar_update(s["prob"], s["pred_ids"], s["visited"], s["vis_mask"], s["code_ids"], B, V, a["fixed_pos"])
+        kern = "sampler_ar_update (fixed position)" if a["fixed_pos"] >= 0 else "sampler_ar_update (most confident)"
+        res = [(k, BD.check_exact(a[k].reshape(-1)[:B * V].long(), s[k].reshape(-1)[:B * V].long(), f"sampler_ar_update {k}"), kern)
+               for k in ("code_ids", "vis_mask", "visited") if a[k] is not None]
+        if a["fixed_pos"] < 0:
+            res.append(("one new visit per row", BD.check_exact((a["visited"].view(B, V) != 0).sum(1) - (s["visited"].view(B, V) != 0).sum(1),
+                                                                torch.zeros(B, dtype=torch.long, device=a["visited"].device),
+                                                                "sampler_ar_update visits"), kern))
+        return res
+
+    def chk_take_f32(self, a, s, run):
+        n = a["idx"].numel()
+        run()
+        self._ref.take_f32(s["src"], s["idx"], a["own_lo"], a["own_hi"], s["dst"])
+        return [("dst", BD.check_exact(a["dst"][:n].double(), s["dst"][:n], "take_f32"), "take_f32")]
+
+    def chk_put_f32(self, a, s, run):
+        run()
+        self._ref.put_f32(s["dst"], s["idx"], s["src"])
+        return [("dst", BD.check_exact(a["dst"].double(), s["dst"], "put_f32"), "put_f32")]
+
+    def chk_bce_logits_fwd_bwd(self, a, s, run):
+        M, N, ld = a["M"], a["N"], a["ld_dlogits"]
+        x, t = _v2(s["logits"], M, N, a["ld_logits"]).clone(), _v2(s["targets"], M, N, a["ld_targets"]).clone()
+        prev = float(s["loss"][0])
+        run()
+        self._ref.bce_logits_fwd_bwd(**s)
+        kern = "bce_logits_kernel" + ("" if a["dlogits"] is not None else " (no gradient)")
+        dl = _v2(s["dlogits"], M, ld, ld) if a["dlogits"] is not None else torch.zeros(M, N, dtype=torch.float64, device=x.device)
+        b_dl, b_loss = BD.bce_bounds(x, t, M, N, dl[:, :N], float(s["loss"][0]), prev,
+                                     a["dlogits"].dtype if a["dlogits"] is not None else torch.float32)
+        res = [("loss", BD.check(a["loss"][:1], s["loss"][:1], b_loss, "bce loss"), kern)]
+        if a["dlogits"] is not None:
+            bound = torch.full_like(dl, BD.TINY)
+            bound[:, :N] = b_dl
+            res.append(("dlogits (pad columns 0)", BD.check(_v2(a["dlogits"], M, ld, ld), dl, bound, "bce dlogits"), kern))
+        return res
+
+    def chk_attn_probs(self, a, s, run):
+        B, H, nq, nk, dh = a["B"], a["H"], a["nq"], a["nk"], a["dh"]
+        Q, K, _, valid, keep = BD.attention_inputs(self._ref, s["q"], s["k"], s["k"], s["key_mask"], B, H, nq, nk, dh, a["ldq"], a["ldk"],
+                                                   a["ldk"], a["p_drop"], a["seed"], s["q_off"], s["k_off"])
+        lse = s["lse"].reshape(-1)[:B * H * nq].view(B, H, nq).clone()
+        run()
+        self._ref.attn_probs(**s)
+        ref = s["probs"].reshape(-1)[:B * H * nq * nk].view(B, H, nq, nk)
+        bound = BD.attn_probs_bound(Q, K, None, valid.expand(B, H, nq, nk), keep, a["scale"], lse, ref)
+        kern = f"attn_probs_kernel{' + dropout' if a['p_drop'] > 0 else ''}{' packed' if a['q_off'] is not None or a['k_off'] is not None else ''}"
+        return [("probs", BD.check(a["probs"].reshape(-1)[:B * H * nq * nk].view(B, H, nq, nk), ref, bound, "attn_probs"), kern)]
 
     def chk_gemm_wgrad_group(self, a, s, run):
         probs, mask = s["problems"], a["overwrite_mask"]
@@ -281,7 +532,7 @@ class Recorder:
                 bnd = BD.SLACK * tt.sum(0) + BD.SLACK * (ref_rows.shape[0] + 1) * BD.U32 * (ref_rows.abs().sum(0)
                                                                                         + bias_prev[i * HD:(i + 1) * HD].abs()) \
                     + BD.U32 * ref_b.abs() + BD.TINY
-                res.append((f"bias {nm}", BD.check(a["bias_grad"][i * HD:(i + 1) * HD], ref_b, bnd, f"sdpa_bwd bias {nm}"), kern))
+                self._sum_out(res, f"bias {nm}", a["bias_grad"][i * HD:(i + 1) * HD], ref_b, bias_prev[i * HD:(i + 1) * HD], bnd, kern)
         return res
 
     # ------------------------------------------------------------------------------------------------ LayerNorm family
@@ -304,18 +555,16 @@ class Recorder:
         assert "dgamma" in prev and "dbeta" in prev
         keep = None
         if a["dx_dropped"] is not None and a["p_drop"] > 0:
-            keep = keep_scale(self._ref._seed(a["seed"]), torch.arange(M)[:, None], torch.arange(N)[None, :], a["p_drop"])
-            keep = keep.to(dy.device).double()
+            keep = keep_scale(self._ref._seed(a["seed"]), torch.arange(M, device=dy.device)[:, None],
+                              torch.arange(N, device=dy.device)[None, :], a["p_drop"]).double()
         run()
         self._ref.layernorm_bwd(**s)
         dx = _v2(s["dx"], M, N, N)
         bdx, t, bdg, bdb = BD.ln_bwd_bounds(dy, x, s["gamma"].double(), mean, rstd, dx, a["dx"].dtype)
         kern = "ln_bwd_dma_kernel" if (M >= 16384 and N == 768) else "ln_bwd_kernel"
-        res = [("dx", BD.check(_v2(a["dx"], M, N, N), dx, bdx, "layernorm_bwd dx"), kern),
-               ("dgamma", BD.check(a["dgamma"], s["dgamma"], bdg + BD.U32 * (s["dgamma"].abs() + prev["dgamma"].abs()),
-                                   "layernorm_bwd dgamma"), kern),
-               ("dbeta", BD.check(a["dbeta"], s["dbeta"], bdb + BD.U32 * (s["dbeta"].abs() + prev["dbeta"].abs()),
-                                  "layernorm_bwd dbeta"), kern)]
+        res = [("dx", BD.check(_v2(a["dx"], M, N, N), dx, bdx, "layernorm_bwd dx"), kern)]
+        self._sum_out(res, "dgamma", a["dgamma"], s["dgamma"], prev["dgamma"], bdg + BD.U32 * (s["dgamma"].abs() + prev["dgamma"].abs()), kern)
+        self._sum_out(res, "dbeta", a["dbeta"], s["dbeta"], prev["dbeta"], bdb + BD.U32 * (s["dbeta"].abs() + prev["dbeta"].abs()), kern)
         if keep is not None:
             dd = _v2(s["dx_dropped"], M, N, N)
             bdd = BD.U16 * dd.abs() + BD.SLACK * keep * t + BD.TINY
@@ -324,7 +573,7 @@ class Recorder:
                 ref = s["dbias_prev"]
                 bb = (BD.U16 * dd.abs() + BD.SLACK * keep * t).sum(0) + BD.SLACK * (M + 1) * BD.U32 * (
                     dd.abs().sum(0) + prev["dbias_prev"].abs()) + BD.U32 * ref.abs() + BD.TINY
-                res.append(("dbias_prev", BD.check(a["dbias_prev"], ref, bb, "layernorm_bwd dbias_prev"), kern))
+                self._sum_out(res, "dbias_prev", a["dbias_prev"], ref, prev["dbias_prev"], bb, kern)
         return res
 
     def _box(self, s, M, N, P):
@@ -372,18 +621,17 @@ class Recorder:
         t2 = BD.SLACK * t2
         kern = "visn_ln_bwd"
 
+        res = [("dxv", BD.check(_v2(a["dxv"], M, N, N), _v2(s["dxv"], M, N, N), b1, "visn_ln_bwd dxv"), kern)]
+
         def acc(k, bnd):
-            ref = s[k].reshape(-1)
-            return BD.check(a[k].reshape(-1), ref, bnd.reshape(-1) + BD.U32 * (ref.abs() + prev[k].reshape(-1).abs()), f"visn {k}")
+            ref, pv = s[k].reshape(-1), prev[k].reshape(-1)
+            self._sum_out(res, k, a[k].reshape(-1), ref, pv, bnd.reshape(-1) + BD.U32 * (ref.abs() + pv.abs()), kern)
         dw_terms = (d2.abs().t() @ pos.abs())
-        res = [("dxv", BD.check(_v2(a["dxv"], M, N, N), _v2(s["dxv"], M, N, N), b1, "visn_ln_bwd dxv"), kern),
-               ("dgv", acc("dgv", bg1), kern), ("dbv", acc("dbv", bb1), kern), ("dgb", acc("dgb", bg2), kern),
-               ("dbb", acc("dbb", bb2), kern),
-               ("dwbox", acc("dwbox", t2.t() @ pos.abs() + BD.SLACK * (M + 1) * BD.U32 * dw_terms), kern),
-               ("dbbox", acc("dbbox", t2.sum(0) + BD.SLACK * (M + 1) * BD.U32 * d2.abs().sum(0)), kern)]
+        acc("dgv", bg1), acc("dbv", bb1), acc("dgb", bg2), acc("dbb", bb2)
+        acc("dwbox", t2.t() @ pos.abs() + BD.SLACK * (M + 1) * BD.U32 * dw_terms)
+        acc("dbbox", t2.sum(0) + BD.SLACK * (M + 1) * BD.U32 * d2.abs().sum(0))
         if a["dbias_visn"] is not None:
-            res.append(("dbias_visn", acc("dbias_visn", (BD.U16 * d1.abs() + BD.SLACK * t1).sum(0)
-                                          + BD.SLACK * (M + 1) * BD.U32 * d1.abs().sum(0)), kern))
+            acc("dbias_visn", (BD.U16 * d1.abs() + BD.SLACK * t1).sum(0) + BD.SLACK * (M + 1) * BD.U32 * d1.abs().sum(0))
         return res
 
     def chk_embed_ln_fwd(self, a, s, run):
@@ -453,12 +701,15 @@ class Recorder:
     def _colsum_like(self, name, a, s, run):
         M, N = a["M"], a["N"]
         sa = dict(s, x=_v2(s["x"], M, N, a["ldx"]).abs().contiguous(), ldx=N, out=s["out"].abs())
+        prev = s["out"][:N].clone()
         run()
         getattr(self._ref, name)(**sa)
         getattr(self._ref, name)(**s)
         ref = s["out"][:N]
         bnd = BD.U32 * ref.abs() + BD.SLACK * (M + 1) * BD.U32 * sa["out"][:N] + BD.TINY
-        return [("out", BD.check(a["out"][:N], ref, bnd, name), name + " (two-stage)")]
+        res = []
+        self._sum_out(res, "out", a["out"][:N], ref, prev, bnd, name + " (two-stage)")
+        return res
 
     def chk_colsum(self, a, s, run):
         return self._colsum_like("colsum", a, s, run)
@@ -646,12 +897,13 @@ def test_every_numeric_call_of_a_bf16_training_step_is_within_its_bound(monkeypa
     dev = {k: v.cuda() for k, v in batch.items()}
     losses = tr.step(dev)
     tr.sync()
-    torch.cuda.synchronize()
+    _sync()
     assert tr.engine.packed, "the language rows ran dense: the packed attention paths were not exercised"
     assert all(torch.isfinite(torch.as_tensor(x)).all() for x in losses if x is not None)
     _table(rec.rows, time.time() - t0)
     assert not rec.unchecked, f"numeric methods without a checker: {sorted(rec.unchecked)}"
     assert not rec.failures, "\n".join(rec.failures)
+    assert not rec.leftover(), rec.leftover()
     for must in ("gemm", "gemm_wgrad_group", "sdpa_fwd", "sdpa_bwd", "layernorm_fwd", "layernorm_bwd", "ce_fwd_bwd", "sumsq", "adamw"):
         assert must in rec.called, must
     print(f"methods called: {sorted(rec.called)}; run time {time.time() - t0:.1f} s")
@@ -701,6 +953,25 @@ def test_gemm_ragged_tiles_padded_ld_and_short_k_within_bounds(pingpong):
         cs, ws = torch.zeros(N, device="cuda"), torch.zeros(rec.workspace_floats(N), device="cuda")
         rec.gemm(A, W, C, bias, None, None, M, N, K, lda, ldb, ldc, colsum=cs, ws=ws)
     _done(rec, t0, 24)
+
+
+@pytest.mark.parametrize("pingpong", [1, 2], ids=["default_dispatch", "pingpong_forced"])
+def test_gemm_m_major_operands_with_an_odd_extent_within_bounds(pingpong):
+    """dW = dY^T X as the 3 129-answer head issues it: A [K, M] and B [K, N] row-major (a_kmajor = b_kmajor = 0), fp32 out, with M
+    -- then N -- odd (3129 inside a leading dimension of 3136, the pad columns holding other data).  Row M-1 of the product lost
+    its last K term on the ping-pong kernel before its buffer range was rounded to whole 16-byte pieces (csrc/gemm_pp_kernel.h)."""
+    t0 = time.time()
+    rec = _rec()
+    rec.set_gemm_pingpong(pingpong)
+    g = torch.Generator(device="cuda").manual_seed(12)
+    K, M, N, ld = 128, 3129, 1536, 3136
+    dY, X = _rn(g, K, ld, scale=0.01), _rn(g, K, N)
+    C = torch.zeros(M, N, device="cuda")
+    rec.gemm(dY, X, C, None, None, None, M, N, K, ld, N, N, a_kmajor=0, b_kmajor=0, out_f32=True)
+    C = torch.zeros(N, ld, device="cuda")
+    rec.gemm(X, dY, C, None, None, None, N, M, K, N, ld, ld, a_kmajor=0, b_kmajor=0, out_f32=True)
+    rec.gemm_wgrad_group([(dY, X, torch.zeros(M, N, device="cuda"), M, N, K, ld, N, N)], overwrite_mask=1)
+    _done(rec, t0, 3)
 
 
 def test_gelu_bwd_tails_within_bound():

@@ -113,8 +113,12 @@ __device__ __forceinline__ void pp_tile(const GemmParams& p, int tm, int tn, int
         return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
                                                  __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
     };
-    const __amdgpu_buffer_rsrc_t ra = rsrc_of(A, (uint32_t)(((size_t)((AK ? p.M : p.K) - 1) * p.lda + (AK ? p.K : p.M)) * 2));
-    const __amdgpu_buffer_rsrc_t rb = rsrc_of(B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : p.N)) * 2));
+    // An M-major (N-major) operand's range ends at a multiple of 8 elements in its last K row: the range check works on whole
+    // dwords, so with an odd M the dword that holds element M-1 of the last row was out of range and read as zero -- row M-1 of
+    // the product lost its last K term (the 3129-answer head's weight gradient; tests/test_kernel_bounds_gpu.py checks it per
+    // element).  The 16-byte pieces never start beyond ld - 8 (srca / srcb above), so the rounded range stays inside the row.
+    const __amdgpu_buffer_rsrc_t ra = rsrc_of(A, (uint32_t)(((size_t)((AK ? p.M : p.K) - 1) * p.lda + (AK ? p.K : ((p.M + 7) & ~7))) * 2));
+    const __amdgpu_buffer_rsrc_t rb = rsrc_of(B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : ((p.N + 7) & ~7))) * 2));
     auto stage_a = [&](auto H, int kt) {
         constexpr int h = decltype(H)::value;
         const int k0 = kbeg + kt * BK;

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_pp_persist_kernel(GemmParams
                                                  __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
     };
     const __amdgpu_buffer_rsrc_t ra = rsrc_of(A, (uint32_t)(((size_t)(p.M - 1) * p.lda + p.K) * 2));
-    const __amdgpu_buffer_rsrc_t rb = rsrc_of(B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : p.N)) * 2));
+    const __amdgpu_buffer_rsrc_t rb = rsrc_of(B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : ((p.N + 7) & ~7))) * 2));     // whole dwords of the last row: see gemm_pp_kernel.h
 
     // tile-independent part of the per-lane source offsets (bytes): the lane's 16 bytes inside a 1 KiB piece
     uint32_t la[2][NA], lb[NB][PB];

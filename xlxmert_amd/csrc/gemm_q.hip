@@ -63,7 +63,7 @@ __global__ __launch_bounds__(512, 4) void gemm_bf16_q_kernel(GemmParams p) {
                                                  __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
     };
     const __amdgpu_buffer_rsrc_t ra = rsrc_of(p.A, (uint32_t)(((size_t)(p.M - 1) * p.lda + p.K) * 2));
-    const __amdgpu_buffer_rsrc_t rb = rsrc_of(p.B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : p.N)) * 2));
+    const __amdgpu_buffer_rsrc_t rb = rsrc_of(p.B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : ((p.N + 7) & ~7))) * 2));     // whole dwords of the last row: see gemm_pp_kernel.h
     auto stage = [&](int kt) {
         const int k0 = kt * BK;
         uint8_t* dst = smem + (kt & 1) * BUF;

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_relay_kernel(GemmParams p) {
                                                  __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
     };
     const __amdgpu_buffer_rsrc_t ra = rsrc_of(p.A, (uint32_t)(((size_t)(p.M - 1) * p.lda + p.K) * 2));
-    const __amdgpu_buffer_rsrc_t rb = rsrc_of(p.B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : p.N)) * 2));
+    const __amdgpu_buffer_rsrc_t rb = rsrc_of(p.B, (uint32_t)(((size_t)((BKM ? p.N : p.K) - 1) * p.ldb + (BKM ? p.K : ((p.N + 7) & ~7))) * 2));     // whole dwords of the last row: see gemm_pp_kernel.h
     // per-lane byte offsets of the lane's 16 bytes inside a 1 KiB piece: K-major pieces are 8 rows x 128 B whose chunk swizzle
     // depends on the piece's parity; M-major pieces are 4 k-rows x 256 B (one pattern).  The piece's first row goes into the
     // scalar offset.
