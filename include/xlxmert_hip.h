@@ -59,6 +59,9 @@ extern "C" {
                              * pre-activation (same bytes; erf and exp(-x^2/2) are already in registers), so that the backward
                              * epilogue is a multiply -- XL_EPI_MULAUX -- instead of a second erf + exp per element        */
 #define XL_EPI_MULAUX   7   /* C = acc * aux                      (backward of XL_EPI_GELU_DG)                            */
+#define XL_EPI_RESIDUAL_F32 8 /* XL_EPI_RESIDUAL with an fp32 residual stream: `residual` is fp32 [M,N] (ldr in elements) whatever
+                             * in_dtype says about A / B, out_dtype must be XL_F32.  Same dropout draw as XL_EPI_RESIDUAL: for one
+                             * seed the kept / dropped pattern of a launch is identical                                      */
 
 const char* xl_last_error(void);
 int  xl_version(void);
@@ -168,6 +171,18 @@ int xl_layernorm_bwd(const void* dy, const void* x, const float* gamma, const fl
                      const float* rstd, void* dx, float* dgamma, float* dbeta, float* dbias_prev,
                      int M, int N, float* workspace, void* dx_dropped, float p_drop, uint64_t seed,
                      int dtype, void* stream);
+/* LayerNorm of the fp32 residual stream (bf16 compute mode with residual_dtype = fp32): fp32 rows in, N a multiple of 4.
+ * xl_layernorm_fwd_res: y32 = LN(x) in fp32 and y16 = bf16(y32), round to nearest even of the very value stored in y32 -- the
+ *   operand of the contractions that read the LayerNorm output; mean / rstd as xl_layernorm_fwd.
+ * xl_layernorm_bwd_res: dy, x (the saved pre-LayerNorm sum) and dx (the gradient that continues along the residual path) are
+ *   fp32; dx_dropped is bf16 and ALWAYS written: bf16(dx * mask(seed)) -- with p_drop = 0 it is bf16(dx) --, the A / B operand
+ *   of the dense layer's dX and dW contractions.  dgamma / dbeta / dbias_prev (column sums of the masked gradient), the
+ *   workspace and the deferred second stage: exactly as xl_layernorm_bwd. */
+int xl_layernorm_fwd_res(const float* x, const float* gamma, const float* beta, float* y32, void* y16,
+                         float* mean, float* rstd, int M, int N, float eps, void* stream);
+int xl_layernorm_bwd_res(const float* dy, const float* x, const float* gamma, const float* mean,
+                         const float* rstd, float* dx, float* dgamma, float* dbeta, float* dbias_prev,
+                         int M, int N, float* workspace, void* dx_dropped, float p_drop, uint64_t seed, void* stream);
 /* Column reductions (LayerNorm affine / bias gradients, column sums) run as a two-stage reduction through a
  * caller-owned fp32 `workspace` of at least xl_workspace_floats(N) elements (per-block partial slabs + one
  * combine launch); workspace == NULL falls back to fp32 atomics on the output. */

@@ -194,9 +194,13 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_mfma_kernel(GemmPar
     const int mq = m0 + wm, nq = n0 + wn;
     if constexpr (EPIK >= 0) {
         if (mq + 64 <= p.M && nq + 64 <= p.N) {
-            QuadOperand op;
-            quad_operand_load<EPIK>(p, lane, mq, nq, op);
-            epilogue_quad_fast<EPIK>(p, wbuf, lane, first, mq, nq, op, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+            if constexpr (EPIK == XL_EPI_RESIDUAL_F32) {
+                epilogue_quad_fast_res32(p, wbuf, lane, first, mq, nq, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+            } else {
+                QuadOperand op;
+                quad_operand_load<EPIK>(p, lane, mq, nq, op);
+                epilogue_quad_fast<EPIK>(p, wbuf, lane, first, mq, nq, op, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+            }
             return;
         }
     }
@@ -220,6 +224,7 @@ static void launch_mfma(const GemmParams& p, int epik, int nblk, hipStream_t st)
             case XL_EPI_GELU: return launch_one<AK, BKM, true, XL_EPI_GELU>(p, nblk, st);
             case XL_EPI_RESIDUAL: return launch_one<AK, BKM, true, XL_EPI_RESIDUAL>(p, nblk, st);
             case XL_EPI_DGELU: return launch_one<AK, BKM, true, XL_EPI_DGELU>(p, nblk, st);
+            case XL_EPI_RESIDUAL_F32: return launch_one<AK, BKM, true, XL_EPI_RESIDUAL_F32>(p, nblk, st);
             case XL_EPI_GELU_DG:
                 if constexpr (BKM) return launch_one<AK, BKM, true, XL_EPI_GELU_DG>(p, nblk, st);
                 break;
@@ -338,7 +343,10 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     XL_CHECK_ARG(A && B && (C || epilogue == XL_EPI_ROWMAX), XL_ERR_BAD_ARG, "xl_gemm: null operand");
     XL_CHECK_ARG(lda >= (a_kmajor ? K : M) && ldb >= (b_kmajor ? K : N) && ldc >= N, XL_ERR_BAD_SHAPE,
                  "xl_gemm: leading dimension too small (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
-    XL_CHECK_ARG(epilogue >= XL_EPI_NONE && epilogue <= XL_EPI_MULAUX, XL_ERR_BAD_ARG, "xl_gemm: bad epilogue %d", epilogue);
+    XL_CHECK_ARG(epilogue >= XL_EPI_NONE && epilogue <= XL_EPI_RESIDUAL_F32, XL_ERR_BAD_ARG, "xl_gemm: bad epilogue %d", epilogue);
+    const bool res32 = epilogue == XL_EPI_RESIDUAL_F32;       // fp32 residual stream: fp32 operand and output, A / B as in_dtype says
+    if (res32) XL_CHECK_ARG(residual && ldr >= N && out_dtype == XL_F32 && !colsum_out, XL_ERR_BAD_ARG,
+                            "xl_gemm: XL_EPI_RESIDUAL_F32 needs an fp32 residual, out_dtype XL_F32 and no colsum_out");
     if (epilogue == XL_EPI_ROWMAX)
         XL_CHECK_ARG(in_dtype == XL_BF16 && a_kmajor && b_kmajor && M % 256 == 0 && N % 256 == 0 && K % 8 == 0 && lda % 8 == 0 &&
                      ldb % 8 == 0 && aux && aligned16(aux) && aligned16(A) && aligned16(B) && (!bias || aligned16(bias)) &&
@@ -437,6 +445,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
         p.vec_epi = 1;
     }
     if (epilogue == XL_EPI_RESIDUAL) p.vec_epi = p.vec_epi && aligned16(residual) && ldr % 8 == 0;
+    if (res32) p.vec_epi = p.vec_epi && aligned16(residual) && ldr % 4 == 0;
     if (epilogue == XL_EPI_GELU || epilogue == XL_EPI_DGELU || epilogue == XL_EPI_GELU_DG || epilogue == XL_EPI_MULAUX)
         p.vec_epi = p.vec_epi && aligned16(aux) && ldx % 8 == 0;
     // fast (templated) epilogue: aligned rows, a kind that has one, plain stores
@@ -535,7 +544,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     if (cx.gemm_duo < 0) cx.gemm_duo = env_int("XL_GEMM_DUO", 1);
     static const int duo_max_tiles = env_int("XL_GEMM_DUO_MAX_TILES", 64);
     int bm = 256;
-    if (!epi_split && pp_ok && pp_mode && cx.gemm_duo && a_kmajor && M % 128 == 0 && N % 192 == 0 && out_dtype == in_dtype && !accumulate && epik >= 0 &&
+    if (!epi_split && pp_ok && pp_mode && cx.gemm_duo && a_kmajor && M % 128 == 0 && N % 192 == 0 && (out_dtype == in_dtype || res32) && !accumulate && epik >= 0 &&
         colsum_out == nullptr && epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && splitk == 1 && !p.atomic_out &&
         (double)M * lda < 1e9 && (cx.gemm_duo == 2 || t256n <= duo_max_tiles)) {
         bm = 128; bn = 192;
@@ -585,8 +594,11 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
         XL_CHECK_ARG(e == hipErrorInvalidValue, XL_ERR_HIP, "xl_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     }
 #endif
-    if (use_pp || bm == 128 || epi_split) {
-        hipError_t e = launch_pp(p, a_kmajor, b_kmajor, epik, bn, nblk, st, bm);
+    if ((use_pp || bm == 128) && epik == XL_EPI_RESIDUAL_F32 && a_kmajor) {
+        hipError_t e = launch_pp_res32(p, b_kmajor, bm, nblk, st);
+        XL_CHECK_ARG(e == hipSuccess, XL_ERR_HIP, "xl_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    } else if (use_pp || bm == 128 || epi_split) {
+        hipError_t e = launch_pp(p, a_kmajor, b_kmajor, epik == XL_EPI_RESIDUAL_F32 ? -1 : epik, bn, nblk, st, bm);
         XL_CHECK_ARG(e == hipSuccess, XL_ERR_HIP, "xl_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     } else if (mfma_ok) {
         if (a_kmajor && b_kmajor) launch_mfma<true, true>(p, epik, nblk, st);

@@ -43,6 +43,11 @@ __device__ __forceinline__ void epilogue_store(const GemmParams& p, int m, int n
             v += Elem<TIn>::ld(res + (size_t)m * p.ldr + n);
             break;
         }
+        case XL_EPI_RESIDUAL_F32: {       // fp32 residual stream: the same draw as XL_EPI_RESIDUAL, an fp32 operand
+            if (p.p_drop > 0.0f) v *= dropout_scale(with_step_seed(p.seed, p.step_seed), (uint32_t)m, (uint32_t)n, p.p_drop, p.inv_keep);
+            v += reinterpret_cast<const float*>(p.residual)[(size_t)m * p.ldr + n];
+            break;
+        }
         case XL_EPI_DGELU: {
             const TIn* aux = reinterpret_cast<const TIn*>(p.aux);
             v *= gelu_erf_grad(Elem<TIn>::ld(aux + (size_t)m * p.ldx + n));
@@ -291,6 +296,17 @@ __device__ __forceinline__ void epilogue_quad(const GemmParams& p, float* wbuf, 
                 }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] += rv[e];
+            } else if (p.epilogue == XL_EPI_RESIDUAL_F32) {
+                const float* r = reinterpret_cast<const float*>(p.residual) + mn * p.ldr + n;
+                const float4 r0 = *reinterpret_cast<const float4*>(r), r1 = *reinterpret_cast<const float4*>(r + 4);
+                const float rv[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+                if (p.p_drop > 0.0f) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        v[e] *= dropout_scale(with_step_seed(p.seed, p.step_seed), (uint32_t)m, (uint32_t)(n + e), p.p_drop, p.inv_keep);
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] += rv[e];
             } else if (p.epilogue == XL_EPI_DGELU) {
                 float av[8];
                 ldvec(reinterpret_cast<const bf16_t*>(p.aux) + mn * p.ldx + n, av);
@@ -329,6 +345,13 @@ __device__ __forceinline__ void epilogue_quad(const GemmParams& p, float* wbuf, 
 // range).  The epilogue kind is a template parameter, the operand rows (residual or aux) of the whole quad are requested
 // BEFORE the LDS transpose and nothing waits on a store: branch-free, one load latency per quad instead of eight.
 struct QuadOperand { uint4 row[8]; };      // residual (RESIDUAL) or saved pre-activation (DGELU): 8 rows x 8 bf16 per lane
+// XL_EPI_RESIDUAL_F32: a lane's 8 columns of a row are two uint4 (row[2 ps], row[2 ps + 1]), so one QuadOperand holds FOUR row groups
+// -- a 32 x 64 half quad (NPS = 4) or a 64 x 32 sub-tile: the callers load the operand per half quad, and the two operands in flight
+// take the 64 registers the bf16 epilogue's two whole-quad operands take.
+__device__ __forceinline__ void unpack8_f32(const uint4& a, const uint4& b, float (&v)[8]) {
+    v[0] = __uint_as_float(a.x); v[1] = __uint_as_float(a.y); v[2] = __uint_as_float(a.z); v[3] = __uint_as_float(a.w);
+    v[4] = __uint_as_float(b.x); v[5] = __uint_as_float(b.y); v[6] = __uint_as_float(b.z); v[7] = __uint_as_float(b.w);
+}
 
 // ---- the same pieces for a sub-tile of 64 rows x W columns (W = 64: the quad above; W = 32: the third accumulator column of
 // the 256x192 kernel's 64x96 wave tile): W/8 lanes share a row, 512/W rows per pass, W/8 passes.
@@ -354,6 +377,16 @@ __device__ __forceinline__ void sub_row_from_lds(const float* wbuf, int row, int
 }
 template <int EPI, int W, int ROWS = 64>
 __device__ __forceinline__ void sub_operand_load(const GemmParams& p, int lane, int mq, int nq, QuadOperand& op) {
+    if constexpr (EPI == XL_EPI_RESIDUAL_F32) {
+        constexpr int LPR = W / 8, RPP = 64 / LPR, NPS = ROWS / RPP;
+        static_assert(NPS <= 4, "an fp32 operand: at most four row groups per QuadOperand");
+        const float* s0 = reinterpret_cast<const float*>(p.residual) + (size_t)(mq + lane / LPR) * p.ldr + nq + (lane % LPR) * 8;
+#pragma unroll
+        for (int ps = 0; ps < NPS; ++ps) {
+            op.row[2 * ps] = *reinterpret_cast<const uint4*>(s0 + (size_t)(ps * RPP) * p.ldr);
+            op.row[2 * ps + 1] = *reinterpret_cast<const uint4*>(s0 + (size_t)(ps * RPP) * p.ldr + 4);
+        }
+    }
     if constexpr (EPI == XL_EPI_RESIDUAL || EPI == XL_EPI_DGELU || EPI == XL_EPI_MULAUX) {
         constexpr int LPR = W / 8, RPP = 64 / LPR, NPS = ROWS / RPP;
         const bf16_t* src = reinterpret_cast<const bf16_t*>(EPI == XL_EPI_RESIDUAL ? p.residual : p.aux);
@@ -377,6 +410,15 @@ __device__ __forceinline__ void sub_load_bias8(const GemmParams& p, int lane, bo
 
 template <int EPI, int NPS = 8>           // NPS row groups of 8 rows: 8 = a 64 x 64 quad, 4 = a 32 x 64 half quad
 __device__ __forceinline__ void quad_operand_load(const GemmParams& p, int lane, int mq, int nq, QuadOperand& op) {
+    if constexpr (EPI == XL_EPI_RESIDUAL_F32) {
+        static_assert(NPS <= 4, "an fp32 operand: one QuadOperand per 32 x 64 half quad");
+        const float* s0 = reinterpret_cast<const float*>(p.residual) + (size_t)(mq + (lane >> 3)) * p.ldr + nq + (lane & 7) * 8;
+#pragma unroll
+        for (int ps = 0; ps < NPS; ++ps) {
+            op.row[2 * ps] = *reinterpret_cast<const uint4*>(s0 + (size_t)(ps * 8) * p.ldr);
+            op.row[2 * ps + 1] = *reinterpret_cast<const uint4*>(s0 + (size_t)(ps * 8) * p.ldr + 4);
+        }
+    }
     if constexpr (EPI == XL_EPI_RESIDUAL || EPI == XL_EPI_DGELU || EPI == XL_EPI_MULAUX) {
         const bf16_t* src = reinterpret_cast<const bf16_t*>(EPI == XL_EPI_RESIDUAL ? p.residual : p.aux);
         const int ld = EPI == XL_EPI_RESIDUAL ? p.ldr : p.ldx;
@@ -453,7 +495,7 @@ __device__ __forceinline__ void load_bias8(const GemmParams& p, int lane, bool f
 // the dropout seed of a launch (site seed + device-resident step part): ONE fetch per workgroup, ahead of the K loop
 template <int EPI>
 __device__ __forceinline__ uint64_t dropout_seed_of(const GemmParams& p) {
-    if constexpr (EPI == XL_EPI_RESIDUAL) return p.p_drop > 0.0f ? with_step_seed(p.seed, p.step_seed) : 0;
+    if constexpr (EPI == XL_EPI_RESIDUAL || EPI == XL_EPI_RESIDUAL_F32) return p.p_drop > 0.0f ? with_step_seed(p.seed, p.step_seed) : 0;
     else return 0;
 }
 
@@ -474,9 +516,10 @@ __device__ __forceinline__ void epilogue_rows_fast(const GemmParams& p, const fl
         if constexpr (EPI == XL_EPI_GELU) {
             stvec(reinterpret_cast<bf16_t*>(p.aux) + m * p.ldx + n, v);
             gelu_fast8(v);
-        } else if constexpr (EPI == XL_EPI_RESIDUAL) {
+        } else if constexpr (EPI == XL_EPI_RESIDUAL || EPI == XL_EPI_RESIDUAL_F32) {
             float rv[8];
-            unpack8(op.row[ps], rv);
+            if constexpr (EPI == XL_EPI_RESIDUAL_F32) unpack8_f32(op.row[2 * ps], op.row[2 * ps + 1], rv);
+            else unpack8(op.row[ps], rv);
             if (drop) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] *= dropout_scale(seed, (uint32_t)m, (uint32_t)(n + e), p.p_drop, p.inv_keep);
@@ -557,9 +600,10 @@ __device__ __forceinline__ void sub_rows_fast(const GemmParams& p, const float* 
         if constexpr (EPI == XL_EPI_GELU) {
             stvec(reinterpret_cast<bf16_t*>(p.aux) + m * p.ldx + n, v);
             gelu_fast8(v);
-        } else if constexpr (EPI == XL_EPI_RESIDUAL) {
+        } else if constexpr (EPI == XL_EPI_RESIDUAL || EPI == XL_EPI_RESIDUAL_F32) {
             float rv[8];
-            unpack8(op.row[ps], rv);
+            if constexpr (EPI == XL_EPI_RESIDUAL_F32) unpack8_f32(op.row[2 * ps], op.row[2 * ps + 1], rv);
+            else unpack8(op.row[ps], rv);
             if (drop) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] *= dropout_scale(seed, (uint32_t)m, (uint32_t)(n + e), p.p_drop, p.inv_keep);
@@ -616,6 +660,23 @@ __device__ __forceinline__ void epilogue_quad_fast(const GemmParams& p, float* w
     quad_to_lds(wbuf, lane, a00, a01, a10, a11);
     epilogue_rows_fast<EPI>(p, wbuf, lane, first, mq, nq, op, cs, bv, dropout_seed_of<EPI>(p));
     if (p.colsum_ws != nullptr) colsum_flush(p, lane, mq >> 6, nq, cs);          // one slab per 64 rows
+}
+
+// XL_EPI_RESIDUAL_F32 on one 64 x 64 quad: the operand of each 32-row half is requested before the transpose
+__device__ __forceinline__ void epilogue_quad_fast_res32(const GemmParams& p, float* wbuf, int lane, bool first, int mq, int nq,
+                                                         const f32x16_t& a00, const f32x16_t& a01, const f32x16_t& a10, const f32x16_t& a11) {
+    constexpr int EPI = XL_EPI_RESIDUAL_F32;
+    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float bv[8];
+    QuadOperand op0, op1;
+    quad_operand_load<EPI, 4>(p, lane, mq, nq, op0);
+    quad_operand_load<EPI, 4>(p, lane, mq + 32, nq, op1);
+    load_bias8(p, lane, first, nq, bv);
+    const uint64_t seed = dropout_seed_of<EPI>(p);
+    quad_to_lds(wbuf, lane, a00, a01, a10, a11);
+    epilogue_rows_fast<EPI, 4>(p, wbuf, lane, first, mq, nq, op0, cs, bv, seed);
+    epilogue_rows_fast<EPI, 4>(p, wbuf + 32 * 64, lane, first, mq + 32, nq, op1, cs, bv, seed);
+    if (p.colsum_ws != nullptr) colsum_flush(p, lane, mq >> 6, nq, cs);
 }
 
 // ---- split-K without atomics on the output (ping-pong kernel).  The splits of one output tile meet in memory: every
@@ -745,6 +806,8 @@ hipError_t launch_pp_group(const GroupParams& g, int nblk, hipStream_t st);
 // the host for launches whose C / residual / aux rows are 16-byte aligned (interior tiles take it, edge tiles fall back)
 // bn: 256 (256x256 tile) or 192 (256x192 tile: N a multiple of 192, every tile interior, fast epilogue, no fused column sums)
 hipError_t launch_pp(const GemmParams& p, int a_kmajor, int b_kmajor, int epik, int bn, int nblk, hipStream_t st, int bm = 256);
+// gemm_pp_res32.hip: the XL_EPI_RESIDUAL_F32 instances of the ping-pong kernel (A K-major; 256x256 tiles, or bm = 128: 128x192 duo tiles)
+hipError_t launch_pp_res32(const GemmParams& p, int b_kmajor, int bm, int nblk, hipStream_t st);
 // gemm_pp_pair.hip: two problems per launch (gemm_pp_kernel.h gemm_bf16_pp_pair_kernel), 256x256 tiles, A K-major, fast epilogue;
 // hipErrorInvalidValue: no instance for this (layout, epilogue kind) -- forward layout: NONE / RESIDUAL / GELU_DG, dX layout:
 // NONE / RESIDUAL / MULAUX.  tiles0: problem 0's tile count (linear tiles [0, tiles0) are its, the rest problem 1's)

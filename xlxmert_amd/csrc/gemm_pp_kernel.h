@@ -341,6 +341,29 @@ __device__ __forceinline__ void pp_tile(const GemmParams& p, int tm, int tn, int
         // 64 x 96 wave tile = one 64x64 quad + one 64x32 half quad; the host sends only launches here whose tiles are all
         // interior and take the fast epilogue
         static_assert(EPIK >= 0, "the 256x192 tile has the fast epilogue only");
+        if constexpr (EPIK == XL_EPI_RESIDUAL_F32) {
+            // fp32 residual operand: one QuadOperand per 32 x 64 half quad / per 64 x 32 sub-tile, two in flight (64 registers,
+            // what the bf16 epilogue's op0 / op1 take); each is requested as soon as its predecessor's rows are done
+            QuadOperand opa, opb;
+            quad_operand_load<EPIK, 4>(p, lane, mw, nw, opa);
+            __builtin_amdgcn_sched_barrier(0);
+            quad_to_lds(wbuf, lane, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+            __builtin_amdgcn_sched_barrier(0);
+            quad_operand_load<EPIK, 4>(p, lane, mw + 32, nw, opb);
+            __builtin_amdgcn_sched_barrier(0);
+            float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            epilogue_rows_fast<EPIK, 4>(p, wbuf, lane, first, mw, nw, opa, cs, bias8, dseed);
+            __builtin_amdgcn_sched_barrier(0);
+            sub_operand_load<EPIK, 32>(p, lane, mw, nw + 64, opa);
+            __builtin_amdgcn_sched_barrier(0);
+            epilogue_rows_fast<EPIK, 4>(p, wbuf + 32 * 64, lane, first, mw + 32, nw, opb, cs, bias8, dseed);
+            __builtin_amdgcn_sched_barrier(0);
+            half_to_lds(wbuf, lane, acc[0][2], acc[1][2]);
+            __builtin_amdgcn_sched_barrier(0);
+            sub_rows_fast<EPIK, 32>(p, wbuf, lane, mw, nw + 64, opa, bias8b, dseed);
+            if (p.trace != nullptr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(3); }
+            return;
+        } else {
         QuadOperand op0, op1;
         quad_operand_load<EPIK>(p, lane, mw, nw, op0);
         __builtin_amdgcn_sched_barrier(0);
@@ -356,8 +379,39 @@ __device__ __forceinline__ void pp_tile(const GemmParams& p, int tm, int tn, int
         sub_rows_fast<EPIK, 32>(p, wbuf, lane, mw, nw + 64, op1, bias8b, dseed);
         if (p.trace != nullptr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(3); }
         return;
+        }
     } else {
         if constexpr (EPIK >= 0) {
+            if constexpr (EPIK == XL_EPI_RESIDUAL_F32) {
+                if (mw + 128 <= p.M && nw + 64 <= p.N) {
+                    // fp32 residual operand, loaded per 32 x 64 half quad: two QuadOperands in flight (the 64 registers of the
+                    // bf16 epilogue's op0 / op1), the next half's rows requested as soon as a half's rows are done
+                    QuadOperand opa, opb;
+                    quad_operand_load<EPIK, 4>(p, lane, mw, nw, opa);
+                    __builtin_amdgcn_sched_barrier(0);
+                    quad_to_lds(wbuf, lane, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    quad_operand_load<EPIK, 4>(p, lane, mw + 32, nw, opb);
+                    __builtin_amdgcn_sched_barrier(0);
+                    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    epilogue_rows_fast<EPIK, 4>(p, wbuf, lane, first, mw, nw, opa, cs, bias8, dseed);
+                    __builtin_amdgcn_sched_barrier(0);
+                    quad_operand_load<EPIK, 4>(p, lane, mw + 64, nw, opa);
+                    __builtin_amdgcn_sched_barrier(0);
+                    epilogue_rows_fast<EPIK, 4>(p, wbuf + 32 * 64, lane, first, mw + 32, nw, opb, cs, bias8, dseed);
+                    __builtin_amdgcn_sched_barrier(0);
+                    quad_to_lds(wbuf, lane, acc[2][0], acc[2][1], acc[3][0], acc[3][1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    quad_operand_load<EPIK, 4>(p, lane, mw + 96, nw, opb);
+                    __builtin_amdgcn_sched_barrier(0);
+                    epilogue_rows_fast<EPIK, 4>(p, wbuf, lane, first, mw + 64, nw, opa, cs, bias8, dseed);
+                    __builtin_amdgcn_sched_barrier(0);
+                    epilogue_rows_fast<EPIK, 4>(p, wbuf + 32 * 64, lane, first, mw + 96, nw, opb, cs, bias8, dseed);
+                    if (p.colsum_ws != nullptr) colsum_flush(p, lane, mw >> 7, nw, cs);      // one slab per 128 rows
+                    if (p.trace != nullptr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(3); }
+                    return;
+                }
+            } else
             if (mw + 128 <= p.M && nw + 64 <= p.N) {
                 // the first quad's operand rows are requested before its transpose, the second quad's as soon as the first
                 // quad's accumulators are in LDS (their registers are free from then on)
@@ -499,5 +553,6 @@ hipError_t launch_pp_nt256(const GemmParams& p, int epik, int nblk, hipStream_t 
 hipError_t launch_pp_other256(const GemmParams& p, int a_kmajor, int b_kmajor, int epik, int nblk, hipStream_t st);   // gemm_pp_nn.hip
 hipError_t launch_pp_192(const GemmParams& p, int b_kmajor, int epik, int nblk, hipStream_t st);   // gemm_pp_192.hip
 hipError_t launch_pp_duo(const GemmParams& p, int b_kmajor, int epik, int nblk, hipStream_t st);   // gemm_pp_duo.hip (128x192, two per CU)
+// (XL_EPI_RESIDUAL_F32, the fp32 residual stream: gemm_pp_res32.hip, launch_pp_res32 in gemm_common.h)
 
 }  // namespace xl

@@ -56,7 +56,7 @@ static const PlanFn kFns[] = {
     XL_PLAN_FN(xl_gemm_pair),
 #endif
     XL_PLAN_FN(xl_gemm_wgrad_group), XL_PLAN_FN(xl_layernorm_fwd),
-    XL_PLAN_FN(xl_layernorm_bwd), XL_PLAN_FN(xl_visn_ln_fwd), XL_PLAN_FN(xl_visn_ln_bwd), XL_PLAN_FN(xl_set_deferred_reduce),
+    XL_PLAN_FN(xl_layernorm_bwd), XL_PLAN_FN(xl_layernorm_fwd_res), XL_PLAN_FN(xl_layernorm_bwd_res), XL_PLAN_FN(xl_visn_ln_fwd), XL_PLAN_FN(xl_visn_ln_bwd), XL_PLAN_FN(xl_set_deferred_reduce),
     XL_PLAN_FN(xl_flush_reductions), XL_PLAN_FN(xl_embed_ln_fwd), XL_PLAN_FN(xl_embed_bwd), XL_PLAN_FN(xl_codebook_gather),
     XL_PLAN_FN(xl_masked_colsum), XL_PLAN_FN(xl_colsum), XL_PLAN_FN(xl_dropout), XL_PLAN_FN(xl_gelu_bwd), XL_PLAN_FN(xl_tanh_bwd),
     XL_PLAN_FN(xl_bce_logits_fwd_bwd), XL_PLAN_FN(xl_sdpa_fwd), XL_PLAN_FN(xl_sdpa_bwd), XL_PLAN_FN(xl_mask_counts),

@@ -289,6 +289,120 @@ __global__ __launch_bounds__(W * 64, 4) void ln_bwd_kernel(const T* __restrict__
     flush_colsums3<NIT, VEC, W>(ag, ab, ax, dbias_prev != nullptr, dgamma, dbeta, dbias_prev, N, red, slot);
 }
 
+// ------------------------------------------------------------------ LayerNorm of the fp32 residual stream
+// (bf16 compute mode with an fp32 residual stream, SURVEY.md section 7: the pre-LayerNorm sums, the LayerNorm outputs and their
+// gradients stay fp32; what the next contraction reads is the bf16 rounding of the fp32 value, written by the same kernel.)
+__device__ __forceinline__ void st4bf(bf16_t* p, const float (&v)[4]) {
+    uint2 t;
+    t.x = pack2bf(v[0], v[1]); t.y = pack2bf(v[2], v[3]);
+    *reinterpret_cast<uint2*>(p) = t;
+}
+
+// forward: fp32 row in; y32 = LN(x) and y16 = bf16(y32) -- computed once, stored twice
+template <int NIT>
+__global__ __launch_bounds__(256) void ln_fwd_res_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ y32,
+                                                         bf16_t* __restrict__ y16, float* __restrict__ mean_o,
+                                                         float* __restrict__ rstd_o, int M, int N, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (row >= M) return;
+    float v[NIT][4];
+    load_row<float, NIT>(x + (size_t)row * N, N, lane, v);
+    float mean, rstd;
+    row_stats<NIT, 4>(v, N, lane, eps, mean, rstd);
+    if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int col = (it * 64 + lane) * 4;
+        if (col < N) {
+            float o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = (v[it][i] - mean) * rstd * gamma[col + i] + beta[col + i];
+            stvec(y32 + (size_t)row * N + col, o);
+            st4bf(y16 + (size_t)row * N + col, o);
+        }
+    }
+}
+
+// backward: ln_bwd_kernel<float> (same arithmetic in the same order) with the gradient entering the dense layer written as
+// bf16 on every launch -- bf16(dx * mask), i.e. bf16(dx) without dropout -- beside the fp32 dx of the residual path.  The
+// column sums of that gradient (d bias of the dense layer) add the fp32 values before the rounding, as ln_bwd_kernel does.
+template <int NIT, int W>
+__global__ __launch_bounds__(W * 64, 4) void ln_bwd_res_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                     const float* __restrict__ gamma, const float* __restrict__ mean_i,
+                                                     const float* __restrict__ rstd_i, float* __restrict__ dx,
+                                                     float* dgamma, float* dbeta, float* dbias_prev, int M, int N, float* ws,
+                                                     bf16_t* __restrict__ dx_drop, float p_drop, float inv_keep, uint64_t seed,
+                                                     const uint64_t* __restrict__ step_seed) {
+    constexpr int VEC = 4;
+    seed = with_step_seed(seed, step_seed);
+    __shared__ float red[3 * W * 64 * VEC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float ag[NIT][VEC] = {}, ab[NIT][VEC] = {}, ax[NIT][VEC] = {};
+    __shared__ __attribute__((aligned(16))) float sgamma[NIT * 64 * VEC];      // [it][lane][4]: conflict-free ds_read_b128
+    for (int c = threadIdx.x; c < NIT * 64 * VEC; c += W * 64) sgamma[c] = c < N ? gamma[c] : 0.f;
+    __syncthreads();
+    const bool drop = p_drop > 0.f;
+    for (int row = blockIdx.x * W + wave; row < M; row += gridDim.x * W) {
+        float xv[NIT][VEC], dv[NIT][VEC];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int col = (it * 64 + lane) * VEC;
+            if (col < N) {
+                ldvec(x + (size_t)row * N + col, xv[it]);
+                ldvec(dy + (size_t)row * N + col, dv[it]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) xv[it][i] = dv[it][i] = 0.f;
+            }
+        }
+        int goff = lane * 4;
+        asm volatile("" : "+v"(goff));          // keep the LDS reads inside the loop (see ln_bwd_kernel)
+        const float mean = mean_i[row], rstd = rstd_i[row];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int col = (it * 64 + lane) * VEC;
+            if (col < N) {
+                float gm[VEC];
+                *reinterpret_cast<float4*>(&gm[0]) = *reinterpret_cast<const float4*>(__builtin_assume_aligned(&sgamma[it * 256 + goff], 16));
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const float xh = (xv[it][i] - mean) * rstd;
+                    const float gd = gm[i] * dv[it][i];
+                    s1 += gd; s2 += gd * xh;
+                    ag[it][i] += dv[it][i] * xh;
+                    ab[it][i] += dv[it][i];
+                }
+            }
+        }
+        const float c1 = wave_sum(s1) / (float)N, c2 = wave_sum(s2) / (float)N;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int col = (it * 64 + lane) * VEC;
+            if (col < N) {
+                float o[VEC], gm[VEC];
+                *reinterpret_cast<float4*>(&gm[0]) = *reinterpret_cast<const float4*>(__builtin_assume_aligned(&sgamma[it * 256 + goff], 16));
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    o[i] = rstd * (gm[i] * dv[it][i] - c1 - (xv[it][i] - mean) * rstd * c2);
+                stvec(dx + (size_t)row * N + col, o);
+                if (drop) {                        // gradient through the dropout of the dense layer feeding this LN
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i)
+                        o[i] *= dropout_scale(seed, (uint32_t)row, (uint32_t)(col + i), p_drop, inv_keep);
+                }
+                st4bf(dx_drop + (size_t)row * N + col, o);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) ax[it][i] += o[i];
+            }
+        }
+    }
+    float* slot = ws ? ws + (size_t)blockIdx.x * 3 * N : nullptr;
+    flush_colsums3<NIT, VEC, W>(ag, ab, ax, dbias_prev != nullptr, dgamma, dbeta, dbias_prev, N, red, slot);
+}
+
 // The same kernel with the NEXT row of a wave requested by LDS-DMA (buffer_load ... lds: global -> LDS without passing through
 // registers) while the current row is processed: per row the plain kernel is a dependent chain -- two row loads, two wave
 // reductions, two passes, the stores -- with ONE row's loads in flight per wave, and at four waves per SIMD the launch sits at
@@ -1710,6 +1824,56 @@ extern "C" int xl_layernorm_bwd(const void* dy, const void* x, const float* gamm
                                (const T*)dy, (const T*)x, gamma, mean, rstd, (T*)dx, dgamma, dbeta, dbias_prev, M, N, workspace,
                                (T*)dx_dropped, p_drop, 1.0f / (1.0f - p_drop), seed, xl::ctx().step_seed);));
     }
+    XL_CHECK_LAUNCH();
+    if (workspace) {
+        ReduceOuts o = {};
+        o.p[0] = dgamma; o.p[1] = dbeta; o.p[2] = dbias_prev;
+        launch_reduce(workspace, grid, 3, N, o, st);
+        XL_CHECK_LAUNCH();
+    }
+    return XL_OK;
+}
+
+// rows of the fp32 stream: 64 lanes x 4 floats per pass; N = 768 takes exactly three
+#define DISPATCH_NIT_RES(N, ...)                                                    \
+    {                                                                               \
+        const int nit__ = ((N) + 255) / 256;                                        \
+        if (nit__ <= 1) { constexpr int NIT = 1; __VA_ARGS__ }                      \
+        else if (nit__ <= 2) { constexpr int NIT = 2; __VA_ARGS__ }                 \
+        else if (nit__ <= 3) { constexpr int NIT = 3; __VA_ARGS__ }                 \
+        else if (nit__ <= 4) { constexpr int NIT = 4; __VA_ARGS__ }                 \
+        else if (nit__ <= 8) { constexpr int NIT = 8; __VA_ARGS__ }                 \
+        else { xl::set_error("row length %d too large", (int)(N)); return XL_ERR_BAD_SHAPE; } \
+    }
+
+extern "C" int xl_layernorm_fwd_res(const float* x, const float* gamma, const float* beta, float* y32, void* y16,
+                                    float* mean, float* rstd, int M, int N, float eps, void* stream) {
+    CHECK_ROW(N, XL_F32);
+    XL_CHECK_ARG(M > 0 && x && y32 && y16 && gamma && beta && mean && rstd, XL_ERR_BAD_ARG, "xl_layernorm_fwd_res: bad args");
+    XL_CHECK_ARG(aligned16(x) && aligned16(y32) && ((uintptr_t)y16 & 7) == 0, XL_ERR_UNALIGNED, "xl_layernorm_fwd_res: unaligned rows");
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_NIT_RES(N,
+        hipLaunchKernelGGL((ln_fwd_res_kernel<NIT>), dim3((M + WPB - 1) / WPB), dim3(256), 0, st,
+                           x, gamma, beta, y32, (bf16_t*)y16, mean, rstd, M, N, eps););
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
+extern "C" int xl_layernorm_bwd_res(const float* dy, const float* x, const float* gamma, const float* mean,
+                                    const float* rstd, float* dx, float* dgamma, float* dbeta, float* dbias_prev,
+                                    int M, int N, float* workspace, void* dx_dropped, float p_drop, uint64_t seed, void* stream) {
+    CHECK_ROW(N, XL_F32);
+    XL_CHECK_ARG(M > 0 && dy && x && gamma && mean && rstd && dx && dgamma && dbeta && dx_dropped, XL_ERR_BAD_ARG,
+                 "xl_layernorm_bwd_res: bad args (dx_dropped is always written)");
+    XL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, XL_ERR_BAD_ARG, "xl_layernorm_bwd_res: p_drop %f", p_drop);
+    XL_CHECK_ARG(aligned16(dy) && aligned16(x) && aligned16(dx) && ((uintptr_t)dx_dropped & 7) == 0, XL_ERR_UNALIGNED,
+                 "xl_layernorm_bwd_res: unaligned rows");
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = min((M + LNB_W - 1) / LNB_W, 512);        // as xl_layernorm_bwd: the same partial slabs, the same second stage
+    DISPATCH_NIT_RES(N,
+        hipLaunchKernelGGL((ln_bwd_res_kernel<NIT, LNB_W>), dim3(grid), dim3(LNB_W * 64), 0, st,
+                           dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dbias_prev, M, N, workspace,
+                           (bf16_t*)dx_dropped, p_drop, 1.0f / (1.0f - p_drop), seed, xl::ctx().step_seed););
     XL_CHECK_LAUNCH();
     if (workspace) {
         ReduceOuts o = {};

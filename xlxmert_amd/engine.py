@@ -22,6 +22,28 @@ import torch
 from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_ROWMAX, EPI_TANH, GemmCall
 
 
+class _Res:
+    """A residual-stream value of the fp32-stream mode (Engine residual_dtype="fp32"): `f` the fp32 value that travels along
+    the residual path, `h` its bf16 rounding, which the contractions read as their operand.  Row slices keep the pair."""
+    __slots__ = ("f", "h")
+
+    def __init__(self, f, h):
+        self.f, self.h = f, h
+
+    def __getitem__(self, s):
+        return _Res(self.f[s], self.h[s])
+
+
+def _h(x):
+    """what a contraction reads of a stream value (the tensor itself in the bf16-stream mode)"""
+    return x.h if isinstance(x, _Res) else x
+
+
+def _f(x):
+    """what the residual path reads of a stream value"""
+    return x.f if isinstance(x, _Res) else x
+
+
 class _Att:
     """LxmertAttention + LxmertAttentionOutput parameters (fused q/k/v views)."""
 
@@ -86,7 +108,7 @@ class SelfAttBlock:
         d = eng.d
         self.qkv = eng.act(Mc, 3 * d)
         self.ctx = eng.act(Mc, d)
-        self.z = eng.act(Mc, d)
+        self.z = eng.zact(Mc, d)
         self.lse = eng.f32(eng.B * eng.H * n_tok)
         self.keep = eng.keep_bits(n_tok, n_tok)
         self.mean, self.rstd = eng.f32(Mc), eng.f32(Mc)
@@ -115,15 +137,15 @@ class SelfAttBlock:
         e, p, d, M = self.e, self.p, self.e.d, self.M
         ops, tag = e.ops, self.tag
         qkv, ctx, z = self.qkv[:M], self.ctx[:M], self.z[:M]
-        yield GemmCall(x, p.wqkv, qkv, p.bqkv, None, None, M, 3 * d, d, d, d, 3 * d, tag=tag)
+        yield GemmCall(_h(x), p.wqkv, qkv, p.bqkv, None, None, M, 3 * d, d, d, d, 3 * d, tag=tag)
         km, vl = self._att_args()
         ops.block = tag
         ops.sdpa_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], km, ctx, self.lse, e.B, e.H, self.n, self.n,
                      e.dh, 3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site), keep_bits=e.kb(self.keep), **vl)
-        yield GemmCall(ctx, p.wo, z, p.bo, x, None, M, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
-                       p_drop=e.p_hid, seed=e.seed(self.site + 1), tag=tag)
+        yield GemmCall(ctx, p.wo, z, p.bo, _f(x), None, M, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
+                       p_drop=e.p_hid, seed=e.seed(self.site + 1), tag=tag, **e.rkw)
         ops.block = tag
-        ops.layernorm_fwd(z, p.g, p.b, y, self.mean, self.rstd, M, d, e.eps)
+        e.ln_fwd(z, p.g, p.b, y, self.mean, self.rstd, M, d)
         self.x = x
 
     def probs(self):
@@ -146,7 +168,7 @@ class SelfAttBlock:
         ops.block = tag
         e.wgrad_sync()                  # the previous block's weight-gradient GEMMs still read the shared scratch
         qkv, ctx, z = self.qkv[:M], self.ctx[:M], self.z[:M]
-        dz = e.tmp("dz", M, d)
+        dz = e.tmp("dz", M, d, res=True)
         dzm = e.ln_bwd_dense(dy, z, p.g, self.mean, self.rstd, dz, p.gg, p.gb, p.gbo, M, d, self.site + 1)
         e.wgrad_defer(dzm, ctx, p.gwo, d, d, M, d, d, d)
         dctx = e.tmp("dctx", M, d)
@@ -157,10 +179,10 @@ class SelfAttBlock:
         ops.sdpa_bwd(qkv, qkv[:, d:], qkv[:, 2 * d:], km, dctx, self.lse, dqkv, dqkv[:, d:],
                      dqkv[:, 2 * d:], e.B, e.H, self.n, self.n, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d,
                      e.scale, e.p_attn, e.seed(self.site), bias_grad=p.gbqkv, ws=e.ws, keep_bits=e.kb(self.keep), **vl)      # + d(b_q | b_k | b_v)
-        e.wgrad_defer(dqkv, self.x, p.gwqkv, 3 * d, d, M, 3 * d, d, d)
+        e.wgrad_defer(dqkv, _h(self.x), p.gwqkv, 3 * d, d, M, 3 * d, d, d)
         e.wgrad_flush(pair=True)        # this layer's four weight gradients: launched together with the next layer's
         yield GemmCall(dqkv, p.wqkv, dx, None, dz, None, M, d, 3 * d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                       epilogue=EPI_RESIDUAL, tag=tag)
+                       epilogue=EPI_RESIDUAL, tag=tag, **e.rkw)
 
 
 class FFNBlock:
@@ -180,7 +202,7 @@ class FFNBlock:
         Mc = eng.MLc if lang else eng.MV
         self.pre = eng.act(Mc, dff)
         self.h = eng.act(Mc, dff)
-        self.z = eng.act(Mc, d)
+        self.z = eng.zact(Mc, d)
         self.mean, self.rstd = eng.f32(Mc), eng.f32(Mc)
         self.site = eng.new_site(1)
         self.rows = None                # row count of a forward on a row SUBSET (Engine: the last cross layer's visual side
@@ -202,11 +224,11 @@ class FFNBlock:
         pre, h, z = self.pre[:M], self.h[:M], self.z[:M]
         # self.pre holds gelu'(pre-activation): erf and exp(-x^2/2) are in registers in the forward epilogue anyway, and the
         # backward epilogue becomes a multiply (no second erf + exp per element of the [M, dff] gradient)
-        yield GemmCall(x, self.w1, h, self.b1, None, pre, M, dff, d, d, d, dff, ldx=dff, epilogue=EPI_GELU_DG, tag=tag)
-        yield GemmCall(h, self.w2, z, self.b2, x, None, M, d, dff, dff, dff, d, ldr=d, epilogue=EPI_RESIDUAL,
-                       p_drop=e.p_hid, seed=e.seed(self.site), tag=tag)
+        yield GemmCall(_h(x), self.w1, h, self.b1, None, pre, M, dff, d, d, d, dff, ldx=dff, epilogue=EPI_GELU_DG, tag=tag)
+        yield GemmCall(h, self.w2, z, self.b2, _f(x), None, M, d, dff, dff, dff, d, ldr=d, epilogue=EPI_RESIDUAL,
+                       p_drop=e.p_hid, seed=e.seed(self.site), tag=tag, **e.rkw)
         ops.block = tag
-        ops.layernorm_fwd(z, self.g, self.b, y, self.mean, self.rstd, M, d, e.eps)
+        e.ln_fwd(z, self.g, self.b, y, self.mean, self.rstd, M, d)
         self.x = x
 
     def bwd(self, dy, dx):
@@ -220,16 +242,16 @@ class FFNBlock:
         pre, h, z = self.pre[:M], self.h[:M], self.z[:M]
         # own scratch names: the two weight gradients registered here are launched together with the attention block's
         # (which runs next on this stream and flushes), so dz / dzm / dpre must outlive that block's scratch use
-        dz = e.tmp("f_dz", M, d)
+        dz = e.tmp("f_dz", M, d, res=True)
         dzm = e.ln_bwd_dense(dy, z, self.g, self.mean, self.rstd, dz, self.gg, self.gb, self.gb2, M, d, self.site,
                              tmp_name="f_dzm")
         e.wgrad_defer(dzm, h, self.gw2, d, dff, M, d, dff, dff)
         dpre = e.tmp("dpre", M, dff)
         yield GemmCall(dzm, self.w2, dpre, None, None, pre, M, dff, d, d, dff, dff, ldx=dff, a_kmajor=1, b_kmajor=0,
                        epilogue=EPI_MULAUX, colsum=self.gb1, ws=e.ws_gemm, tag=tag)      # d(b1) = column sums of dpre, in the same epilogue
-        e.wgrad_defer(dpre, self.x, self.gw1, dff, d, M, dff, d, d)
+        e.wgrad_defer(dpre, _h(self.x), self.gw1, dff, d, M, dff, d, d)
         yield GemmCall(dpre, self.w1, dx, None, dz, None, M, d, dff, dff, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                       epilogue=EPI_RESIDUAL, tag=tag)
+                       epilogue=EPI_RESIDUAL, tag=tag, **e.rkw)
 
 
 class CrossAttBlock:
@@ -248,7 +270,7 @@ class CrossAttBlock:
         d = eng.d
         self.qkv = eng.act(eng.MXc, 3 * d)
         self.ctx = eng.act(eng.MXc, d)
-        self.z = eng.act(eng.MXc, d)
+        self.z = eng.zact(eng.MXc, d)
         self.lse_l = eng.f32(eng.B * eng.H * eng.L)
         self.lse_v = eng.f32(eng.B * eng.H * eng.V)
         self.keep_l, self.keep_v = eng.keep_bits(eng.L, eng.V), eng.keep_bits(eng.V, eng.L)
@@ -271,32 +293,33 @@ class CrossAttBlock:
         ops.block = self.tag
         L_, V_ = e.lr, e.vr
         qkv_l, qkv_v = L_(self.qkv), V_(self.qkv)
+        Xh, Xf = _h(X), _f(X)           # (fp32 stream: the contractions read the bf16 copy, the residual epilogue the fp32 value)
         if not self.need_vis:
-            ops.gemm(L_(X), p.wqkv, qkv_l, p.bqkv, None, None, ML, d, d, d, d, 3 * d)                    # Q of language rows
-            ops.gemm(V_(X), p.wqkv[d:], qkv_v[:, d:], p.bqkv[d:], None, None, MV, 2 * d, d, d, d, 3 * d)  # K,V of visual rows
+            ops.gemm(L_(Xh), p.wqkv, qkv_l, p.bqkv, None, None, ML, d, d, d, d, 3 * d)                    # Q of language rows
+            ops.gemm(V_(Xh), p.wqkv[d:], qkv_v[:, d:], p.bqkv[d:], None, None, MV, 2 * d, d, d, d, 3 * d)  # K,V of visual rows
             ops.sdpa_fwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, L_(self.ctx), self.lse_l, e.B, e.H, e.L, e.V, e.dh,
                          3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site), keep_bits=e.kb(self.keep_l), **self._lq())
-            ops.gemm(L_(self.ctx), p.wo, L_(self.z), p.bo, L_(X), None, ML, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
-                     p_drop=e.p_hid, seed=e.seed(self.site + 2))
-            ops.layernorm_fwd(L_(self.z), p.g, p.b, L_(Y), L_(self.mean), L_(self.rstd), ML, d, e.eps)
+            ops.gemm(L_(self.ctx), p.wo, L_(self.z), p.bo, L_(Xf), None, ML, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
+                     p_drop=e.p_hid, seed=e.seed(self.site + 2), **e.rkw)
+            e.ln_fwd(L_(self.z), p.g, p.b, L_(Y), L_(self.mean), L_(self.rstd), ML, d)
             self.X = X
             return
         if self.need_lang:
-            ops.gemm(X[:MX], p.wqkv, self.qkv[:MX], p.bqkv, None, None, MX, 3 * d, d, d, d, 3 * d)
+            ops.gemm(Xh[:MX], p.wqkv, self.qkv[:MX], p.bqkv, None, None, MX, 3 * d, d, d, d, 3 * d)
             # language queries over visual keys/values (no mask: visual_attention_mask is None in every caller)
             ops.sdpa_fwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, L_(self.ctx), self.lse_l, e.B, e.H, e.L, e.V, e.dh,
                          3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site), keep_bits=e.kb(self.keep_l), **self._lq())
         else:
-            ops.gemm(V_(X), p.wqkv, qkv_v, p.bqkv, None, None, MV, d, d, d, d, 3 * d)                    # Q of visual rows
-            ops.gemm(L_(X), p.wqkv[d:], qkv_l[:, d:], p.bqkv[d:], None, None, ML, 2 * d, d, d, d, 3 * d)  # K,V of language rows
+            ops.gemm(V_(Xh), p.wqkv, qkv_v, p.bqkv, None, None, MV, d, d, d, d, 3 * d)                    # Q of visual rows
+            ops.gemm(L_(Xh), p.wqkv[d:], qkv_l[:, d:], p.bqkv[d:], None, None, ML, 2 * d, d, d, d, 3 * d)  # K,V of language rows
         # visual queries over language keys/values, padded language keys excluded
         km, vl = self._lk()
         ops.sdpa_fwd(qkv_v, qkv_l[:, d:], qkv_l[:, 2 * d:], km, V_(self.ctx), self.lse_v, e.B, e.H, e.V, e.L, e.dh,
                      3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site + 1), keep_bits=e.kb(self.keep_v), **vl)
         M = MX if self.need_lang else MV           # rows [0, M): visual rows, then (both directions) the language rows
-        ops.gemm(self.ctx[:M], p.wo, self.z[:M], p.bo, X[:M], None, M, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
-                 p_drop=e.p_hid, seed=e.seed(self.site + 2))
-        ops.layernorm_fwd(self.z[:M], p.g, p.b, Y[:M], self.mean[:M], self.rstd[:M], M, d, e.eps)
+        ops.gemm(self.ctx[:M], p.wo, self.z[:M], p.bo, Xf[:M], None, M, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
+                 p_drop=e.p_hid, seed=e.seed(self.site + 2), **e.rkw)
+        e.ln_fwd(self.z[:M], p.g, p.b, Y[:M], self.mean[:M], self.rstd[:M], M, d)
         self.X = X
 
     def probs(self):
@@ -320,7 +343,7 @@ class CrossAttBlock:
             return self._bwd_lang_only(dY, dX)
         L_, V_ = e.lr, e.vr
         M = MX if self.need_lang else MV
-        dz_full = e.tmp("dz", MX, d)
+        dz_full = e.tmp("dz", MX, d, res=True)
         dz = dz_full[:M]
         dzm = e.ln_bwd_dense(dY[:M], self.z[:M], p.g, self.mean[:M], self.rstd[:M], dz, p.gg, p.gb, p.gbo, M, d,
                              self.site + 2)
@@ -335,7 +358,7 @@ class CrossAttBlock:
         ops.sdpa_bwd(qkv_v, qkv_l[:, d:], qkv_l[:, 2 * d:], km, V_(dctx_full), self.lse_v, dqkv_v, dqkv_l[:, d:],
                      dqkv_l[:, 2 * d:], e.B, e.H, e.V, e.L, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d, e.scale,
                      e.p_attn, e.seed(self.site + 1), bias_grad=p.gbqkv, ws=e.ws, keep_bits=e.kb(self.keep_v), **vl)
-        X = self.X
+        X = _h(self.X)
         if self.need_lang:
             ops.sdpa_bwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, L_(dctx_full), self.lse_l, dqkv_l, dqkv_v[:, d:],
                          dqkv_v[:, 2 * d:], e.B, e.H, e.L, e.V, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d, e.scale,
@@ -343,21 +366,21 @@ class CrossAttBlock:
             e.wgrad_defer(dqkv, X[:MX], p.gwqkv, 3 * d, d, MX, 3 * d, d, d)
             e.wgrad_flush()
             ops.gemm(dqkv, p.wqkv, dX[:MX], None, dz_full, None, MX, d, 3 * d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                     epilogue=EPI_RESIDUAL)
+                     epilogue=EPI_RESIDUAL, **e.rkw)
         else:
             e.wgrad_defer(dqkv_v, V_(X), p.gwqkv, d, d, MV, 3 * d, d, d)
             e.wgrad_defer(dqkv_l[:, d:], L_(X), p.gwqkv[d:], 2 * d, d, ML, 3 * d, d, d)
             e.wgrad_flush()
             ops.gemm(dqkv_v, p.wqkv, V_(dX), None, dz, None, MV, d, d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                     epilogue=EPI_RESIDUAL)
-            ops.gemm(dqkv_l[:, d:], p.wqkv[d:], L_(dX), None, None, None, ML, d, 2 * d, 3 * d, d, d, a_kmajor=1, b_kmajor=0)
+                     epilogue=EPI_RESIDUAL, **e.rkw)
+            e.gemm_dx_plain(dqkv_l[:, d:], p.wqkv[d:], L_(dX), ML, d, 2 * d, 3 * d, d)
 
     def _bwd_lang_only(self, dY, dX):
         e, p, d = self.e, self.p, self.e.d
         ops, ML, MV, MX = e.ops, e.ML, e.MV, e.MX
         L_, V_ = e.lr, e.vr
-        X = self.X
-        dz = L_(e.tmp("dz", MX, d))
+        X = _h(self.X)
+        dz = L_(e.tmp("dz", MX, d, res=True))
         dzm = e.ln_bwd_dense(L_(dY), L_(self.z), p.g, L_(self.mean), L_(self.rstd), dz, p.gg, p.gb, p.gbo, ML, d, self.site + 2)
         e.wgrad_defer(dzm, L_(self.ctx), p.gwo, d, d, ML, d, d, d)
         dctx = L_(e.tmp("dctx", MX, d))
@@ -371,8 +394,9 @@ class CrossAttBlock:
         e.wgrad_defer(dqkv_l, L_(X), p.gwqkv, d, d, ML, 3 * d, d, d)
         e.wgrad_defer(dqkv_v[:, d:], V_(X), p.gwqkv[d:], 2 * d, d, MV, 3 * d, d, d)
         e.wgrad_flush()
-        ops.gemm(dqkv_l, p.wqkv, L_(dX), None, dz, None, ML, d, d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL)
-        ops.gemm(dqkv_v[:, d:], p.wqkv[d:], V_(dX), None, None, None, MV, d, 2 * d, 3 * d, d, d, a_kmajor=1, b_kmajor=0)
+        ops.gemm(dqkv_l, p.wqkv, L_(dX), None, dz, None, ML, d, d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL,
+                 **e.rkw)
+        e.gemm_dx_plain(dqkv_v[:, d:], p.wqkv[d:], V_(dX), MV, d, 2 * d, 3 * d, d)
 
 
 class AnswerHead:
@@ -569,11 +593,11 @@ class LangHeads:
         e.wgrad_defer(dpre, self.x, self.gwt, d, d, M, d, d, d)
         e.wgrad_flush()
         if self.n_rows:
-            dx = e.tmp("mlm_dx", e.MLd, d)[:M]
-            ops.gemm(dpre, self.wt, dx, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0)
+            dx = e.tmp("mlm_dx", e.MLd, d, res=True)[:M]      # (fp32 stream: the heads' gradients enter it in fp32)
+            ops.gemm(dpre, self.wt, dx, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **e.rkw)
             ops.scatter_rows(dx, self.rows, d_lang, M, d, d, d)
         else:
-            ops.gemm(dpre, self.wt, d_lang, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0)
+            ops.gemm(dpre, self.wt, d_lang, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **e.rkw)
         return self.loss
 
     # ---- matched
@@ -622,8 +646,18 @@ class Engine:
     """Static-shape forward/backward program.  `need_lang`: whether lang/pooled outputs of the last cross layer are
     consumed (False for the masked-visual-token step)."""
 
-    def __init__(self, cfg, store, ops, B, L, V, need_lang=False, train_dropout=False, two_streams=True, pack_lang=None):
-        """pack_lang: run the language side on the REAL tokens only.  The attention mask (input_ids > 0, ref lxmert_pretrain.py:206)
+    def __init__(self, cfg, store, ops, B, L, V, need_lang=False, train_dropout=False, two_streams=True, pack_lang=None,
+                 residual_dtype=None):
+        """residual_dtype: "bf16" (default) or "fp32"; None reads env XL_RESIDUAL.  Meaningful with a bf16 compute dtype (with fp32
+        compute the stream is fp32 already: accepted, changes nothing).  "fp32" is the blueprint's precision mode (SURVEY.md
+        section 7: bf16 operands, fp32 accumulate, fp32 LN / softmax / RESIDUAL STREAM): every residual-stream value -- the
+        embeddings' LayerNorm output, the visual feature encoder's output, and in every attention-output / FFN-output sub-block the
+        pre-LayerNorm sum and the LayerNorm output -- and its gradient is kept in fp32; every LayerNorm output also exists as
+        its bf16 rounding, which the contractions read.  Everything else (q/k/v, attention context, GELU output, the gradient
+        entering a dense layer) stays bf16.  hidden_states() returns the fp32 values.  Not supported in this mode (ValueError):
+        XL_PAIR_BLOCKS=1.  The experimental kernel switches (HipOps.set_gemm_relay / _q / _persistent / _tile192 / _split_epi /
+        _pair) are accepted: the library runs the fp32 residual epilogue on the default kernels whatever they say.
+        pack_lang: run the language side on the REAL tokens only.  The attention mask (input_ids > 0, ref lxmert_pretrain.py:206)
         removes the [PAD] positions as keys everywhere (HF:238-266) and no loss or head reads a [PAD] position's output, so every
         row the reference computes for them -- a third of the B x 20 language rows at sentence lengths U{6..20} -- is dead work:
         after the embeddings the language rows are gathered into a packed [sum of lengths, d] matrix (row list + per-example
@@ -638,6 +672,13 @@ class Engine:
         assert L <= 512 and V <= 64, "text length <= 512 (position table), visual grid <= 64 tokens (samplers / on-chip attention)"
         self.cfg, self.store, self.ops = cfg, store, ops
         self.dev, self.cdtype = store.device, store.compute_dtype
+        if residual_dtype is None:
+            residual_dtype = os.environ.get("XL_RESIDUAL", "bf16")
+        if residual_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"residual_dtype / XL_RESIDUAL must be 'bf16' or 'fp32', got {residual_dtype!r}")
+        self.residual_dtype = residual_dtype
+        self.res32 = residual_dtype == "fp32" and self.cdtype == torch.bfloat16      # fp32 stream beside bf16 operands
+        self.rkw = {"out_f32": True} if self.res32 else {}       # keywords of a contraction that writes a stream value / gradient
         self.B, self.L, self.V = B, L, V
         self.d, self.dff, self.F, self.K = cfg.hidden_size, cfg.intermediate_size, cfg.visual_feat_dim, cfg.num_clusters
         self.H, self.dh = cfg.num_attention_heads, cfg.head_dim
@@ -654,6 +695,8 @@ class Engine:
         # better than the language stream of rounds 1-4 beside the visual chain.  Default: off.
         self.pair_blocks = os.environ.get("XL_PAIR_BLOCKS", "0") != "0"
         self.pair_side = os.environ.get("XL_PAIR_SIDE", "0") != "0"       # ... the language block's own kernels on the language stream
+        if self.res32 and self.pair_blocks:
+            raise ValueError("XL_PAIR_BLOCKS=1 is not supported with residual_dtype='fp32' (paired launches have no fp32 residual epilogue)")
         self.packed = False                 # this batch runs packed (set_inputs: pack_lang and a usable attention mask)
         self.MLd, self.MV = B * L, B * V    # dense language rows / visual rows
         # language row CAPACITY of every buffer (a packed row count is rounded up to the row tile) and the ACTIVE count
@@ -707,24 +750,26 @@ class Engine:
                 blk["ffn_l"] = FFNBlock(self, p + ".lang_inter", p + ".lang_output", True, f"x{i}l")
             self.x_layers.append(blk)
         # ---- activations of the chain
-        self.emb_y, self.emb_pre = self.act(self.MLd, d), self.act(self.MLd, d)        # embeddings: dense [B*L] rows
+        self.emb_y, self.emb_pre = self.sact(self.MLd, d), self.act(self.MLd, d)       # embeddings: dense [B*L] rows
+        self.emb_pre32 = self.f32act(self.MLd, d) if self.res32 else None              # (fp32 stream: the pre-LayerNorm sum as the LayerNorm reads it)
         self.emb_mean, self.emb_rstd = self.f32(self.MLd), self.f32(self.MLd)
-        self.emb_p = self.act(self.MLc, d) if self.pack_lang else None                 # ... gathered to the packed rows
+        self.emb_p = self.sact(self.MLc, d) if self.pack_lang else None                # ... gathered to the packed rows
         self.lrows = torch.full((self.MLc,), -1, dtype=torch.int32, device=self.dev)   # b*L+l of packed row r (-1: pad tail)
         self.loff = torch.zeros(B + 1, dtype=torch.int32, device=self.dev)             # first packed row of example b
         self.lang_pad = self.act(self.MLd, d) if self.pack_lang else None              # final language output, dense layout
-        self.glang_pad = self.act(self.MLd, d) if self.pack_lang else None             # its gradient, dense layout
+        self.glang_pad = self.gact(self.MLd, d) if self.pack_lang else None            # its gradient, dense layout
         self.feats = self.act(self.MV, self.F)
         self.xv = self.act(self.MV, d)
-        self.vis0 = self.act(self.MV, d)
+        self.xv32 = self.f32act(self.MV, d) if self.res32 else None      # (fp32 stream: what the feature encoder's LayerNorm reads)
+        self.vis0 = self.sact(self.MV, d)
         self.vn_stats = [self.f32(self.MV) for _ in range(4)]
-        self.lang_mid = [self.act(self.MLc, d) for _ in range(cfg.l_layers)]          # attention-block outputs
-        self.lang_out = [self.act(self.MLc, d) for _ in range(cfg.l_layers - 1)]
-        self.vis_mid = [self.act(self.MV, d) for _ in range(cfg.r_layers)]
-        self.vis_out = [self.act(self.MV, d) for _ in range(cfg.r_layers - 1)]
-        self.X = [self.act(self.MXc, d) for _ in range(cfg.x_layers + 1)]            # [vis ; lang] per cross layer
-        self.XY = [self.act(self.MXc, d) for _ in range(cfg.x_layers)]               # cross-attention outputs
-        self.XS = [self.act(self.MXc, d) for _ in range(cfg.x_layers)]               # self-attention outputs
+        self.lang_mid = [self.sact(self.MLc, d) for _ in range(cfg.l_layers)]         # attention-block outputs
+        self.lang_out = [self.sact(self.MLc, d) for _ in range(cfg.l_layers - 1)]
+        self.vis_mid = [self.sact(self.MV, d) for _ in range(cfg.r_layers)]
+        self.vis_out = [self.sact(self.MV, d) for _ in range(cfg.r_layers - 1)]
+        self.X = [self.sact(self.MXc, d) for _ in range(cfg.x_layers + 1)]           # [vis ; lang] per cross layer
+        self.XY = [self.sact(self.MXc, d) for _ in range(cfg.x_layers)]              # cross-attention outputs
+        self.XS = [self.sact(self.MXc, d) for _ in range(cfg.x_layers)]              # self-attention outputs
         self.pooled = self.act(B, d)
         self.kmask = torch.ones(B, L, dtype=torch.uint8, device=self.dev)
         self.vkmask, self._vkmask_buf = None, None        # visual_attention_mask (HF:760-770): None in every reference caller
@@ -775,7 +820,7 @@ class Engine:
         self.mf_tmp = self.f32(d)
         self.mf_tmp_c = self.act(1, d)
         # ---- activation-gradient ping-pong
-        self.GA, self.GB = self.act(self.MXc, d), self.act(self.MXc, d)
+        self.GA, self.GB = self.gact(self.MXc, d), self.gact(self.MXc, d)
         # two-stage column reductions: one workspace per stream (language / visual work runs concurrently)
         # (the second stages are deferred and combined per layer -- flush_reductions -- so every producer between two flushes
         # gets a workspace region of its own: _WS_REGIONS per stream)
@@ -829,6 +874,60 @@ class Engine:
 
     def f32(self, *shape):
         return torch.zeros(*shape, dtype=torch.float32, device=self.dev)
+
+    def f32act(self, *shape):
+        """an fp32 activation of the fp32-stream mode (counted in act_bytes)"""
+        t = self.f32(*shape)
+        self.act_bytes += t.numel() * 4
+        return t
+
+    def sact(self, *shape):
+        """a residual-stream value: a compute-dtype tensor, or -- fp32 stream -- the pair (fp32 value, its bf16 rounding)"""
+        return _Res(self.f32act(*shape), self.act(*shape)) if self.res32 else self.act(*shape)
+
+    def zact(self, *shape):
+        """a pre-LayerNorm sum (read by the LayerNorm forward / backward only: no bf16 copy in the fp32-stream mode)"""
+        return self.f32act(*shape) if self.res32 else self.act(*shape)
+
+    def gact(self, *shape):
+        """a gradient buffer of the residual path"""
+        return self.f32act(*shape) if self.res32 else self.act(*shape)
+
+    def ln_fwd(self, z, g, b, y, mean, rstd, M, N):
+        """LayerNorm of a pre-LayerNorm sum into the stream value y (fp32 stream: fp32 y and its bf16 rounding from one kernel)"""
+        if self.res32:
+            self.ops.layernorm_fwd_res(z, g, b, y.f, y.h, mean, rstd, M, N, self.eps)
+        else:
+            self.ops.layernorm_fwd(z, g, b, y, mean, rstd, M, N, self.eps)
+
+    def dropout_stream(self, y, M, seed):
+        """in-place dropout of a whole stream buffer (embeddings, feature encoder output); fp32 stream: on the fp32 value, then
+        the bf16 copy is its rounding"""
+        d = self.d
+        if self.res32:
+            self.ops.dropout(y.f, y.f, M, d, d, d, self.p_hid, seed)
+            self.ops.cast_from_f32(y.f, y.h, M * d)
+        else:
+            self.ops.dropout(y, y, M, d, d, d, self.p_hid, seed)
+
+    def gather_stream(self, src, rows, dst, n):
+        """rows of a stream value (both copies in the fp32-stream mode)"""
+        d = self.d
+        if self.res32:
+            self.ops.gather_rows(src.f, rows, dst.f, n, d, d, d)
+        self.ops.gather_rows(_h(src), rows, _h(dst), n, d, d, d)
+
+    def gemm_dx_plain(self, dY, W, dX, M, N, K, lda, ldb):
+        """dX = dY W into a gradient buffer of the residual path, no residual term (the key / value side of a cross-attention
+        whose other direction is skipped).  fp32 stream: an fp32-output contraction without an epilogue would be K-split through
+        fp32 atomics (the weight-gradient rule of xl_gemm), whose summation order varies from run to run -- so the buffer is
+        cleared and the in-place residual epilogue adds into it: one writer per element, the same bits every run."""
+        if self.res32:
+            self.ops.zero(dX)
+            self.ops.gemm(dY, W, dX, None, dX, None, M, N, K, lda, ldb, N, ldr=N, a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL,
+                          out_f32=True)
+        else:
+            self.ops.gemm(dY, W, dX, None, None, None, M, N, K, lda, ldb, N, a_kmajor=1, b_kmajor=0)
 
     def keep_bits(self, nq, nk):
         """buffer in which an attention core's forward leaves its dropout decisions for its backward (xl_sdpa_fwd / _bwd keep_bits:
@@ -1200,12 +1299,13 @@ class Engine:
             self._dw_busy[tag] = False
         self._gen_guard[tag].clear()
 
-    def tmp(self, name, M, N):
+    def tmp(self, name, M, N, res=False):
         """backward scratch, shared by all blocks of one stream (sized for the largest user); NGEN sets per stream, one per scratch
-        generation (wgrad_flush)."""
-        key = (name, N, self._tag, self._gen[self._tag])
+        generation (wgrad_flush).  res: a gradient of the residual path (fp32 in the fp32-stream mode)."""
+        dt = torch.float32 if (res and self.res32) else self.cdtype
+        key = (name, N, self._tag, self._gen[self._tag]) + ((dt,) if self.res32 else ())      # (a name serves both types in that mode)
         if key not in self._tmp:
-            self._tmp[key] = torch.zeros(self.MXc, N, dtype=self.cdtype, device=self.dev)
+            self._tmp[key] = torch.zeros(self.MXc, N, dtype=dt, device=self.dev)
         return self._tmp[key][:M]
 
     ROW_PAD = 256
@@ -1254,6 +1354,11 @@ class Engine:
     def ln_bwd_dense(self, dy, z, g, mean, rstd, dz, gg, gb, gbias, M, N, site, tmp_name="dzm"):
         """LayerNorm backward of a `LN(dropout(dense(.)) + residual)` block: returns the gradient entering the dense layer
         (dz itself when dropout is off, else the masked copy written by the same kernel); the dense bias gradient is fused."""
+        if self.res32:              # fp32 dy / z / dz; the bf16 gradient entering the dense layer is written on every launch
+            dzm = self.tmp(tmp_name, M, N)
+            self.ops.layernorm_bwd_res(dy, z, g, mean, rstd, dz, gg, gb, gbias, M, N, ws=self.ws, dx_dropped=dzm,
+                                       p_drop=self.p_hid, seed=self.seed(site))
+            return dzm
         if self.p_hid == 0:
             self.ops.layernorm_bwd(dy, z, g, mean, rstd, dz, gg, gb, gbias, M, N, ws=self.ws)
             return dz
@@ -1417,11 +1522,12 @@ class Engine:
         cfg, ML = self.cfg, self.ML
         lang = [self.lang_out[i][:ML] if i < cfg.l_layers - 1 else self.lr(self.X[0]) for i in range(cfg.l_layers)]
         vis = [self.vis_out[i] if i < cfg.r_layers - 1 else self.vr(self.X[0]) for i in range(cfg.r_layers)]
+        lang, vis = [_f(t) for t in lang], [_f(t) for t in vis]           # (fp32 stream: the fp32 values)
         for i, blk in enumerate(self.x_layers):
             if blk["lang_on"]:
-                lang.append(self.lr(self.X[i + 1]))
+                lang.append(_f(self.lr(self.X[i + 1])))
             if blk["vis_on"]:
-                vis.append(self.vr(self.X[i + 1]))
+                vis.append(_f(self.vr(self.X[i + 1])))
         if self.packed:                 # packed language rows -> the dense [B*L, d] layout, zero rows at the [PAD] positions
             lang = [self._dense_lang(t) for t in lang]
         return lang, vis
@@ -1440,7 +1546,7 @@ class Engine:
     def _dense_lang(self, t, out=None):
         """packed language rows -> dense [B*L, d] (zero rows where the attention mask is 0)"""
         if out is None:
-            out = torch.zeros(self.MLd, self.d, dtype=self.cdtype, device=self.dev)
+            out = torch.zeros(self.MLd, self.d, dtype=t.dtype, device=self.dev)
         else:
             self.ops.zero(out)
         self.ops.scatter_rows(t, self.lrows, out, self.ML, self.d, self.d, self.d)
@@ -1489,14 +1595,18 @@ class Engine:
         ops.embed_ln_fwd(self._emb_ids if emb else self.ids, self.tt,
                          self._emb_tab if emb else st.cview(e + ".word_embeddings.weight"), st.cview(e + ".position_embeddings.weight"),
                          st.cview(e + ".token_type_embeddings.weight"), st.view(e + ".LayerNorm.weight"),
-                         st.view(e + ".LayerNorm.bias"), self.emb_y, self.emb_pre, self.emb_mean, self.emb_rstd,
+                         st.view(e + ".LayerNorm.bias"), _h(self.emb_y), self.emb_pre, self.emb_mean, self.emb_rstd,
                          self.B, self.L, d, self.eps)
+        if self.res32:                  # composed: the LayerNorm again on the saved pre-LayerNorm sum, fp32 value + bf16 rounding
+            ops.cast_to_f32(self.emb_pre, self.emb_pre32, self.MLd * d)
+            self.ln_fwd(self.emb_pre32, st.view(e + ".LayerNorm.weight"), st.view(e + ".LayerNorm.bias"), self.emb_y,
+                        self.emb_mean, self.emb_rstd, self.MLd, d)
         if self.p_hid > 0:              # HF:213
-            ops.dropout(self.emb_y, self.emb_y, self.MLd, d, d, d, self.p_hid, self.seed(0))
+            self.dropout_stream(self.emb_y, self.MLd, self.seed(0))
         x = self.emb_y
         if self.packed:                 # the real tokens' rows, packed (zero rows in the tail that pads to the row tile)
             x = self.emb_p[:ML]
-            ops.gather_rows(self.emb_y, self.lrows, x, ML, d, d, d)
+            self.gather_stream(self.emb_y, self.lrows, x, ML)
         for i, (sa, ffn) in enumerate(self.lang_layers[:n_layers]):
             self._pr(("lang", i))
             x, mid, y = self._lang_layer_io(i)
@@ -1534,12 +1644,18 @@ class Engine:
         ops.block = "visn_fc"
         ops.gemm(self.feats, st.cview(v + ".visn_fc.weight"), self.xv, st.view(v + ".visn_fc.bias"), None, None,
                  MV, d, self.F, self.F, self.F, d)
-        ops.visn_ln_fwd(self.xv, self.pos, st.view(v + ".box_fc.weight"), st.view(v + ".box_fc.bias"),
+        xv, vis0 = self.xv, self.vis0
+        if self.res32:                  # composed: the fp32 instance of the feature encoder tail on an fp32 copy of visn_fc's output
+            ops.cast_to_f32(self.xv, self.xv32, MV * d)
+            xv, vis0 = self.xv32, self.vis0.f
+        ops.visn_ln_fwd(xv, self.pos, st.view(v + ".box_fc.weight"), st.view(v + ".box_fc.bias"),
                         st.view(v + ".visn_layer_norm.weight"), st.view(v + ".visn_layer_norm.bias"),
                         st.view(v + ".box_layer_norm.weight"), st.view(v + ".box_layer_norm.bias"),
-                        self.vis0, *self.vn_stats, MV, d, self.P, self.eps)
+                        vis0, *self.vn_stats, MV, d, self.P, self.eps)
         if self.p_hid > 0:              # HF:475
-            ops.dropout(self.vis0, self.vis0, MV, d, d, d, self.p_hid, self.seed(1))
+            self.dropout_stream(self.vis0, MV, self.seed(1))
+        elif self.res32:
+            ops.cast_from_f32(self.vis0.f, self.vis0.h, MV * d)
         for i, (sa, ffn) in enumerate(self.vis_layers[:n_vis_alone]):
             self._pr(("vis", i))
             x, mid, y = self._vis_layer_io(i)
@@ -1572,9 +1688,9 @@ class Engine:
                 if blk is last and ffn_rows is not None:
                     rows, n = ffn_rows
                     if self._ffn_in_c is None:
-                        self._ffn_in_c, self._vis_c = self.act(MV, d), self.act(MV, d)
+                        self._ffn_in_c, self._vis_c = self.sact(MV, d), self.sact(MV, d)
                     ops.block = blk["ffn_v"].tag
-                    ops.gather_rows(self.vr(S), rows, self._ffn_in_c[:n], n, d, d, d)       # (pad entries: zero rows)
+                    self.gather_stream(self.vr(S), rows, self._ffn_in_c[:n], n)             # (pad entries: zero rows)
                     blk["ffn_v"].rows = n
                     blk["ffn_v"].fwd(self._ffn_in_c[:n], self._vis_c[:n])
                 else:
@@ -1582,9 +1698,9 @@ class Engine:
             if blk["lang_on"]:
                 self.join()
         Xl = self.X[-1]
-        self.lang_final, self.vis_final = self.lr(Xl), self.vr(Xl)
+        self.lang_final, self.vis_final = _h(self.lr(Xl)), _h(self.vr(Xl))      # (the heads read the bf16 copy of an fp32 stream)
         if self.packed and self.need_lang:          # language_output in the reference's [B, L, d] layout for whoever reads it
-            self.lang_final = self._dense_lang(self.lr(Xl), self.lang_pad)
+            self.lang_final = self._dense_lang(self.lang_final, self.lang_pad)
         self._pr("heads")                   # pooler and every head on top of the encoder
         if want_pooled and self.need_lang:
             # LxmertPooler (HF:566-572): tanh(dense(lang[:, 0]))
@@ -1608,7 +1724,7 @@ class Engine:
         vis = self.vis_final
         if self._hrows is not None and self._ffn_rows_run is not None:
             assert self._ffn_rows_run[1] == M
-            self._hvis_buf = self._vis_c                       # the last visual feed-forward block ran on these rows only
+            self._hvis_buf = _h(self._vis_c)                   # the last visual feed-forward block ran on these rows only
             vis = self._hvis_buf[:M]
         elif self._hrows is not None:
             self._hvis_buf = self.tmp("vis_c", self.MV, d)     # kept: the backward contracts over it (tmp() there may hand out the
@@ -1654,10 +1770,10 @@ class Engine:
         self.wgrad_flush()
         if accumulate:              # in-place: every output element is read (residual) and written by the same lane
             ops.gemm(dz, st.cview("bert.pooler.dense.weight"), d_cls, None, d_cls, None, B, d, d, d, d, L * d, ldr=L * d,
-                     a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL)
+                     a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL, **self.rkw)
         else:
             ops.gemm(dz, st.cview("bert.pooler.dense.weight"), d_cls, None, None, None, B, d, d, d, d, L * d,
-                     a_kmajor=1, b_kmajor=0)
+                     a_kmajor=1, b_kmajor=0, **self.rkw)
 
     # ---- QA branch of a task_qa pretraining model (ref lxrt/modeling.py:292-304): rides on every task
     def _qa_forward(self, qa_labels):
@@ -2033,10 +2149,10 @@ class Engine:
         self.wgrad_defer(dtp, hv, hd["wt"][1], d, d, Mk, d, d, d)
         self.wgrad_flush()
         if self._hrows is None:
-            ops.gemm(dtp, hd["wt"][0], d_vis, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0)
+            ops.gemm(dtp, hd["wt"][0], d_vis, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **self.rkw)
         else:                       # gradient of the masked rows, scattered into an otherwise zero d(vision_output)
-            dvc = self.tmp("dvis_c", MV, d)
-            ops.gemm(dtp, hd["wt"][0], dvc, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0)
+            dvc = self.tmp("dvis_c", MV, d, res=True)          # (fp32 stream: the head's gradient enters it in fp32)
+            ops.gemm(dtp, hd["wt"][0], dvc, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **self.rkw)
             if self._ffn_rows_run is not None:          # ... or handed over compact: the last visual feed-forward block's
                 self._dvis_c = dvc[:M]                  # backward runs on these rows too (_encoder_backward); d_vis is not written
             else:
@@ -2099,7 +2215,7 @@ class Engine:
                         ops.block = blk["ffn_v"].tag
                         ops.zero(V_(GB))                    # d(the block's input): zero on the rows it did not read
                         if dvc is not Engine._NO_VIS_GRAD:
-                            dsc = self.tmp("dffn_c", MV, d)[:n]
+                            dsc = self.tmp("dffn_c", MV, d, res=True)[:n]
                             blk["ffn_v"].bwd(dvc, dsc)
                             ops.block = blk["ffn_v"].tag
                             ops.scatter_rows(dsc, rows, V_(GB), n, d, d, d)
@@ -2140,14 +2256,19 @@ class Engine:
             e = "bert.embeddings"
             dy, MLd = L_(GA), self.MLd
             if self.packed:                       # back to the dense [B*L] rows of the embedding kernels (zero at [PAD] positions)
-                dy = self.tmp("emb_dy", MLd, d)
+                dy = self.tmp("emb_dy", MLd, d, res=True)
                 ops.zero(dy)
                 ops.scatter_rows(L_(GA), self.lrows, dy, ML, d, d, d)
             if self.p_hid > 0:
                 ops.dropout(dy, dy, MLd, d, d, d, self.p_hid, self.seed(0))
-            dpre = self.tmp("emb_dz", MLd, d)     # not "dz": layer 0's weight-gradient group may still be reading it
-            ops.layernorm_bwd(dy, self.emb_pre, st.view(e + ".LayerNorm.weight"), self.emb_mean, self.emb_rstd, dpre,
-                              st.gview(e + ".LayerNorm.weight"), st.gview(e + ".LayerNorm.bias"), None, MLd, d, ws=self.ws)
+            dpre = self.tmp("emb_dz", MLd, d, res=True)     # not "dz": layer 0's weight-gradient group may still be reading it
+            if self.res32:              # composed: fp32 d(pre) for the fp32 instance of the table scatter (the bf16 copy is not read)
+                ops.layernorm_bwd_res(dy, self.emb_pre32, st.view(e + ".LayerNorm.weight"), self.emb_mean, self.emb_rstd, dpre,
+                                      st.gview(e + ".LayerNorm.weight"), st.gview(e + ".LayerNorm.bias"), None, MLd, d, ws=self.ws,
+                                      dx_dropped=self.tmp("emb_dzm", MLd, d))
+            else:
+                ops.layernorm_bwd(dy, self.emb_pre, st.view(e + ".LayerNorm.weight"), self.emb_mean, self.emb_rstd, dpre,
+                                  st.gview(e + ".LayerNorm.weight"), st.gview(e + ".LayerNorm.bias"), None, MLd, d, ws=self.ws)
             emb = getattr(self, "embeds_mode", False)
             if emb:                                   # d(inputs_embeds) instead of d(word_embeddings): see set_inputs
                 ops.zero(self._emb_grad)
@@ -2176,12 +2297,18 @@ class Engine:
         dxv = self.tmp("dctx", MV, d)
         if self.p_hid > 0:
             ops.dropout(V_(GA), V_(GA), MV, d, d, d, self.p_hid, self.seed(1))
-        ops.visn_ln_bwd(V_(GA), self.xv, self.pos, st.view(v + ".box_fc.weight"), st.view(v + ".box_fc.bias"),
+        dxv16 = dxv
+        if self.res32:                  # composed: the fp32 instance on the fp32 copy of visn_fc's output, then the bf16 operand
+            dxv = self.tmp("dxv32", MV, d, res=True)
+        ops.visn_ln_bwd(V_(GA), self.xv32 if self.res32 else self.xv, self.pos, st.view(v + ".box_fc.weight"), st.view(v + ".box_fc.bias"),
                         st.view(v + ".visn_layer_norm.weight"), st.view(v + ".box_layer_norm.weight"), *self.vn_stats,
                         dxv, st.gview(v + ".visn_layer_norm.weight"), st.gview(v + ".visn_layer_norm.bias"),
                         st.gview(v + ".box_layer_norm.weight"), st.gview(v + ".box_layer_norm.bias"),
                         st.gview(v + ".box_fc.weight"), st.gview(v + ".box_fc.bias"), st.gview(v + ".visn_fc.bias"),
                         MV, d, self.P, ws=self.ws)
+        if self.res32:
+            ops.cast_from_f32(dxv, dxv16, MV * d)
+            dxv = dxv16
         if self.grad_ready is None:
             self.wgrad_flush(pair=True, force=True)          # (the visual stack's last held layer: see above)
         ops.gemm(dxv, self.feats, st.gview(v + ".visn_fc.weight"), None, None, None, d, self.F, MV, d, self.F, self.F,

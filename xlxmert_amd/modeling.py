@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .config import XLxmertConfig
-from .engine import Engine
+from .engine import Engine, _h
 from .ops import HipOps
 from .params import ParamStore
 
@@ -76,9 +76,13 @@ class _EncoderFn(torch.autograd.Function):
 class LxmertModel(_Named):
     """Embeddings + LxmertEncoder (9 language / 5 visual / 5 cross layers) + pooler (HF:675-822)."""
 
-    def __init__(self, config: XLxmertConfig, store=None, device=None, dtype=torch.bfloat16, task="all"):
+    def __init__(self, config: XLxmertConfig, store=None, device=None, dtype=torch.bfloat16, task="all", residual_dtype=None):
+        """residual_dtype ("bf16" | "fp32"; None: env XL_RESIDUAL, default "bf16"; meaningful with dtype=torch.bfloat16): storage type
+        of the residual stream, passed on to engine.Engine -- "fp32" keeps the pre-LayerNorm sums, the LayerNorm outputs and their
+        gradients in fp32 beside bf16 operands; output_hidden_states then returns the fp32 values."""
         super().__init__()
         self.config = config
+        self._residual_dtype = residual_dtype
         dev = torch.device(device if device is not None else "cuda")
         self._owns_store = store is None
         self._store = store if store is not None else ParamStore(config, dev, dtype, task=task)
@@ -93,7 +97,7 @@ class LxmertModel(_Named):
     def _engine_for(self, B, L, V):
         if self._geom != (B, L, V, self.training):
             self._engine = Engine(self.config, self._store, self._ops, B, L, V, need_lang=True,
-                                  train_dropout=self.training)
+                                  train_dropout=self.training, residual_dtype=self._residual_dtype)
             self._geom = (B, L, V, self.training)
         self._engine.sync_compute_weights()
         self._advance_seed(self._engine)
@@ -157,8 +161,8 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, vis, want_obj):
         eng = head._bert._engine
-        eng.vr(eng.X[-1]).copy_(vis.reshape(eng.MV, eng.d))
-        eng.vis_final = eng.vr(eng.X[-1])
+        eng.vis_final = _h(eng.vr(eng.X[-1]))               # (the head reads the bf16 copy of an fp32 residual stream)
+        eng.vis_final.copy_(vis.reshape(eng.MV, eng.d))
         feat, logits = eng.head_forward(want_logits=want_obj)
         ctx.head = head
         B, V = eng.B, eng.V
@@ -174,7 +178,7 @@ class _HeadFn(torch.autograd.Function):
         eng.with_feat_loss = d_feat is not None
         if d_feat is not None:
             eng.dfeat.copy_(d_feat.reshape(MV, eng.F))
-        d_vis = torch.empty(MV, eng.d, dtype=eng.cdtype, device=eng.dev)
+        d_vis = torch.empty(MV, eng.d, dtype=torch.float32 if eng.res32 else eng.cdtype, device=eng.dev)
         eng.head_backward(d_vis)
         return None, d_vis.view(eng.B, eng.V, eng.d), None
 
@@ -199,8 +203,8 @@ class LxmertVisualObjHead(_Named):
         if torch.is_grad_enabled() and hidden_states.requires_grad:
             feat, obj = _HeadFn.apply(self, hidden_states, True)
         else:
-            eng.vr(eng.X[-1]).copy_(hidden_states.reshape(eng.MV, eng.d))
-            eng.vis_final = eng.vr(eng.X[-1])
+            eng.vis_final = _h(eng.vr(eng.X[-1]))
+            eng.vis_final.copy_(hidden_states.reshape(eng.MV, eng.d))
             f, o = eng.head_forward(True)
             feat, obj = f.view(eng.B, eng.V, -1).float().clone(), o.view(eng.B, eng.V, -1).clone()
         output = {}
@@ -255,7 +259,8 @@ class XLxmertForPretraining(nn.Module):
     """ref lxrt/modeling.py:56-308: `.bert`, `.cls` (task_mask_lm or task_matched), `.obj_predict_head` (task_obj_predict),
     `.answer_head` (task_qa), `.mask_feat`, `.vis_emb`; forward(task = 'vis_mask' | 'word_mask' | 'matched' | 'qa')."""
 
-    def __init__(self, config: XLxmertConfig, num_clusters=None, device=None, dtype=torch.bfloat16):
+    def __init__(self, config: XLxmertConfig, num_clusters=None, device=None, dtype=torch.bfloat16, residual_dtype=None):
+        """residual_dtype: see LxmertModel (storage type of the residual stream: "bf16" default, "fp32")."""
         super().__init__()
         if num_clusters is not None:
             config.num_clusters = num_clusters
@@ -269,7 +274,7 @@ class XLxmertForPretraining(nn.Module):
         # dead-branch-free layout of the masked-visual-token step
         self._store = ParamStore(config, dev, dtype, task="all" if multi else "vis_mask",
                                  num_answers=self.num_qa_labels if self.task_qa else 0)
-        self.bert = LxmertModel(config, store=self._store, device=dev)
+        self.bert = LxmertModel(config, store=self._store, device=dev, residual_dtype=residual_dtype)
         if self.task_mask_lm or self.task_matched:
             self.cls = LxmertPreTrainingHeads(self._store)
         self.obj_predict_head = LxmertVisualObjHead(config, self.bert)
@@ -400,7 +405,8 @@ class XLxmertForPretraining(nn.Module):
         key = (B, L, V, self.training, "step")
         if self.bert._geom != key:
             self.bert._engine = Engine(self.config, self._store, self.bert._ops, B, L, V,
-                                       need_lang=self._store.task != "vis_mask", train_dropout=self.training)
+                                       need_lang=self._store.task != "vis_mask", train_dropout=self.training,
+                                       residual_dtype=self.bert._residual_dtype)
             self.bert._geom = key
         self.bert._engine.sync_compute_weights()
         self.bert._advance_seed(self.bert._engine)
@@ -447,12 +453,13 @@ class VQAModel(nn.Module):
 
     _task = "vqa"
 
-    def __init__(self, config: XLxmertConfig, num_answers, num_clusters=-1, device=None, dtype=torch.bfloat16):
+    def __init__(self, config: XLxmertConfig, num_answers, num_clusters=-1, device=None, dtype=torch.bfloat16, residual_dtype=None):
+        """residual_dtype: see LxmertModel (storage type of the residual stream: "bf16" default, "fp32")."""
         super().__init__()
         self.config, self.num_answers = config, num_answers
         dev = torch.device(device if device is not None else "cuda")
         self._store = ParamStore(config, dev, dtype, task=self._task, num_answers=num_answers)
-        self.bert = LxmertModel(config, store=self._store, device=dev)
+        self.bert = LxmertModel(config, store=self._store, device=dev, residual_dtype=residual_dtype)
         self.answer_head = LxmertVisualAnswerHead(self._store)
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         from .trainer import init_reference_weights
@@ -487,7 +494,7 @@ class VQAModel(nn.Module):
         key = (B, L, V, self.training, self._task)
         if self.bert._geom != key:
             self.bert._engine = Engine(self.config, self._store, self.bert._ops, B, L, V, need_lang=True,
-                                       train_dropout=self.training)
+                                       train_dropout=self.training, residual_dtype=self.bert._residual_dtype)
             self.bert._geom = key
         eng = self.bert._engine
         eng.sync_compute_weights()
@@ -511,8 +518,8 @@ class NLVR2Model(VQAModel):
     the head that forward needs -- Linear(2d, 2d) -> GeLU -> LayerNorm(2d) -> Linear(2d, 2) -- under `.answer_head`."""
     _task = "nlvr2"
 
-    def __init__(self, config: XLxmertConfig, num_answers=2, num_clusters=-1, device=None, dtype=torch.bfloat16):
-        super().__init__(config, num_answers, num_clusters, device, dtype)
+    def __init__(self, config: XLxmertConfig, num_answers=2, num_clusters=-1, device=None, dtype=torch.bfloat16, residual_dtype=None):
+        super().__init__(config, num_answers, num_clusters, device, dtype, residual_dtype=residual_dtype)
 
     def forward(self, input_ids=None, visual_feats=None, visual_pos=None, attention_mask=None, visual_attention_mask=None,
                 token_type_ids=None, inputs_embeds=None, return_dict=True):

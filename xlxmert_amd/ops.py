@@ -13,6 +13,7 @@ from ._lib import XlError, get_lib
 
 XL_F32, XL_BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_TANH, EPI_ROWMAX, EPI_GELU_DG, EPI_MULAUX = 0, 1, 2, 3, 4, 5, 6, 7
+EPI_RESIDUAL_F32 = 8            # XL_EPI_RESIDUAL with an fp32 residual and output (the fp32 residual stream); chosen by HipOps.gemm
 
 TORCH_DTYPE = {XL_F32: torch.float32, XL_BF16: torch.bfloat16}
 _SLAB_WS = {}
@@ -200,7 +201,13 @@ class HipOps:
     # -- dense contractions
     def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1,
              out_f32=False, epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
-        """colsum: optional fp32 [N] that receives += the column sums of C (bias gradient), with workspace `ws`."""
+        """colsum: optional fp32 [N] that receives += the column sums of C (bias gradient), with workspace `ws`.
+        epilogue=EPI_RESIDUAL with bf16 operands and an fp32 `residual` (the fp32 residual stream): XL_EPI_RESIDUAL_F32 -- `C` is fp32
+        too (out_f32 required); same dropout draw."""
+        if epilogue == EPI_RESIDUAL and residual is not None and residual.dtype == torch.float32 and self.dt == XL_BF16:
+            if not out_f32 or C.dtype != torch.float32:
+                raise XlError("gemm: an fp32 residual (XL_EPI_RESIDUAL_F32) needs out_f32=True and an fp32 C")
+            epilogue = EPI_RESIDUAL_F32
         self._call("xl_gemm", self._p(A), self._p(B), self._p(C), self._p(bias), self._p(residual), self._p(aux),
                       M, N, K, lda, ldb, ldc, ldr, ldx, int(a_kmajor), int(b_kmajor), self.dt,
                       XL_F32 if out_f32 else self.dt, epilogue, float(alpha), int(accumulate), float(p_drop),
@@ -280,6 +287,22 @@ class HipOps:
         self._call("xl_layernorm_fwd", self._p(x), self._p(gamma), self._p(beta), self._p(y), self._p(mean),
                       self._p(rstd), M, N, float(eps), self.dt, self._stream())
 
+    def layernorm_fwd_res(self, x, gamma, beta, y32, y16, mean, rstd, M, N, eps):
+        """fp32 residual stream: x fp32 -> y32 = LN(x) fp32 and y16 = bf16(y32) (xl_layernorm_fwd_res)"""
+        if not (x.dtype == y32.dtype == torch.float32 and y16.dtype == torch.bfloat16):
+            raise XlError("layernorm_fwd_res: x / y32 are fp32, y16 is bf16")
+        self._call("xl_layernorm_fwd_res", self._p(x), self._p(gamma), self._p(beta), self._p(y32), self._p(y16), self._p(mean),
+                   self._p(rstd), M, N, float(eps), self._stream())
+
+    def layernorm_bwd_res(self, dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dbias_prev, M, N, ws=None, dx_dropped=None,
+                          p_drop=0.0, seed=0):
+        """fp32 residual stream: dy, x, dx fp32; dx_dropped bf16, always written (xl_layernorm_bwd_res)"""
+        if not (dy.dtype == x.dtype == dx.dtype == torch.float32 and dx_dropped is not None and dx_dropped.dtype == torch.bfloat16):
+            raise XlError("layernorm_bwd_res: dy / x / dx are fp32, dx_dropped is bf16 and always written")
+        self._call("xl_layernorm_bwd_res", self._p(dy), self._p(x), self._p(gamma), self._p(mean), self._p(rstd),
+                   self._p(dx), self._p(dgamma), self._p(dbeta), self._p(dbias_prev), M, N, self._p(ws),
+                   self._p(dx_dropped), float(p_drop), int(seed), self._stream())
+
     def workspace_floats(self, N):
         return int(self.lib.raw("xl_workspace_floats")(int(N)))
 
@@ -292,14 +315,14 @@ class HipOps:
     def visn_ln_fwd(self, xv, pos, wbox, bbox, gv, bv, gb, bb, y, mean_v, rstd_v, mean_b, rstd_b, M, N, P, eps):
         self._call("xl_visn_ln_fwd", self._p(xv), self._p(pos), self._p(wbox), self._p(bbox), self._p(gv),
                       self._p(bv), self._p(gb), self._p(bb), self._p(y), self._p(mean_v), self._p(rstd_v),
-                      self._p(mean_b), self._p(rstd_b), M, N, P, float(eps), self.dt, self._stream())
+                      self._p(mean_b), self._p(rstd_b), M, N, P, float(eps), xl_dtype(xv.dtype), self._stream())
 
     def visn_ln_bwd(self, dy, xv, pos, wbox, bbox, gv, gb, mean_v, rstd_v, mean_b, rstd_b, dxv, dgv, dbv, dgb, dbb,
                     dwbox, dbbox, dbias_visn, M, N, P, ws=None):
         self._call("xl_visn_ln_bwd", self._p(dy), self._p(xv), self._p(pos), self._p(wbox), self._p(bbox),
                       self._p(gv), self._p(gb), self._p(mean_v), self._p(rstd_v), self._p(mean_b), self._p(rstd_b),
                       self._p(dxv), self._p(dgv), self._p(dbv), self._p(dgb), self._p(dbb), self._p(dwbox),
-                      self._p(dbbox), self._p(dbias_visn), M, N, P, self._p(ws), self.dt, self._stream())
+                      self._p(dbbox), self._p(dbias_visn), M, N, P, self._p(ws), xl_dtype(xv.dtype), self._stream())
 
     # -- embeddings / codebook
     def embed_ln_fwd(self, ids, tt, word, pos, type_, gamma, beta, y, pre, mean, rstd, B, L, N, eps):
@@ -310,7 +333,7 @@ class HipOps:
     def embed_bwd(self, dpre, ids, tt, dword, dpos, dtype_tab, B, L, N, order=None, n_types=2):
         """order: int32 [B*L] rows sorted by (id, row) -- trainer.word_order_of(input_ids); None: the (slow) scanning kernel"""
         self._call("xl_embed_bwd", self._p(dpre), self._p(ids), self._p(tt), self._p(order), self._p(dword), self._p(dpos),
-                      self._p(dtype_tab), B, L, N, int(n_types), self.dt, self._stream())
+                      self._p(dtype_tab), B, L, N, int(n_types), xl_dtype(dpre.dtype), self._stream())
 
     def codebook_gather(self, cluster_ids, vis_mask, centroids, mask_feat, feats, M, F):
         self._call("xl_codebook_gather", self._p(cluster_ids), self._p(vis_mask), self._p(centroids),
@@ -324,7 +347,7 @@ class HipOps:
         self._call("xl_colsum", self._p(x), self._p(out), M, N, ldx, self._p(ws), self.dt, self._stream())
 
     def dropout(self, x, y, M, N, ldx, ldy, p_drop, seed):
-        self._call("xl_dropout", self._p(x), self._p(y), M, N, ldx, ldy, float(p_drop), int(seed), self.dt,
+        self._call("xl_dropout", self._p(x), self._p(y), M, N, ldx, ldy, float(p_drop), int(seed), xl_dtype(x.dtype),
                       self._stream())
 
     def gelu_bwd(self, dy, pre, dx, n):
@@ -392,10 +415,10 @@ class HipOps:
                       self._p(rows), int(n_rows), self._p(targets), self.dt, self._stream())
 
     def gather_rows(self, src, rows, dst, n_rows, N, ld_src, ld_dst):
-        self._call("xl_gather_rows", self._p(src), self._p(rows), self._p(dst), n_rows, N, ld_src, ld_dst, self.dt, self._stream())
+        self._call("xl_gather_rows", self._p(src), self._p(rows), self._p(dst), n_rows, N, ld_src, ld_dst, xl_dtype(src.dtype), self._stream())
 
     def scatter_rows(self, src, rows, dst, n_rows, N, ld_src, ld_dst):
-        self._call("xl_scatter_rows", self._p(src), self._p(rows), self._p(dst), n_rows, N, ld_src, ld_dst, self.dt, self._stream())
+        self._call("xl_scatter_rows", self._p(src), self._p(rows), self._p(dst), n_rows, N, ld_src, ld_dst, xl_dtype(src.dtype), self._stream())
 
     def rowmax_combine(self, ws, n_seg, M, row_maxprob, row_argmax, row_lse=None):
         """second half of gemm(epilogue=EPI_ROWMAX, aux=ws): per-row argmax / max softmax probability / log-sum-exp."""

@@ -53,8 +53,12 @@ class PretrainStep:
                  lr=1e-4, weight_decay=0.0, warmup_ratio=0.05, total_steps=100000, clip_grad_norm=1.0,
                  betas=(0.9, 0.999), eps=1e-6, seed=9595, feat_loss=None, train_dropout=False, store=None,
                  bucket_mb=64, ops=None, task="vis_mask", num_answers=0, visual_losses="obj", grad_comm_dtype=None,
-                 plan=None, drop_grads=None, overlap_optimizer=None, collective=None, overwrite_grads=None, gather=None):
+                 plan=None, drop_grads=None, overlap_optimizer=None, collective=None, overwrite_grads=None, gather=None,
+                 residual_dtype=None):
         """`ops` is injected only by the CPU test-suite (tests/fake_ops.py); the product always runs HipOps.
+        residual_dtype ("bf16" default | "fp32"; None: env XL_RESIDUAL; meaningful with dtype=torch.bfloat16): storage type of the
+        residual stream -- "fp32" keeps every pre-LayerNorm sum, every LayerNorm output and their gradients in fp32 beside bf16
+        operands (engine.Engine residual_dtype: about a third less gradient error for ~0.5 GB more activations at bs 256).
         task: "vis_mask" (masked-visual-token pretraining step, ref lxmert_pretrain.py), "word_mask" / "matched" (the
         language pretraining branches) or "vqa" (VQA/GQA fine-tune step on real grid features with `num_answers` answers,
         ref tasks/vqa.py:166-198) -- same clip / AdamW / schedule.  task="all": the three pretraining branches on ONE
@@ -125,7 +129,7 @@ class PretrainStep:
         if store is None:
             init_reference_weights(self.store, seed)          # same seed on every rank == DDP's rank-0 broadcast
         self.engine = Engine(cfg, self.store, self.ops, batch_size, text_len, n_grids, need_lang=(task != "vis_mask"),
-                             train_dropout=train_dropout)
+                             train_dropout=train_dropout, residual_dtype=residual_dtype)
         self.engine.sync_compute_weights()
         self.store.ensure_adam_state()
         self._plans, self._plan_warm = {}, False
