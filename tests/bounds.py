@@ -144,22 +144,55 @@ def attention_parts(Q, K, V, valid, keep, scale):
     return s, P, Pk, eS
 
 
-def sdpa_fwd_bounds(Q, K, V, valid, keep, scale, O_ref, lse_ref):
+def score_range(s, valid):
+    """max_k |s_k - max s| over the valid keys of every query row (0 for a row without one): attention_parts' `rng`"""
+    mx = s.amax(-1, keepdim=True).nan_to_num(0.0, neginf=0.0)
+    return ((s.masked_fill(~valid, 0.0) - mx).abs() * valid).amax(-1, keepdim=True)
+
+
+def blocked_rescale_error(n_blk, rng):
+    """relative error that the online softmax of sdpa_fwd_flash / sdpa_fwd_long adds to every term of the running sum and of the
+    output accumulators.  Key block i multiplies both by corr_i = __expf(m_{i-1} - m_i) (m the running maximum; corr = 0 exactly
+    while no key has been seen, 1 exactly while the maximum stays): the subtraction and the log2 e scaling of the argument round
+    once each (2 U32 |m_{i-1} - m_i| relative to corr_i), v_exp_f32 EXP_ULP, the multiply 1.  The running maximum only rises and
+    ends at max s, starting from a valid score, so sum_i |m_{i-1} - m_i| <= rng = max_k |s_k - max s|.  A term passes at most
+    n_blk - 1 rescales:   (n_blk - 1) (EXP_ULP + 1) U32 + 2 U32 rng."""
+    return (n_blk - 1) * (EXP_ULP + 1) * U32 + 2 * U32 * rng
+
+
+def sdpa_fwd_bounds(Q, K, V, valid, keep, scale, O_ref, lse_ref, n_kblk=1):
     """xl_sdpa_fwd (sdpa_fwd_mfma).  P' = softmax(s) keep is rounded to bf16 before the PV MFMA (design: U16 |P'||V|).  A score
     error e_S moves every p_j by at most p_j (|ds_j| + sum_k p_k |ds_k|) <= 2 e_S p_j; exp (v_exp_f32, 2 ulp), 1/sum (1 ulp) and
     the nk-deep fp32 sum add (nk + 4) U32 relative to the row.  So
         |dO| <= U16 |O| + SLACK (U16 + 2 e_S + (nk + 4) U32) |P'| |V|.
-    lse = max + log(sum): e_S + (nk + 4) U32 + 2 U32 |lse| + 2^-21 (__logf on a sum in [1, nk])."""
+    lse = max + log(sum): e_S + (nk + 4) U32 + 2 U32 |lse| + 2^-21 (__logf on a sum in [1, nk]).
+
+    n_kblk > 1: the kernels that walk the keys in n_kblk = ceil(nk / 64) blocks (sdpa_fwd_flash; the plain sdpa_fwd_long is the
+    same algorithm with one key per step, fp32 throughout and P not rounded to bf16: it stays inside this bound).  What changes:
+      * the un-normalised P~ = exp(s - m_running) keep is what is rounded to bf16, relative to the RUNNING maximum: the same
+        relative U16 per term, and the later rescales are common factors of the term -- U16 |P'||V| as before;
+      * the rounding of exp's argument s - m_running is U32 |s - m_running| <= U32 rng: e_S has it;
+      * every term of the sum and of the accumulators carries r = blocked_rescale_error(n_kblk, rng); numerator and denominator of
+        O = acc / sum each move by r relative to |P'||V|:  2 r |P'||V|;
+      * O^T += V^T P^T is an fp32 MFMA chain over all nk keys carried across the blocks, and the division by the sum is one
+        multiply of the accumulator at the end:  (nk + 1) U32 |P'||V|;
+      * lse = m + __logf(sum) with the sum accumulated (and rescaled) across the blocks:  + r.
+    With n_kblk = 1 none of these terms exists and the result is the on-chip bound, bit for bit."""
     nk = K.shape[-2]
-    _, P, Pk, eS = attention_parts(Q, K, V, valid, keep, scale)
+    s, P, Pk, eS = attention_parts(Q, K, V, valid, keep, scale)
     pv = Pk.abs() @ V.abs()
     bO = U16 * O_ref.abs() + SLACK * (U16 + 2 * eS + (nk + 4) * U32) * pv + TINY
     lse_f = lse_ref.nan_to_num(0.0, neginf=0.0)
     bl = SLACK * (eS[..., 0] + (nk + 4) * U32 + 2 * U32 * lse_f.abs() + 2.0 ** -21)
+    if n_kblk > 1:
+        assert n_kblk == (nk + 63) // 64, (n_kblk, nk)
+        r = blocked_rescale_error(n_kblk, score_range(s, valid))
+        bO = bO + SLACK * (2 * r + (nk + 1) * U32) * pv
+        bl = bl + SLACK * r[..., 0]
     return bO, bl
 
 
-def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref):
+def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref, n_kblk=1, n_qblk=1):
     """xl_sdpa_bwd (sdpa_bwd_mfma).  P = exp(s - lse) from the saved lse (the reference uses the same lse): e_P = e_S + 2 U32 +
     U32 |s - lse| relative.  dP = dO V^T (dh-deep: dh U32 |dO||V|^T), times keep.  delta = sum_k P dP': nk-deep.
     dS = P (dP' - delta) scale, |err| <= scale (e_P P |dP' - delta| + P (|ddP| + |ddelta|)) + 3 U32 |dS|, then rounded to bf16
@@ -167,8 +200,27 @@ def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref
         dV = P'^T dO   U16 |dV| + SLACK (U16 + e_P + (nq + 2) U32) |P'|^T |dO|            (P' rounded to bf16 by design)
         dQ = dS K      U16 |dQ| + SLACK (|dS_err| |K| + nk U32 |dS| |K|)
         dK = dS^T Q    U16 |dK| + SLACK (|dS_err|^T |Q| + nq U32 |dS|^T |Q|)
-    Returns the three bounds and the per-element fp32 error terms (without the final rounding) for the fused bias sums."""
+    Returns the three bounds and the per-element fp32 error terms (without the final rounding) for the fused bias sums.
+
+    n_kblk, n_qblk > 1: the two-launch backward of the long path (sdpa_bwd_flash_q over n_kblk = ceil(nk / 64) key blocks,
+    sdpa_bwd_flash_k over n_qblk = ceil(nq / 64) query blocks; sdpa_bwd_long_q / _k are the same sums one key / query per step,
+    fp32 throughout: inside this bound).  Term by term:
+      * P = __expf(s scale - lse) is recomputed per block, in both launches, from the same saved lse by the same expression: e_P
+        as above, nothing accumulates across blocks;
+      * delta: a lane sums its 32 products of a block serially, adds the block's partial to its running delta (n_kblk additions)
+        and the two half-waves combine once.  Every product still passes fewer than nk additions (32 + n_kblk + 1 <= nk for
+        nk > 64), but the partials are additions outside any one chain, so the bound counts them:  K_eff = nk + n_kblk + 1.
+        delta reaches the key-side launch through an fp32 workspace: exact;
+      * dQ^T += K^T dS^T over the key blocks, dK^T += Q^T dS and dV^T += dO^T P~ over the query blocks: MFMA accumulators carried
+        in fp32 across the blocks, depth nk resp. nq -- the terms above already have these depths (rows of a partial block
+        beyond the length are exact zeros); n_qblk adds nothing and is accepted so that a caller states the geometry;
+      * dS and P~ are rounded to bf16 per block exactly as on chip: U16 |dS|, U16 |P'|.
+    With both counts 1 the result is the on-chip bound, bit for bit."""
     nq, nk, dh = Q.shape[-2], K.shape[-2], Q.shape[-1]
+    assert n_kblk >= 1 and n_qblk >= 1
+    if n_kblk > 1 or n_qblk > 1:
+        assert n_kblk == (nk + 63) // 64 and n_qblk == (nq + 63) // 64, (n_kblk, nk, n_qblk, nq)
+    k_delta = nk if n_kblk == 1 else nk + n_kblk + 1
     s = (Q @ K.transpose(-1, -2)) * scale
     P = torch.exp(s - lse[..., None]).masked_fill(~valid, 0.0).nan_to_num(0.0, posinf=0.0)
     sabs = (Q.abs() @ K.abs().transpose(-1, -2)) * abs(scale)
@@ -176,7 +228,7 @@ def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref
     dP = (dO @ V.transpose(-1, -2)) * keep
     edP = dh * U32 * (dO.abs() @ V.abs().transpose(-1, -2)) * keep
     delta = (P * dP).sum(-1, keepdim=True)
-    edelta = (eP * P * dP.abs() + P * edP).sum(-1, keepdim=True) + nk * U32 * (P * dP.abs()).sum(-1, keepdim=True)
+    edelta = (eP * P * dP.abs() + P * edP).sum(-1, keepdim=True) + k_delta * U32 * (P * dP.abs()).sum(-1, keepdim=True)
     dS = P * (dP - delta) * scale
     edS = abs(scale) * (eP * P * (dP - delta).abs() + P * (edP + edelta)) + 3 * U32 * dS.abs() + U16 * dS.abs()
     Pk = (P * keep).abs()
@@ -482,13 +534,18 @@ def bce_bounds(x, t, M, N, dl_ref, loss_ref, loss_prev, out_dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------------ attn_probs
-def attn_probs_bound(Q, K, V_unused, valid, keep, scale, lse, ref):
+def attn_probs_bound(Q, K, V_unused, valid, keep, scale, lse, ref, n_kblk=1):
     """xl_attn_probs: probs = exp(s - lse) keep from the forward's saved lse (the reference reads the same lse), fp32 out, a serial
     dh-deep fma chain per score.  With attention_parts' per-row score error e_S (the dh-deep contraction and the rounding of the
     exponent) every probability moves by p (e_S + U32 |s - lse| (subtraction + expf scaling: 2) + EXP_ULP U32), the dropout scale
     is one more multiply:  U32 |ref| + SLACK |ref| (e_S + 2 U32 |s - lse| + (EXP_ULP + 2) U32).
     No bf16 rounding of P here: the designed U16 |P'| of sdpa_fwd_bounds belongs to the PV MFMA, which this kernel does not have.
-    Invalid pairs (masked keys, rows / keys beyond a packed example's length) are exactly 0."""
+    Invalid pairs (masked keys, rows / keys beyond a packed example's length) are exactly 0.
+    n_kblk = ceil(nk / 64) > 1 (long sequences): attn_probs_kernel is one lane per query with the keys in a serial loop -- no
+    running maximum, no rescale, no state carried from one key to the next -- and the lse it reads is the one the reference
+    reads, whichever forward kernel wrote it.  No term depends on the block count; it is accepted (and checked against nk) so that
+    the caller states the geometry it ran."""
+    assert n_kblk == 1 or n_kblk == (K.shape[-2] + 63) // 64, (n_kblk, K.shape[-2])
     s, _, _, eS = attention_parts(Q, K, Q[..., :1, :], valid, keep, scale)
     arg = (s - lse[..., None]).abs().masked_fill(~valid, 0.0).nan_to_num(0.0, posinf=0.0)
     return U32 * ref.abs() + SLACK * ref.abs() * (eS + 2 * U32 * arg + (EXP_ULP + 2) * U32) + TINY

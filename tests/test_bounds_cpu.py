@@ -661,3 +661,258 @@ def test_dropout_mask_restatement_in_torch_integers_equals_the_numpy_statement()
             assert torch.equal(keep_scale(seed, row, col, p_drop), keep_scale_torch(seed, *torch.broadcast_tensors(row, col), p_drop))
     assert torch.equal(keep_scale(9, torch.arange(300)[:, None], torch.arange(64)[None, :], 0.1),
                        keep_scale_torch(9, torch.arange(300)[:, None], torch.arange(64)[None, :], 0.1))
+
+
+# ------------------------------------------------------------------------------------------------------------------ long attention
+# Attention with 65..512 tokens per side (csrc/sdpa.hip sdpa_fwd_flash, sdpa_bwd_flash_q, sdpa_bwd_flash_k): a host emulation of
+# the blocked algorithm in plain torch -- fp32 arithmetic, 64-key / 64-query blocks, the un-normalised P~ rounded to bf16 before
+# the PV product, dS rounded to bf16 -- passes the block-aware bounds, and every fault of LONG_FAULTS built into it is rejected.
+# Inputs: 12 heads of 64, q scaled by 1.5 (score standard deviation 1.5: the running maximum rises in later blocks on most rows).
+LONG_SHAPES = [(128, 128), (200, 70), (70, 200)]
+LONG_SCALE = 0.125
+
+
+def long_case(nq, nk, p_drop, kind, seed=17):
+    """kind "masked": B = 3 dense, random key mask with key 0 valid, example 1 with its first 64 keys ALL masked (later keys valid).
+    kind "packed": B = 4, both sides packed, lengths 1 / 64 / 65 / 128 (clipped to the side's capacity), no key mask."""
+    g = _gen(seed)
+    if kind == "packed":
+        B = 4
+        lens = torch.tensor([1, 64, 65, 128])
+        len_q, len_k = lens.clamp(max=nq), lens.clamp(max=nk)
+        q_off, k_off = (torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(l, 0)]).to(torch.int32) for l in (len_q, len_k))
+        rows_q, rows_k, key_mask = int(q_off[-1]), int(k_off[-1]), None
+    else:
+        B = 3
+        len_q, len_k, q_off, k_off = torch.full((B,), nq), torch.full((B,), nk), None, None
+        rows_q, rows_k = B * nq, B * nk
+        key_mask = (torch.rand(B, nk, generator=g) > 0.2).to(torch.uint8)
+        key_mask[:, 0] = 1
+        key_mask[1, :64] = 0
+        key_mask[1, 64:] = 1
+    q = bf(torch.randn(rows_q, H * DH, generator=g) * 1.5)
+    k, v = (bf(torch.randn(rows_k, H * DH, generator=g)) for _ in range(2))
+    do = bf(torch.randn(rows_q, H * DH, generator=g))
+    return dict(q=q, k=k, v=v, do=do, B=B, nq=nq, nk=nk, rows_q=rows_q, rows_k=rows_k, q_off=q_off, k_off=k_off, len_q=len_q,
+                len_k=len_k, key_mask=key_mask, p_drop=p_drop, seed=seed)
+
+
+def long_reference(c):
+    """float64 restatement (FakeOps) and the block-aware bounds, everything in the dense [B, H, n, dh] layout"""
+    B, nq, nk, HD = c["B"], c["nq"], c["nk"], H * DH
+    kw = dict(p_drop=c["p_drop"], seed=c["seed"], q_off=c["q_off"], k_off=c["k_off"])
+    o = torch.zeros(c["rows_q"], HD, dtype=torch.float64)
+    lse = torch.zeros(B * H * nq, dtype=torch.float64)
+    R64.sdpa_fwd(c["q"], c["k"], c["v"], c["key_mask"], o, lse, B, H, nq, nk, DH, HD, HD, HD, HD, LONG_SCALE, **kw)
+    Q, K, V, valid, keep = BD.attention_inputs(R64, c["q"], c["k"], c["v"], c["key_mask"], B, H, nq, nk, DH, HD, HD, HD, c["p_drop"],
+                                               c["seed"], c["q_off"], c["k_off"])
+    lse = lse.view(B, H, nq)
+    lse32 = lse.float()                                   # what the forward kernel hands the backward
+    O_ = R64._load(o, B, nq, H, DH, HD, c["q_off"])[0]
+    n_kblk, n_qblk = (nk + 63) // 64, (nq + 63) // 64
+    bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, LONG_SCALE, O_, lse, n_kblk=n_kblk)
+    dq, dk, dv = (torch.zeros(r, HD, dtype=torch.float64) for r in (c["rows_q"], c["rows_k"], c["rows_k"]))
+    R64.sdpa_bwd(c["q"], c["k"], c["v"], c["key_mask"], c["do"], lse32.double().reshape(-1), dq, dk, dv, B, H, nq, nk, DH,
+                 *([HD] * 7), LONG_SCALE, **kw)
+    dO = R64._load(c["do"], B, nq, H, DH, HD, c["q_off"])[0]
+    dense = [R64._load(t, B, n, H, DH, HD, off)[0] for t, n, off in ((dq, nq, c["q_off"]), (dk, nk, c["k_off"]), (dv, nk, c["k_off"]))]
+    bb, _ = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, LONG_SCALE, lse32.double(), *dense, n_kblk=n_kblk, n_qblk=n_qblk)
+    exist = valid.any(-1).expand(B, H, nq)
+    return dict(Q=Q, K=K, V=V, dO=dO, O=O_, lse=lse, lse32=lse32, exist=exist, bO=bO, bl=bl, grads=dense, bgrads=bb)
+
+
+def _pad_rows(t, n):
+    return torch.nn.functional.pad(t, (0, 0, 0, n - t.shape[-2]))
+
+
+def _long_masks(c, nkp, fault):
+    """per example: the keys a block treats as attending (mask bit and key < length) over the padded key range, and the dropout
+    keep scale over the padded range"""
+    B, nq, nk = c["B"], c["nq"], c["nk"]
+    ar = torch.arange(nkp)
+    in_len = ar[None, :] < c["len_k"][:, None]
+    bits = torch.ones(B, nkp, dtype=torch.bool)
+    if c["key_mask"] is not None:                         # (key_bits: lanes beyond the capacity read no byte: bit off)
+        bits = torch.nn.functional.pad(c["key_mask"] != 0, (0, nkp - nk))
+    if fault == "mask_bit_read_from_the_neighbouring_block":
+        bits = bits.view(B, nkp // 64, 64).roll(-1, 1).reshape(B, nkp)
+    ok = bits if fault == "key_beyond_nk_in_the_last_partial_block_counted_valid" else bits & in_len
+    keepm = torch.ones(B, H, nq, nkp)
+    if c["p_drop"] > 0:
+        col = ar % 64 if fault == "dropout_column_counter_without_the_block_offset" else ar
+        keepm = keep_scale(c["seed"], torch.arange(B * H * nq).view(B, H, nq, 1), col.view(1, 1, 1, nkp), c["p_drop"])
+    return ok, keepm
+
+
+def flash_fwd_emulate(c, r, fault=None):
+    """sdpa_fwd_flash in fp32: per 64-key block the scores, the running maximum and sum, the accumulators rescaled by
+    exp(m_old - m_new), P~ rounded to bf16 for the PV product; division by the sum and lse = m + log(sum) at the end"""
+    B, nq, nk = c["B"], c["nq"], c["nk"]
+    nb = (nk + 63) // 64
+    Q, K, V = r["Q"].float(), _pad_rows(r["K"].float(), nb * 64), _pad_rows(r["V"].float(), nb * 64)
+    ok, keepm = _long_masks(c, nb * 64, fault)
+    ninf = torch.tensor(-math.inf)
+    mx, sm, acc = torch.full((B, H, nq), -math.inf), torch.zeros(B, H, nq), torch.zeros(B, H, nq, DH)
+    bm = mx
+    for i in range(nb):
+        ks = slice(i * 64, (i + 1) * 64)
+        s = torch.where(ok[:, None, None, ks], (Q @ K[:, :, ks].transpose(-1, -2)) * LONG_SCALE, ninf)
+        bm = s.amax(-1)
+        nm = torch.maximum(mx, bm)
+        corr = torch.where(mx == -math.inf, torch.zeros(()), torch.exp(mx - nm))
+        e = torch.where(s == -math.inf, torch.zeros(()), torch.exp(s - nm[..., None]))
+        pv = bf(e * keepm[..., ks]).float()
+        sm = sm * (1.0 if fault == "running_sum_not_rescaled" else corr) + e.sum(-1)
+        acc = acc * (1.0 if fault == "accumulators_not_rescaled" else corr[..., None]) + pv @ V[:, :, ks]
+        mx = nm
+    inv = torch.where(sm > 0, 1.0 / sm, torch.zeros(()))
+    m_lse = bm if fault == "lse_from_the_last_block_maximum" else mx
+    lse = torch.where(m_lse == -math.inf, torch.zeros(()), m_lse) + torch.log(sm)
+    qv = (torch.arange(nq)[None, :] < c["len_q"][:, None]).view(B, 1, nq, 1)
+    return acc * inv[..., None] * qv, lse
+
+
+def flash_bwd_emulate(c, r, fault=None):
+    """sdpa_bwd_flash_q (two passes over the key blocks: delta, then dQ) and sdpa_bwd_flash_k (one pass over the query blocks with
+    the saved lse and delta) in fp32, dS and P~ rounded to bf16 before their products"""
+    B, nq, nk = c["B"], c["nq"], c["nk"]
+    nkb, nqb = (nk + 63) // 64, (nq + 63) // 64
+    nkp, nqp = nkb * 64, nqb * 64
+    Q, dO = _pad_rows(r["Q"].float(), nqp), _pad_rows(r["dO"].float(), nqp)
+    K, V = _pad_rows(r["K"].float(), nkp), _pad_rows(r["V"].float(), nkp)
+    lse = torch.nn.functional.pad(r["lse32"], (0, nqp - nq))
+    ok_k, keepm = _long_masks(c, nkp, None)
+    keepm = torch.nn.functional.pad(keepm, (0, 0, 0, nqp - nq), value=1.0)
+    ok_q = torch.arange(nqp)[None, :] < c["len_q"][:, None]
+    ok = ok_k[:, None, None, :] & ok_q[:, None, :, None]
+    zero = torch.zeros(())
+    # query side
+    S = Q @ K.transpose(-1, -2)
+    P = torch.where(ok, torch.exp(S * LONG_SCALE - lse[..., None]), zero)
+    dP = (dO @ V.transpose(-1, -2)) * keepm
+    delta = torch.zeros(B, H, nqp)
+    for i in range(nkb):
+        prod = (P * dP)[..., i * 64:(i + 1) * 64]
+        if fault == "delta_not_combined_across_the_half_waves":
+            prod = prod[..., (torch.arange(64) & 4) == 0]            # the keys of the low half-wave's accumulator rows
+        if fault == "delta_covers_the_first_key_block_only" and i > 0:
+            continue
+        delta = delta + prod.sum(-1)
+    dQ = torch.zeros(B, H, nqp, DH)
+    for i in range(nkb):
+        ks = slice(i * 64, (i + 1) * 64)
+        dS = bf(P[..., ks] * (dP[..., ks] - delta[..., None]) * LONG_SCALE).float()
+        dQ = dQ + dS @ K[:, :, ks]
+    # key side
+    dK, dV = torch.zeros(B, H, nkp, DH), torch.zeros(B, H, nkp, DH)
+    for j in range(nqb):
+        qs = slice(j * 64, (j + 1) * 64)
+        okb = ok[:, :, qs]
+        if fault == "dk_dv_miss_the_last_partial_query_block":
+            partial = ((j + 1) * 64 > c["len_q"]) & (c["len_q"] % 64 != 0)
+            okb = okb & ~partial.view(B, 1, 1, 1)
+        arg = S[:, :, qs] * (1.0 if fault == "key_side_p_from_unscaled_scores" else LONG_SCALE) - lse[:, :, qs, None]
+        Pb = torch.where(okb, torch.exp(arg), zero)
+        dPb = dP[:, :, qs]
+        dS = bf(Pb * (dPb - delta[:, :, qs, None]) * LONG_SCALE).float()
+        Pt = bf(Pb * keepm[:, :, qs]).float()
+        dV = dV + Pt.transpose(-1, -2) @ dO[:, :, qs]
+        dK = dK + dS.transpose(-1, -2) @ Q[:, :, qs]
+    return dQ[:, :, :nq], dK[:, :, :nk], dV[:, :, :nk]
+
+
+@pytest.mark.parametrize("kind", ["masked", "packed"])
+@pytest.mark.parametrize("p_drop", [0.1, 0.0], ids=["dropout", "no_dropout"])
+@pytest.mark.parametrize("nq,nk", LONG_SHAPES)
+def test_long_attention_honest_blocked_emulation_passes(nq, nk, p_drop, kind):
+    c = long_case(nq, nk, p_drop, kind)
+    r = long_reference(c)
+    o, lse = flash_fwd_emulate(c, r)
+    BD.check(bf(o), r["O"], r["bO"], "flash fwd O")
+    BD.check(lse[r["exist"]], r["lse"][r["exist"]], r["bl"][r["exist"]], "flash fwd lse")
+    for nm, got, ref, b in zip(("dQ", "dK", "dV"), flash_bwd_emulate(c, r), r["grads"], r["bgrads"]):
+        BD.check(bf(got), ref, b, f"flash bwd {nm}")
+
+
+# fault -> (nq, nk, p_drop, kind, the outputs that must be rejected)
+LONG_FAULTS = {
+    "accumulators_not_rescaled": (128, 128, 0.0, "masked", ("O",)),
+    "running_sum_not_rescaled": (128, 128, 0.0, "masked", ("O", "lse")),
+    "lse_from_the_last_block_maximum": (128, 128, 0.0, "masked", ("lse",)),
+    "dropout_column_counter_without_the_block_offset": (128, 128, 0.1, "masked", ("O",)),
+    "key_beyond_nk_in_the_last_partial_block_counted_valid": (200, 70, 0.0, "packed", ("O", "lse")),
+    "mask_bit_read_from_the_neighbouring_block": (128, 128, 0.0, "masked", ("O", "lse")),
+    "delta_covers_the_first_key_block_only": (128, 128, 0.1, "masked", ("dQ", "dK")),
+    "delta_not_combined_across_the_half_waves": (128, 128, 0.1, "masked", ("dQ", "dK")),
+    "dk_dv_miss_the_last_partial_query_block": (70, 200, 0.1, "masked", ("dK", "dV")),
+    "key_side_p_from_unscaled_scores": (128, 128, 0.1, "masked", ("dK", "dV")),
+}
+
+
+@pytest.mark.parametrize("fault", sorted(LONG_FAULTS))
+def test_long_attention_bounds_reject_blocked_kernel_faults(fault):
+    nq, nk, p_drop, kind, outs = LONG_FAULTS[fault]
+    c = long_case(nq, nk, p_drop, kind)
+    r = long_reference(c)
+    o, lse = flash_fwd_emulate(c, r, fault)
+    dq, dk, dv = flash_bwd_emulate(c, r, fault)
+    ex = r["exist"]
+    got = {"O": (bf(o), r["O"], r["bO"]), "lse": (lse[ex], r["lse"][ex], r["bl"][ex]), "dQ": (bf(dq), r["grads"][0], r["bgrads"][0]),
+           "dK": (bf(dk), r["grads"][1], r["bgrads"][1]), "dV": (bf(dv), r["grads"][2], r["bgrads"][2])}
+    for nm in outs:
+        must_reject(*got[nm], f"{fault}: {nm}")
+    for nm in set(got) - set(outs):          # a fault moves nothing but what it is built into (the emulation stays honest elsewhere)
+        if (nm in ("O", "lse")) != (outs[0] in ("O", "lse")):
+            BD.check(*got[nm], f"{fault}: untouched {nm}")
+
+
+def test_attention_bounds_without_block_counts_are_the_on_chip_bounds_bit_for_bit():
+    """the three bound functions called as before (no block count) and with a count of 1 return what the unchanged formulas,
+    written out here, give -- torch.equal, not a tolerance"""
+    c = attn_case(False, 0.1)
+    o, lse = attn_fwd(R64, c, torch.float64)
+    B, n = c["B"], c["n"]
+    Q, K, V, valid, keep = BD.attention_inputs(R64, c["q"], c["k"], c["v"], c["key_mask"], B, H, n, n, DH, H * DH, H * DH, H * DH,
+                                               c["p_drop"], c["seed"], None, None)
+    O_ = R64._load(o, B, n, H, DH, H * DH, None)[0]
+    L = lse.view(B, H, n)
+    U16, U32, SL, TINY = 2.0 ** -8, 2.0 ** -24, 2.0, 2.0 ** -126
+    s, P, Pk, eS = BD.attention_parts(Q, K, V, valid, keep, 0.125)
+    pv = Pk.abs() @ V.abs()
+    want_O = U16 * O_.abs() + SL * (U16 + 2 * eS + (n + 4) * U32) * pv + TINY
+    want_l = SL * (eS[..., 0] + (n + 4) * U32 + 2 * U32 * L.abs() + 2.0 ** -21)
+    for kw in ({}, {"n_kblk": 1}):
+        bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, 0.125, O_, L, **kw)
+        assert torch.equal(bO, want_O) and torch.equal(bl, want_l)
+    # attn_probs
+    ref = torch.exp(s - L[..., None]).masked_fill(~valid.expand_as(s), 0.0) * keep
+    arg = (s - L[..., None]).abs().masked_fill(~valid.expand_as(s), 0.0).nan_to_num(0.0, posinf=0.0)
+    want_p = U32 * ref.abs() + SL * ref.abs() * (eS + 2 * U32 * arg + (2.0 + 2) * U32) + TINY
+    for kw in ({}, {"n_kblk": 1}):
+        assert torch.equal(BD.attn_probs_bound(Q, K, None, valid.expand_as(s), keep, 0.125, L, ref, **kw), want_p)
+    # backward
+    dO = R64._load(c["do"], B, n, H, DH, H * DH, None)[0]
+    dq, dk, dv = (torch.zeros(c["rows"], H * DH, dtype=torch.float64) for _ in range(3))
+    R64.sdpa_bwd(c["q"], c["k"], c["v"], c["key_mask"], c["do"], lse, dq, dk, dv, B, H, n, n, DH, *([H * DH] * 7), 0.125,
+                 p_drop=c["p_drop"], seed=c["seed"])
+    dense = [R64._load(t, B, n, H, DH, H * DH, None)[0] for t in (dq, dk, dv)]
+    sc = 0.125
+    s0 = (Q @ K.transpose(-1, -2)) * sc
+    Pb = torch.exp(s0 - L[..., None]).masked_fill(~valid, 0.0).nan_to_num(0.0, posinf=0.0)
+    sabs = (Q.abs() @ K.abs().transpose(-1, -2)) * sc
+    eP = DH * U32 * sabs + 2 * U32 + U32 * (s0 - L[..., None]).abs().masked_fill(~valid, 0.0).nan_to_num(0.0, posinf=0.0)
+    dP = (dO @ V.transpose(-1, -2)) * keep
+    edP = DH * U32 * (dO.abs() @ V.abs().transpose(-1, -2)) * keep
+    delta = (Pb * dP).sum(-1, keepdim=True)
+    edelta = (eP * Pb * dP.abs() + Pb * edP).sum(-1, keepdim=True) + n * U32 * (Pb * dP.abs()).sum(-1, keepdim=True)
+    dS = Pb * (dP - delta) * sc
+    edS = sc * (eP * Pb * (dP - delta).abs() + Pb * (edP + edelta)) + 3 * U32 * dS.abs() + U16 * dS.abs()
+    Pk2 = (Pb * keep).abs()
+    tV = (U16 + eP.amax(-2, keepdim=True).transpose(-1, -2) + (n + 2) * U32) * (Pk2.transpose(-1, -2) @ dO.abs())
+    tQ = edS @ K.abs() + n * U32 * (dS.abs() @ K.abs())
+    tK = edS.transpose(-1, -2) @ Q.abs() + n * U32 * (dS.abs().transpose(-1, -2) @ Q.abs())
+    want = [U16 * g.abs() + SL * t + TINY for g, t in zip(dense, (tQ, tK, tV))]
+    for kw in ({}, {"n_kblk": 1, "n_qblk": 1}):
+        bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, 0.125, L, *dense, **kw)
+        assert all(torch.equal(b, w) for b, w in zip(bounds, want))
+        assert all(torch.equal(t, w) for t, w in zip(terms, (tQ, tK, tV)))

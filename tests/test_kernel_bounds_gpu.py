@@ -88,6 +88,32 @@ def gemm_kernel(M, N, K, lda, ldb, A, B, out_f32, epilogue):
     return name
 
 
+def sdpa_kernel(direction, nq, nk, dh, lds, aligned, tr_read=True, dtype=torch.bfloat16, long_mfma=None):
+    """the kernel xl_sdpa_fwd / xl_sdpa_bwd (csrc/sdpa.hip) selects: direction "fwd" or "bwd"; lds the leading dimensions the
+    entry point tests (fwd: q, k, v, o; bwd: those and dq, dk, dv), `aligned` the 16-byte alignment of the pointers it tests (fwd:
+    q, k, v, o; bwd: q, k, v, dout, dq, dk, dv), tr_read the xl_set_lds_transpose_read switch, long_mfma the XL_SDPA_LONG_MFMA
+    environment switch (None: read it).  Returns (name, n_kblk, n_qblk): the block counts the bounds need, 1 on the on-chip kernels.
+      sdpa_*_mfma QFxKF   nq, nk <= 64, bf16, dh 16 / 32 / 64, every ld a multiple of 8, every pointer 16-byte aligned
+      sdpa_*_generic      nq, nk <= 64 otherwise
+      sdpa_*_flash        nq or nk in 65..512, the mfma conditions and the transpose read on (bwd: sdpa_bwd_flash_q + _k)
+      sdpa_*_long         nq or nk in 65..512 otherwise (bwd: sdpa_bwd_long_q + _k)"""
+    assert direction in ("fwd", "bwd")
+    if long_mfma is None:
+        import os
+        e = os.environ.get("XL_SDPA_LONG_MFMA")
+        long_mfma = e is None or (e.strip().lstrip("+-").isdigit() and int(e) != 0)
+    mfma = dtype == torch.bfloat16 and dh in (16, 32, 64) and all(ld % 8 == 0 for ld in lds) and all(bool(x) for x in aligned)
+    if nq > 64 or nk > 64:
+        name = f"sdpa_{direction}_flash" if (mfma and tr_read and long_mfma) else f"sdpa_{direction}_long"
+        return name, (nk + 63) // 64, (nq + 63) // 64
+    if mfma:
+        return f"sdpa_{direction}_mfma {(nq + 31) // 32}x{(nk + 31) // 32}", 1, 1
+    return f"sdpa_{direction}_generic", 1, 1
+
+
+SDPA_KERNELS = tuple(f"sdpa_{d}_{k}" for d in ("fwd", "bwd") for k in ("mfma", "flash", "long", "generic"))
+
+
 class Recorder:
     """stands in for the step's HipOps: forwards every attribute, checks the first call of each signature"""
 
@@ -111,6 +137,8 @@ class Recorder:
         object.__setattr__(self, "_cur", None)
         object.__setattr__(self, "ncalls", {})          # (step tag, method) -> number of calls
         object.__setattr__(self, "checked", [])         # (method, {argument: scalar value / None / "T" for a tensor}) of every checked call
+        object.__setattr__(self, "_tr_read", True)      # xl_set_lds_transpose_read (library default 1): part of the attention dispatch
+        object.__setattr__(self, "lse_excluded", [])    # (method, shape, number of lse entries left out: queries without a valid key)
 
     def mark(self, tag):
         object.__setattr__(self, "_tag", tag)
@@ -146,6 +174,11 @@ class Recorder:
                 object.__setattr__(self, "_deferred", bool(on))
                 return attr(on)
             return fwd_defer
+        if name == "set_lds_transpose_read":
+            def fwd_tr(enable):
+                object.__setattr__(self, "_tr_read", bool(enable))
+                return attr(enable)
+            return fwd_tr
         if name in ("flush_reductions", "flush_reductions_on"):
             return lambda *args: self._flush(name, attr, args)
         if name in NON_NUMERIC or _is_setter(name):
@@ -168,6 +201,10 @@ class Recorder:
             ba.apply_defaults()
             a = dict(ba.arguments)
             key = self._signature(name, a)
+            if name in ("sdpa_fwd", "sdpa_bwd"):      # a call that changes kernel (a switch, an alignment) is checked again
+                key += (("kernel", self._sdpa_kernel(name[5:], a)[0]),)
+            elif name == "attn_probs":
+                key += (("kernel", "attn_probs_kernel"), ("n_kblk", (a["nk"] + 63) // 64))
             if name in STEP_KEYED or (name == "gemm" and a["epilogue"] == BD.EPI_ROWMAX):
                 key += (("step", self._tag),)
             dests = self._dests(name, a) if self._deferred else []
@@ -197,7 +234,8 @@ class Recorder:
                 print(f"FAILED {self.failures[-1]}", flush=True)
                 return None
             self._note_dests(dests, True, key)
-            self.checked.append((name, {k: ("T" if isinstance(v, (torch.Tensor, list, tuple)) else v) for k, v in a.items()}))
+            self.checked.append((name, dict({k: ("T" if isinstance(v, (torch.Tensor, list, tuple)) else v) for k, v in a.items()},
+                                            _kernel=res[0][2] if res else None)))
             for what, ratio, kernel in res:
                 self.rows.append((name, what, self._short(a), kernel, ratio))
             print(f"checked {name} {self._short(a)}" + (f" step={self._tag}" if key[-1][0] == "step" else ""), flush=True)
@@ -456,7 +494,8 @@ class Recorder:
         run()
         self._ref.attn_probs(**s)
         ref = s["probs"].reshape(-1)[:B * H * nq * nk].view(B, H, nq, nk)
-        bound = BD.attn_probs_bound(Q, K, None, valid.expand(B, H, nq, nk), keep, a["scale"], lse, ref)
+        n_kblk = (nk + 63) // 64
+        bound = BD.attn_probs_bound(Q, K, None, valid.expand(B, H, nq, nk), keep, a["scale"], lse, ref, n_kblk=n_kblk)
         kern = f"attn_probs_kernel{' + dropout' if a['p_drop'] > 0 else ''}{' packed' if a['q_off'] is not None or a['k_off'] is not None else ''}"
         return [("probs", BD.check(a["probs"].reshape(-1)[:B * H * nq * nk].view(B, H, nq, nk), ref, bound, "attn_probs"), kern)]
 
@@ -485,6 +524,21 @@ class Recorder:
         return BD.attention_inputs(self._ref, s["q"], s["k"], s["v"], s["key_mask"], a["B"], a["H"], a["nq"], a["nk"], a["dh"],
                                    a["ldq"], a["ldk"], a["ldv"], a["p_drop"], a["seed"], s["q_off"], s["k_off"])
 
+    def _sdpa_kernel(self, direction, a):
+        """sdpa_kernel(...) of a call's arguments: (label with the dropout / keep_bits / packed suffixes, n_kblk, n_qblk)"""
+        lds = [a[k] for k in ("ldq", "ldk", "ldv", "ldo")]
+        ptrs = [a[k] for k in ("q", "k", "v")]
+        if direction == "fwd":
+            ptrs.append(a["o"])
+        else:
+            lds += [a[k] for k in ("lddq", "lddk", "lddv")]
+            ptrs += [a[k] for k in ("dout", "dq", "dk", "dv")]
+        name, n_kblk, n_qblk = sdpa_kernel(direction, a["nq"], a["nk"], a["dh"], lds, [_al16(t) for t in ptrs], self._tr_read,
+                                           a["q"].dtype)
+        name += f"{' + dropout' if a['p_drop'] > 0 else ''}{' keep_bits' if a.get('keep_bits') is not None else ''}" \
+                f"{' packed' if a['q_off'] is not None or a['k_off'] is not None else ''}"
+        return name, n_kblk, n_qblk
+
     def chk_sdpa_fwd(self, a, s, run):
         B, H, nq, nk, dh = a["B"], a["H"], a["nq"], a["nk"], a["dh"]
         Q, K, V, valid, keep = self._att(s, a)
@@ -495,12 +549,13 @@ class Recorder:
         BD.attention_rows(self._ref, s["o"], B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"]).nan_to_num_(0.0)
         O_, _ = self._ref._load(s["o"], B, nq, H, dh, a["ldo"], s["q_off"])
         lse = s["lse"].reshape(-1)[:B * H * nq].view(B, H, nq)
-        bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, a["scale"], O_, lse)
+        kern, n_kblk, _ = self._sdpa_kernel("fwd", a)
+        bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, a["scale"], O_, lse, n_kblk=n_kblk)
         rows = lambda t: BD.attention_rows(self._ref, t, B, nq, H, dh, a["ldo"], a["q_off"], a["q_pad"])   # noqa: E731
         ref_rows = BD.attention_rows(self._ref, s["o"], B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"])
         bO = BD.attention_scatter(self._ref, bO, B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"])[:ref_rows.shape[0]]
-        exist = valid.any(-1).expand(B, H, nq)
-        kern = f"sdpa_fwd_mfma{' + dropout' if a['p_drop'] > 0 else ''}{' packed' if a['q_off'] is not None else ''}"
+        exist = valid.any(-1).expand(B, H, nq)       # (the only elements left out of a comparison: the lse of a query without a key)
+        self.lse_excluded.append(("sdpa_fwd", self._short(a), int((~exist).sum())))
         got_l = a["lse"].reshape(-1)[:B * H * nq].view(B, H, nq)
         return [("O", BD.check(rows(a["o"]), ref_rows, bO, "sdpa_fwd O"), kern),
                 ("lse", BD.check(got_l[exist], lse[exist], bl[exist], "sdpa_fwd lse"), kern)]
@@ -515,9 +570,12 @@ class Recorder:
         self._ref.sdpa_bwd(**s)
         sides = (("dq", nq, "lddq", "q_off", "q_pad"), ("dk", nk, "lddk", "k_off", "k_pad"), ("dv", nk, "lddv", "k_off", "k_pad"))
         dense = [self._ref._load(s[nm], B, n, H, dh, a[ld], s[off])[0] for nm, n, ld, off, _ in sides]
-        bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, a["scale"], lse, *dense)
-        kern = f"sdpa_bwd_mfma{' + dropout' if a['p_drop'] > 0 else ''}{' keep_bits' if a['keep_bits'] is not None else ''}" \
-               f"{' packed' if a['q_off'] is not None else ''}"
+        kern, n_kblk, n_qblk = self._sdpa_kernel("bwd", a)
+        bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, a["scale"], lse, *dense, n_kblk=n_kblk, n_qblk=n_qblk)
+        # the long and the generic kernels have no fused partials: their bias gradients are xl_colsum of the STORED dq / dk / dv
+        # (bf16-rounded), so each element enters the sum with its whole bound: bounds.colsum_bound.  The on-chip MFMA kernel keeps
+        # the bound it has always been held to (fused fp32 partials: no rounding of the summands).
+        stored_sums = not kern.startswith("sdpa_bwd_mfma")
         res = []
         HD = H * dh
         for (nm, n, ld, off, pad), b, t in zip(sides, bounds, terms):
@@ -529,6 +587,10 @@ class Recorder:
                 i = "dq dk dv".split().index(nm)
                 tt = BD.attention_scatter(self._ref, t, B, n, H, dh, a[ld], s[off], a[pad])[:ref_rows.shape[0]]
                 ref_b = s["bias_grad"][i * HD:(i + 1) * HD]
+                if stored_sums:
+                    bnd = BD.colsum_bound(bb, ref_rows, bias_prev[i * HD:(i + 1) * HD]) + BD.U32 * ref_b.abs()
+                    self._sum_out(res, f"bias {nm}", a["bias_grad"][i * HD:(i + 1) * HD], ref_b, bias_prev[i * HD:(i + 1) * HD], bnd, kern)
+                    continue
                 bnd = BD.SLACK * tt.sum(0) + BD.SLACK * (ref_rows.shape[0] + 1) * BD.U32 * (ref_rows.abs().sum(0)
                                                                                         + bias_prev[i * HD:(i + 1) * HD].abs()) \
                     + BD.U32 * ref_b.abs() + BD.TINY
