@@ -101,6 +101,22 @@ class FakeOps:
     def set_lds_transpose_read(self, enable):
         pass
 
+    # the kernel-choice switches of xl_gemm: no kernel to choose here
+    def set_gemm_pingpong(self, mode):
+        pass
+
+    def set_gemm_duo(self, mode):
+        pass
+
+    def set_gemm_wgrad_slabs(self, on):
+        pass
+
+    def set_gemm_tail_split(self, max_tail_tiles, min_k):
+        pass
+
+    def gemm_workspace(self, slabs=256, stream=None):
+        return None
+
     def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1,
              out_f32=False, epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
         self.calls.append(("gemm", M, N, K, a_kmajor, b_kmajor, epilogue))

@@ -916,3 +916,106 @@ def test_attention_bounds_without_block_counts_are_the_on_chip_bounds_bit_for_bi
         bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, 0.125, L, *dense, **kw)
         assert all(torch.equal(b, w) for b, w in zip(bounds, want))
         assert all(torch.equal(t, w) for t, w in zip(terms, (tQ, tK, tV)))
+
+
+# ------------------------------------------------------------------------------------------------------------------ GEMM dispatch edges
+# tests/test_gemm_edges_bounds_gpu.py over the host restatement: the same calls (tests/gemm_edge_cases.py), the same recorder, the
+# same label assertions.  The tail-split shape is the GPU test's own (4300, 4090, 1096), no stand-in: a few seconds of host float64.
+GEMM_EDGE_RUNS = {
+    **{f"shapes-{sw}": ("run_shapes", (sw,)) for sw in ("default", "pingpong_forced", "mfma_128_only", "transpose_read_off")},
+    **{f"epilogues-{sw}": ("run_epilogues", (sw,)) for sw in ("default", "pingpong_forced", "mfma_128_only", "transpose_read_off")},
+    **{f"colsums-{sw}": ("run_colsums", (sw,)) for sw in ("default", "pingpong_forced")},
+    **{f"ksplits-{sw}-{'slabs' if sl else 'atomics'}": ("run_ksplits", (sw, sl)) for sw in ("default", "pingpong_forced")
+       for sl in (False, True)},
+    "tail_split": ("run_tail_split", ()), "duo": ("run_duo", ()),
+    "wgrad_groups-atomics": ("run_wgrad_groups", (False,)), "wgrad_groups-slabs": ("run_wgrad_groups", (True,))}
+
+
+@pytest.mark.parametrize("run", list(GEMM_EDGE_RUNS))
+def test_gemm_edge_cases_pass_over_the_host_restatement(run):
+    """an honest implementation (fp32 arithmetic on bf16 storage that reads the logical extents only and stores into the logical
+    views only) is inside every bound at the inputs of the edge cases, guard rows included, and the sweep reaches the kernel labels
+    the GPU tests expect"""
+    import test_gemm_edges_bounds_gpu as G
+    fn, args = GEMM_EDGE_RUNS[run]
+    getattr(G, fn)(*args, ops=FakeOps(torch.bfloat16), dev="cpu")
+
+
+class FaultyOps(FakeOps):
+    """the host restatement with ONE kernel fault, applied at every call it can apply to:
+      m_major_lost_term   the last row of an M-major A (last column of an N-major B) loses its final K term
+      pad_as_k_term       the pad element behind the last row of a K-major A enters as one more K term
+      short_slice_dropped the last, short K slice of a K split is dropped (K no multiple of 64: the K % 64 tail and what the
+                          rounded slice leaves)
+      stale_edge_tile     accumulate = 0 leaves the old C in the edge tile (the clearing pass stops at the last whole 128 x 128 tile)
+      store_in_pad_column one store lands in C[0, N]
+      store_in_row_m      one store lands in row M of a taller allocation
+      overwrite_ignored   the overwrite bit of grouped problem 0 is ignored"""
+
+    def __init__(self, fault):
+        super().__init__(torch.bfloat16)
+        self.fault, self.applied = fault, 0
+
+    def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1, out_f32=False,
+             epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
+        f = self.fault
+        kw = dict(ldr=ldr, ldx=ldx, a_kmajor=a_kmajor, b_kmajor=b_kmajor, out_f32=out_f32, epilogue=epilogue, alpha=alpha,
+                  accumulate=accumulate, p_drop=p_drop, seed=seed, colsum=colsum, ws=ws)
+        old = torch.as_strided(C, (M, N), (ldc, 1)).clone()
+        if f == "m_major_lost_term" and not (a_kmajor and b_kmajor) and K > 1:
+            if not a_kmajor:
+                A = A.clone()
+                A[(K - 1) * lda + M - 1] = 0
+            else:
+                B = B.clone()
+                B[(K - 1) * ldb + N - 1] = 0
+            self.applied += 1
+        if f == "short_slice_dropped" and out_f32 and epilogue == EPI_NONE and K >= 1024 and K % 512:
+            K -= K % 512 if K % 512 < 256 else K % 64
+            self.applied += 1
+        super().gemm(A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, **kw)
+        c = torch.as_strided(C, (M, N), (ldc, 1))
+        if f == "pad_as_k_term" and a_kmajor and lda > K and epilogue == EPI_NONE and not accumulate:
+            b_last = (torch.as_strided(B, (N,), (ldb,), B.storage_offset() + K - 1) if b_kmajor
+                      else torch.as_strided(B, (N,), (1,), B.storage_offset() + (K - 1) * ldb))
+            c[M - 1] = (c[M - 1].double() + alpha * float(A[(M - 1) * lda + K]) * b_last.double()).to(c.dtype)
+            self.applied += 1
+        if f == "stale_edge_tile" and out_f32 and not accumulate and (M % 128 or N % 128):
+            c[M - M % 128:, N - N % 128:] += old[M - M % 128:, N - N % 128:]
+            self.applied += 1
+        if f == "store_in_pad_column" and ldc > N:
+            C[N] = 0
+            self.applied += 1
+        if f == "store_in_row_m" and C.numel() > M * ldc:
+            C[M * ldc] = 0
+            self.applied += 1
+
+    def gemm_wgrad_group(self, problems, overwrite_mask=0):
+        if self.fault == "overwrite_ignored" and overwrite_mask & 1:
+            overwrite_mask &= ~1
+            self.applied += 1
+        super().gemm_wgrad_group(problems, overwrite_mask)
+
+
+@pytest.mark.parametrize("fault,family", [("m_major_lost_term", "shapes"), ("pad_as_k_term", "shapes"), ("short_slice_dropped", "ksplits"),
+                                          ("stale_edge_tile", "ksplits"), ("store_in_pad_column", "shapes"), ("store_in_row_m", "shapes"),
+                                          ("overwrite_ignored", "wgrad_groups")])
+def test_gemm_edge_cases_reject_plausible_kernel_faults(fault, family):
+    """the same recorder run as the honest pass, over an implementation with one fault: it must fail, at EVERY call the fault
+    applied to (each such call shows the fault on its own: none hides behind another's failure)"""
+    import gemm_edge_cases as GE
+    from test_kernel_bounds_gpu import Recorder
+    ops = FaultyOps(fault)
+    rec = Recorder(ops)
+    g = torch.Generator().manual_seed(101)
+    if family == "shapes":
+        n = GE.shapes(rec, "cpu", g, shapes_=GE.SHAPES[3:9], f32_shapes=GE.F32_SHAPES[1:3])
+    elif family == "ksplits":
+        n = GE.ksplits(rec, "cpu", g, mn=GE.KSPLIT_MN[:1])
+    else:
+        n = GE.wgrad_groups(rec, "cpu", g, Ks=(72, 4104))
+    assert len(rec.checked) + len(rec.failures) == n and ops.applied > 0
+    print(f"{fault}: applied at {ops.applied} of {n} calls, {len(rec.failures)} failed")
+    assert len(rec.failures) == ops.applied, (fault, ops.applied, len(rec.failures), rec.failures[:3])
+    word = {"store_in_pad_column": "outside", "store_in_row_m": "outside"}.get(fault, "beyond their bound")
+    assert all(word in f for f in rec.failures), rec.failures[:3]

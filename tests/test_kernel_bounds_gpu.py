@@ -11,6 +11,14 @@ not final at its own call: the recorder keeps, per producing stream, a pending l
 bound) and checks every destination when flush_reductions / flush_reductions_on combines that stream; a pending entry that no
 flush covers, or a destination that also received an unrecorded contribution, fails the test (Recorder.leftover()).
 
+Stray stores.  Around every gemm / gemm_wgrad_group call the whole storage of every output (C, a written aux, the column-sum
+target) is held bit for bit -- as integers -- to its content before the call everywhere outside the logical views the call may
+write: the row "C outside view".  A store into a pad column of C or past row M-1 lands in a neighbouring tensor.
+
+Kernel labels.  The recorder remembers the GEMM switches it forwards (set_gemm_pingpong / _duo / _wgrad_slabs / _tail_split,
+set_lds_transpose_read, the slab workspace registered per stream); gemm_kernel / wgrad_group_kernel restate the dispatch of
+csrc/gemm.hip under them, and the label is part of a call's signature: the same arguments after a switch change are checked again.
+
 What the proxy switches off.  PretrainStep gates four paths on isinstance(self.ops, HipOps) (trainer.py): (1) a separate bf16
 HipOps for a bf16 gradient exchange and (2) the library's RCCL binding -- both only with more than one rank, no numeric call of
 a one-GPU step; (3) plan mode -- a recorded launch plan replays the same C-ABI calls without passing through Python, so these
@@ -65,27 +73,131 @@ def _v2(t, r, c, ld):
     return torch.as_strided(t, (r, c), (ld, 1))
 
 
-def gemm_kernel(M, N, K, lda, ldb, A, B, out_f32, epilogue):
-    """the kernel xl_gemm's dispatch (csrc/gemm.hip, default switches) selects for these arguments"""
-    mfma = A.dtype == torch.bfloat16 and lda % 8 == 0 and ldb % 8 == 0 and _al16(A) and _al16(B)
-    if not mfma:
-        return "generic 64x64"
-    may_split = out_f32 and epilogue == BD.EPI_NONE
+# the xl_gemm switches of a library context and their library defaults (csrc/common.h Ctx; the XL_GEMM_* environment variables
+# give the initial values): what Recorder remembers of the setters it forwards, and what gemm_kernel reads
+def gemm_switches():
+    import os
+    e = lambda k, d: int(os.environ.get(k, d))                  # noqa: E731
+    return dict(pingpong=e("XL_GEMM_PP", 1), tr_read=True, duo=e("XL_GEMM_DUO", 1), slabs=e("XL_GEMM_WGRAD_SLABS", 0),
+                tail_max=e("XL_GEMM_TAIL_MAX", 64), tail_min_k=e("XL_GEMM_TAIL_MIN_K", 4096), ws_slabs=0)
+
+
+def _ws_holds(sw, tiles, slabs):
+    """slab_workspace(): the stream has a registered workspace with 4096 tickets in front of `ws_slabs` slabs"""
+    return sw["ws_slabs"] > 0 and tiles * 4 <= 16384 and slabs <= sw["ws_slabs"]
+
+
+def gemm_vec_epi(C, ldc, out_f32, epilogue, residual=None, ldr=0, aux=None, ldx=0):
+    """p.vec_epi of xl_gemm: 16-byte rows of C and of the epilogue's operand"""
+    v = bool(_al16(C)) and (ldc % 4 == 0 if out_f32 else ldc % 8 == 0)
+    if epilogue == BD.EPI_RESIDUAL:
+        v = v and bool(_al16(residual)) and (ldr % 4 == 0 if residual.dtype == torch.float32 else ldr % 8 == 0)
+    if epilogue in (BD.EPI_GELU, BD.EPI_DGELU, BD.EPI_GELU_DG, BD.EPI_MULAUX):
+        v = v and bool(_al16(aux)) and ldx % 8 == 0
+    return v
+
+
+def gemm_kernel(M, N, K, lda, ldb, A, B, out_f32, epilogue, a_kmajor=1, b_kmajor=1, accumulate=0, vec_epi=True, bias_al16=True,
+                colsum=False, res32=False, sw=None):
+    """the kernel xl_gemm's dispatch (csrc/gemm.hip) selects for these arguments under the switches `sw` (gemm_switches(): the
+    library defaults):
+      generic 64x64         operands the MFMA loader does not take (fp32, a leading dimension off 8, a pointer off 16 bytes)
+      ping-pong 256x256     pingpong 2, or 1 and >= 48 tiles of 256x256 (x K splits); needs the LDS transpose read and K % 8 == 0
+      duo 128x192           forward / dX layouts, M % 128 == N % 192 == 0, a fast epilogue; duo 1: at most 64 tiles of 256x256
+      MFMA 128x128          otherwise (" plain LDS read": the instance without the transpose read)
+    suffixes: " split-K S atomics" / " split-K S slabs" (fp32 out, EPI_NONE, K >= 1024, too few tiles; slabs: the ping-pong kernel
+    with set_gemm_wgrad_slabs and a registered workspace), " += atomics" (accumulate without a split), " + tail split RxS",
+    " + scalar epilogue" (vec_epi == 0: every element through the scalar store), " + generic epilogue" (aligned rows but no
+    templated epilogue -- template argument EPIK = -1: TANH, an unaligned bias, GELU_DG with b_kmajor = 0, MULAUX with b_kmajor = 1,
+    every launch with a_kmajor = 0, the instance without the transpose read), " + scalar edge epilogue" (a templated epilogue whose
+    ragged edge tiles take the scalar store), " + fused colsum" / " + separate colsum".  Held against the kernel names of a
+    rocprofv3 --kernel-trace run of tests/test_gemm_edges_bounds_gpu.py once: profiles/bounds_gemm_edges.txt."""
+    sw = dict(gemm_switches(), **(sw or {}))
+    mfma = A.dtype == torch.bfloat16 and lda % 8 == 0 and ldb % 8 == 0 and bool(_al16(A)) and bool(_al16(B))
+    may_split = mfma and out_f32 and epilogue == BD.EPI_NONE
     t256 = ((M + 255) // 256) * ((N + 255) // 256)
+    pp_ok = mfma and sw["tr_read"] and K % 8 == 0 and (M if a_kmajor else K) * lda < 1e9 and (N if b_kmajor else K) * ldb < 1e9
     blocks = t256 * max(1, min(256 // t256, K // 512)) if (may_split and t256 < 256 and K >= 1024) else t256
-    pp = K % 8 == 0 and blocks >= 48
-    tile = 256 if pp else 128
+    pp = pp_ok and (sw["pingpong"] == 2 or (sw["pingpong"] == 1 and blocks >= 48))
+    tile = 256 if pp else 128 if mfma else 64
     tiles = ((M + tile - 1) // tile) * ((N + tile - 1) // tile)
     want = 256 if pp else 768
-    split = max(1, min(want // tiles if pp else (want + tiles - 1) // tiles, K // 512)) if (may_split and tiles < want and K >= 1024) else 1
-    name = "ping-pong 256x256" if pp else "MFMA 128x128 / duo 128x192"
+    split = 1
+    if may_split and tiles < want and K >= 1024:
+        split = max(1, min(want // tiles if pp else (want + tiles - 1) // tiles, K // 512))
+    kstep = 64 if mfma else 16
+    kper = ((K + split - 1) // split + kstep - 1) // kstep * kstep
+    split = (K + kper - 1) // kper
+    atomic = bool(accumulate) or split > 1
+    slabs = pp and split > 1 and sw["slabs"] and _ws_holds(sw, tiles, tiles * split)
+    epik = epilogue if (vec_epi and not atomic and epilogue != BD.EPI_TANH and bias_al16) else -1
+    if (epilogue == BD.EPI_GELU_DG and not b_kmajor) or (epilogue == BD.EPI_MULAUX and b_kmajor):
+        epik = -1
+    duo = bool(pp_ok and sw["pingpong"] and sw["duo"] and a_kmajor and M % 128 == 0 and N % 192 == 0 and (not out_f32 or res32)
+               and not accumulate and epik >= 0 and not colsum and epilogue != BD.EPI_TANH and split == 1
+               and M * lda < 1e9 and (sw["duo"] == 2 or t256 <= 64))
+    if not mfma:
+        name = "generic 64x64"
+    elif duo:
+        name, tile = "duo 128x192", None
+    elif pp:
+        name = "ping-pong 256x256"
+    else:
+        name = "MFMA 128x128" + ("" if sw["tr_read"] else " plain LDS read")
     if split > 1:
-        name += f" split-K {split}"
-    if pp and K >= 4096 and not may_split:
-        name += " (tail split eligible)"
-    if (M % tile or N % tile):
-        name += " + scalar edge epilogue"
+        name += f" split-K {split} " + ("slabs" if slabs else "atomics")
+    elif accumulate:
+        name += " += atomics"
+    if pp and not duo and split == 1 and not atomic and tiles > 256 and 0 < tiles % 256 <= sw["tail_max"] and K >= sw["tail_min_k"]:
+        rem = tiles % 256
+        S = min(256 // rem, K // 512, 8)
+        if S >= 2:
+            kper_t = ((K + S - 1) // S + 63) // 64 * 64
+            S = (K + kper_t - 1) // kper_t
+            if S >= 2 and _ws_holds(sw, rem, rem * S):
+                name += f" + tail split {rem}x{S}"
+    ragged = tile is not None and (M % tile or N % tile)
+    if mfma and not atomic:
+        if not vec_epi:
+            name += " + scalar epilogue"
+        elif epik < 0 or not a_kmajor or (not sw["tr_read"] and not pp):
+            name += " + generic epilogue"
+        elif ragged:
+            name += " + scalar edge epilogue"
+    if colsum:
+        fused = mfma and epik >= 0 and split == 1 and a_kmajor and M % tile == 0 and N % tile == 0
+        name += " + fused colsum" if fused else " + separate colsum"
     return name
+
+
+def wgrad_group_kernel(problems, overwrite_mask=0, sw=None):
+    """xl_gemm_wgrad_group (csrc/gemm.hip): problems of (A, B, C, M, N, K, lda, ldb, ldc).  One launch of the grouped ping-pong
+    kernel when every member is bf16 with 16-byte rows and K % 8 == 0, there is more than one, the ping-pong family and the transpose
+    read are on and the launch puts up >= 96 workgroups; otherwise one xl_gemm per member.  -> (label of the launch, [label per
+    member])"""
+    sw = dict(gemm_switches(), **(sw or {}))
+    grouped = len(problems) > 1 and sw["pingpong"] != 0 and sw["tr_read"]
+    total, max_split = 0, 1 << 20
+    for A, B, C, M, N, K, lda, ldb, ldc in problems:
+        grouped = grouped and A.dtype == torch.bfloat16 and lda % 8 == 0 and ldb % 8 == 0 and bool(_al16(A)) and bool(_al16(B)) \
+            and K % 8 == 0 and K * lda < 1e9 and K * ldb < 1e9
+        total += ((M + 255) // 256) * ((N + 255) // 256)
+        max_split = min(max_split, max(1, K // 512))
+    split = 1 if total >= 256 else max(1, min(256 // total, max_split))
+    if grouped and total * split < 96:
+        grouped = False
+    if not grouped:
+        return "ungrouped: one xl_gemm per member", ["ungrouped " + gemm_kernel(M, N, K, lda, ldb, A, B, True, BD.EPI_NONE, 0, 0,
+                                                        accumulate=0 if (overwrite_mask >> i) & 1 else 1,
+                                                        vec_epi=gemm_vec_epi(C, ldc, True, BD.EPI_NONE), sw=sw)
+                             for i, (A, B, C, M, N, K, lda, ldb, ldc) in enumerate(problems)]
+    ranges = [(C.data_ptr(), C.data_ptr() + ((M - 1) * ldc + N) * 4) for _, _, C, M, N, _, _, _, ldc in problems]
+    disjoint = all(not (a0 < b1 and b0 < a1) for i, (a0, a1) in enumerate(ranges) for b0, b1 in ranges[i + 1:])
+    slabs = disjoint and sw["slabs"] and _ws_holds(sw, total, total * split)
+    how = "slabs" if slabs else "one writer per tile" if (disjoint and split == 1) else "atomics"
+    name = f"grouped ping-pong 256x256 split-K {split} {how}" if split > 1 else f"grouped ping-pong 256x256 {how}"
+    return name, [name + (" + scalar edge epilogue" if (M % 256 or N % 256 or not (_al16(C) and ldc % 4 == 0)) else "")
+                  for _, _, C, M, N, _, _, _, ldc in problems]
 
 
 def sdpa_kernel(direction, nq, nk, dh, lds, aligned, tr_read=True, dtype=torch.bfloat16, long_mfma=None):
@@ -138,6 +250,8 @@ class Recorder:
         object.__setattr__(self, "ncalls", {})          # (step tag, method) -> number of calls
         object.__setattr__(self, "checked", [])         # (method, {argument: scalar value / None / "T" for a tensor}) of every checked call
         object.__setattr__(self, "_tr_read", True)      # xl_set_lds_transpose_read (library default 1): part of the attention dispatch
+        object.__setattr__(self, "_sw", gemm_switches())   # the xl_gemm switches forwarded so far: part of the GEMM dispatch
+        object.__setattr__(self, "_ws_slabs", {})       # stream -> slabs of the workspace registered on it (gemm_workspace)
         object.__setattr__(self, "lse_excluded", [])    # (method, shape, number of lse entries left out: queries without a valid key)
 
     def mark(self, tag):
@@ -177,8 +291,24 @@ class Recorder:
         if name == "set_lds_transpose_read":
             def fwd_tr(enable):
                 object.__setattr__(self, "_tr_read", bool(enable))
+                self._sw["tr_read"] = bool(enable)
                 return attr(enable)
             return fwd_tr
+        if name in ("set_gemm_pingpong", "set_gemm_duo", "set_gemm_wgrad_slabs"):
+            def fwd_sw(v):
+                self._sw[{"set_gemm_pingpong": "pingpong", "set_gemm_duo": "duo", "set_gemm_wgrad_slabs": "slabs"}[name]] = int(v)
+                return attr(v)
+            return fwd_sw
+        if name == "set_gemm_tail_split":
+            def fwd_tail(max_tail_tiles, min_k):
+                self._sw["tail_max"], self._sw["tail_min_k"] = int(max_tail_tiles), int(min_k)
+                return attr(max_tail_tiles, min_k)
+            return fwd_tail
+        if name == "gemm_workspace":
+            def fwd_ws(slabs=256, stream=None):
+                self._ws_slabs[stream.cuda_stream if stream is not None else self._stream_key()] = int(slabs)
+                return attr(slabs, stream)
+            return fwd_ws
         if name in ("flush_reductions", "flush_reductions_on"):
             return lambda *args: self._flush(name, attr, args)
         if name in NON_NUMERIC or _is_setter(name):
@@ -205,6 +335,10 @@ class Recorder:
                 key += (("kernel", self._sdpa_kernel(name[5:], a)[0]),)
             elif name == "attn_probs":
                 key += (("kernel", "attn_probs_kernel"), ("n_kblk", (a["nk"] + 63) // 64))
+            elif name == "gemm" and a["epilogue"] != BD.EPI_ROWMAX:     # (the same for the GEMM switches and leading dimensions)
+                key += (("kernel", self._gemm_kernel(a)),)
+            elif name == "gemm_wgrad_group":
+                key += (("kernel", tuple(wgrad_group_kernel(a["problems"], a["overwrite_mask"], self._switches())[1])),)
             if name in STEP_KEYED or (name == "gemm" and a["epilogue"] == BD.EPI_ROWMAX):
                 key += (("step", self._tag),)
             dests = self._dests(name, a) if self._deferred else []
@@ -364,10 +498,56 @@ class Recorder:
             pre, absprod = pre + b[None, :], absprod + b.abs()[None, :]
         return pre, absprod
 
+    def _switches(self):
+        """the forwarded switches with the slab workspace of the CURRENT stream (where the next call is queued)"""
+        return dict(self._sw, ws_slabs=self._ws_slabs.get(self._stream_key(), 0))
+
+    def _gemm_kernel(self, a):
+        epi = a["epilogue"]
+        res32 = epi == BD.EPI_RESIDUAL and a["residual"] is not None and a["residual"].dtype == torch.float32 \
+            and a["A"].dtype == torch.bfloat16
+        return gemm_kernel(a["M"], a["N"], a["K"], a["lda"], a["ldb"], a["A"], a["B"], a["out_f32"], epi, a["a_kmajor"], a["b_kmajor"],
+                           a["accumulate"], gemm_vec_epi(a["C"], a["ldc"], a["out_f32"], epi, a["residual"], a["ldr"], a["aux"], a["ldx"]),
+                           a["bias"] is None or bool(_al16(a["bias"])), a["colsum"] is not None, res32, self._switches())
+
+    # -- stray stores: everything an output's storage holds OUTSIDE the logical views the call may write stays bit-identical
+    @staticmethod
+    def _raw(t):
+        """the whole storage of t as integers of its element size (a view: bit patterns, so that NaN sentinels compare)"""
+        st = t.untyped_storage()
+        it = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]
+        return torch.tensor([], dtype=it, device=t.device).set_(st, 0, (st.nbytes() // t.element_size(),), (1,))
+
+    def _guard(self, outs):
+        """outs: [(tensor, shape, stride)] -- the logical views this call may write (strides in elements of the tensor's type, from
+        its storage offset).  Snapshots the bit patterns of every storage involved; the returned function, called after the run,
+        holds every element outside all the views to its earlier bits and returns the result row."""
+        groups = {}
+        for t, shape, stride in outs:
+            groups.setdefault((t.untyped_storage().data_ptr(), t.element_size()), []).append((t, shape, stride))
+        before = {k: self._raw(v[0][0]).clone() for k, v in groups.items()}
+
+        def after(kern):
+            for k, views in groups.items():
+                now, was = self._raw(views[0][0]), before[k]
+                for t, shape, stride in views:          # inside the views: whatever the call wrote
+                    torch.as_strided(was, shape, stride, t.storage_offset()).copy_(torch.as_strided(now, shape, stride, t.storage_offset()))
+                BD.check_exact(now, was, f"{self._cur[0]} stores outside the [M, N] views of its outputs (storage of {len(now)} elements)")
+            return ("C outside view", 0.0, kern)
+        return after
+
     def chk_gemm(self, a, s, run):
         M, N, K, epi = a["M"], a["N"], a["K"], a["epilogue"]
         if epi == BD.EPI_ROWMAX:
             return self._chk_gemm_rowmax(a, s, run)
+        outs = [(a["C"], (M, N), (a["ldc"], 1))]
+        if epi in (BD.EPI_GELU, BD.EPI_GELU_DG):
+            outs.append((a["aux"], (M, N), (a["ldx"], 1)))
+        if a["colsum"] is not None:                     # (the column-sum workspace is scratch: all of it may change)
+            outs.append((a["colsum"], (N,), (1,)))
+            if a["ws"] is not None:
+                outs.append((a["ws"], tuple(a["ws"].shape), tuple(a["ws"].stride())))
+        guard = self._guard(outs)
         pre, absprod = self._gemm_pre(s, M, N, K)
         prev = _v2(s["C"], M, N, a["ldc"]).clone() if a["accumulate"] else None
         aux_in = _v2(s["aux"], M, N, a["ldx"]).clone() if epi in (BD.EPI_DGELU, BD.EPI_MULAUX) else None
@@ -385,8 +565,8 @@ class Recorder:
                                 aux_dtype=a["C"].dtype)
         if prev is not None:
             bc = bc + BD.SLACK * BD.U32 * (prev.abs() + ref_c.abs())
-        kern = gemm_kernel(M, N, K, a["lda"], a["ldb"], a["A"], a["B"], a["out_f32"], epi)
-        res = [("C", BD.check(_v2(a["C"], M, N, a["ldc"]), ref_c, bc, "gemm C"), kern)]
+        kern = self._gemm_kernel(a)
+        res = [("C", BD.check(_v2(a["C"], M, N, a["ldc"]), ref_c, bc, "gemm C"), kern), guard(kern)]
         if ba is not None:
             res.append(("aux", BD.check(_v2(a["aux"], M, N, a["ldx"]), ref_aux, ba, "gemm aux"), kern))
         if a["colsum"] is not None:
@@ -506,6 +686,8 @@ class Recorder:
             p, ab = self._gemm_pre(dict(A=A, B=B, lda=lda, ldb=ldb, a_kmajor=0, b_kmajor=0, alpha=1.0, bias=None), M, N, K)
             prev = None if (mask >> i) & 1 else _v2(C, M, N, ldc).clone()
             pre.append((p, ab, prev))
+        launch, kerns = wgrad_group_kernel(a["problems"], mask, self._switches())
+        guard = self._guard([(pr[2], (pr[3], pr[4]), (pr[8], 1)) for pr in a["problems"]])
         run()
         self._ref.gemm_wgrad_group(probs, mask)
         res = []
@@ -514,9 +696,9 @@ class Recorder:
             bc, _ = BD.gemm_bounds(p, ab, K, BD.EPI_NONE, torch.float32, ref_c)
             if prev is not None:
                 bc = bc + BD.SLACK * BD.U32 * (prev.abs() + ref_c.abs())
-            kern = gemm_kernel(M, N, K, lda, ldb, a["problems"][i][0], a["problems"][i][1], True, 0)
             res.append((f"dW[{i}] {M}x{N}x{K}" + (" overwrite" if prev is None else ""),
-                        BD.check(_v2(a["problems"][i][2], M, N, ldc), ref_c, bc, f"wgrad problem {i}"), "grouped " + kern))
+                        BD.check(_v2(a["problems"][i][2], M, N, ldc), ref_c, bc, f"wgrad problem {i}"), kerns[i]))
+        res.append(guard(launch))
         return res
 
     # ------------------------------------------------------------------------------------------------ attention
