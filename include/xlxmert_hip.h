@@ -63,6 +63,15 @@ extern "C" {
                              * in_dtype says about A / B, out_dtype must be XL_F32.  Same dropout draw as XL_EPI_RESIDUAL: for one
                              * seed the kept / dropped pattern of a launch is identical                                      */
 
+#define XL_EPI_ROWSAMPLE 9   /* no C: XL_EPI_ROWMAX's sibling for temperature sampling (same preconditions).  y = alpha * acc + bias[n]: the
+                             * caller passes alpha = 1/T and a bias already divided by T; `seed` is the launch's noise seed (p_drop 0).
+                             * aux[(n/64)*M + m] = float4{max_n y, sum_n exp(y - max), s = argmax_n (y_n + g(seed, m, n)) (int bits), y_s}
+                             * over the 64-column segment, g = the Gumbel noise of xl_gumbel_from_bits' hash (csrc/common.h: an exact
+                             * draw from softmax(x / T); lowest index on ties); finish with xl_rowsample_combine (same seed).
+                             * Pad columns: zero rows of B and bias -1e30, NOT divided by T -- y = -1e30 there whatever alpha is, and
+                             * a real column's y + g >= -|x| / T - 2.82, so for 1e-3 <= T <= 1e3 (the range the host layers accept)
+                             * and |x| < 1e26 a pad column is never drawn and adds exp() = 0 to the sum                          */
+
 const char* xl_last_error(void);
 int  xl_version(void);
 /* Contexts: xl_ctx_create() -> handle (>= 1); xl_ctx_bind(handle) makes it the calling thread's current context (0 = the
@@ -350,6 +359,19 @@ int xl_gather_labels(const int64_t* labels, const int* rows, int64_t* out, int n
  * row_argmax[m] = argmax_n x (lowest index on ties, as torch.max), row_maxprob[m] = softmax(x)[argmax] = 1 / sum_n exp(x_n - max),
  * row_lse[m] = max + log(sum) (any output may be NULL). */
 int xl_rowmax_combine(const float* ws, int n_seg, int M, float* row_maxprob, int* row_argmax, float* row_lse, void* stream);
+
+/* Temperature sampling (Gumbel-max).  Noise g(seed, m, n) = -log(-log u): u from one 32-bit hash of (row m, column n, seed), an
+ * odd multiple of 2^-24 (csrc/common.h states the constants and the derived bound G_ABS = 5.97e-6 on the float part's absolute
+ * error).  The same function in all three places, so the fused and the unfused path perturb an element identically.
+ * xl_rowsample_combine: second half of XL_EPI_ROWSAMPLE over ws[seg*M + m] (same seed as the GEMM): row_id[m] = s, the drawn column;
+ *   row_lse[m] = log sum_n exp(y_n); row_prob[m] = exp(y_s - row_lse[m]), the tempered probability of the drawn column.
+ * xl_sample_rows: the same three outputs from fp32 logits in memory [M, K] (ldl), y = logits * inv_T (inv_T = 1/T); one wave per row.
+ * Any output may be NULL.  Rows are GLOBAL rows: the caller's row m is the noise function's row m.
+ * xl_gumbel_from_bits (test): g[i] = the float part evaluated on the caller's hash words h[i]. */
+int xl_rowsample_combine(const float* ws, int n_seg, int M, uint64_t seed, float* row_prob, int32_t* row_id, float* row_lse, void* stream);
+int xl_sample_rows(const float* logits, int M, int K, int ldl, float inv_T, uint64_t seed, float* row_prob, int32_t* row_id,
+                   float* row_lse, void* stream);
+int xl_gumbel_from_bits(const uint32_t* h, float* g, int n, void* stream);
 
 /* ---------------------------------------------------------------- optimizer side (ref lxmert_pretrain.py:343-364)
  * sumsq[0] += sum g^2 over n fp32 elements.  Deterministic: block partials are added in a fixed order by the last block to

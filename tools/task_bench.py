@@ -1,13 +1,22 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py"""
-import os, sys, time
+Usage: python tools/task_bench.py [--rows all|sampler] [--temperature T [--seed S]]
+--temperature: the sampler rows are timed greedy AND with temperature sampling, alternating in this process (rounds of 8 loops
+each; the line gives the median and the min..max spread of both)."""
+import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import torch
 import lxmert_oracle as O
 from xlxmert_amd.config import XLxmertConfig
 from xlxmert_amd.trainer import PretrainStep, word_rows_of
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", choices=("all", "sampler"), default="all")
+ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
+ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
+ap.add_argument("--rounds", type=int, default=5, help="greedy / sampled alternations (with --temperature)")
+args = ap.parse_args()
 
 cfg, oc = XLxmertConfig(), O.OracleConfig()
 dev = "cuda"
@@ -28,13 +37,13 @@ def cuda(d):
     return {k: v.cuda() for k, v in d.items()}
 
 
-for B in (128, 512):
+for B in (128, 512) if args.rows == "all" else ():
     tr = PretrainStep(cfg, B, 20, 64, device=dev, task="vqa", num_answers=3129, train_dropout=True, total_steps=1000)
     batch = cuda(O.make_vqa_inputs(oc, 3129, 1, B, 20, 8))
     dt = timed(lambda: tr.step(batch))
     print(f"vqa step        bs {B:4d}: {dt * 1e3:7.2f} ms  {B / dt:9.0f} examples/s")
     del tr
-for task in ("word_mask", "matched"):
+for task in ("word_mask", "matched") if args.rows == "all" else ():
     B = 256
     tr = PretrainStep(cfg, B, 20, 64, device=dev, task=task, train_dropout=True, total_steps=1000)
     g = torch.Generator().manual_seed(0)
@@ -63,4 +72,13 @@ for B in (64, 256):
                    cluster_ids=torch.zeros(B, 64, dtype=torch.long, device=dev), vis_mask=torch.ones(B, 64, dtype=torch.bool, device=dev))
     dt = timed(lambda: eng.sample_codes_nar(4))
     print(f"sampler T=4     bs {B:4d}: {dt * 1e3:7.2f} ms  {B / dt:9.0f} images/s (codes for the GAN decoder)")
+    if args.temperature is not None:
+        runs = {"greedy": [], "sampled": []}
+        for _ in range(args.rounds):
+            runs["greedy"].append(timed(lambda: eng.sample_codes_nar(4), warm=1))
+            runs["sampled"].append(timed(lambda: eng.sample_codes_nar(4, temperature=args.temperature, seed=args.seed), warm=1))
+        for k, v in runs.items():
+            v = sorted(v)
+            print(f"  {k:8s} bs {B:4d}: median {v[len(v) // 2] * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}"
+                  + (f"  (temperature {args.temperature}, seed {args.seed})" if k == "sampled" else ""))
     del eng, store

@@ -252,6 +252,50 @@ __device__ __forceinline__ float dropout_scale(uint64_t seed, uint32_t row, uint
 __device__ __forceinline__ uint64_t with_step_seed(uint64_t site_seed, const uint64_t* __restrict__ step) {
     return step != nullptr ? site_seed + *step * 1000003ull : site_seed;
 }
+// ------------------------------------------------------------------ Gumbel noise of the temperature samplers
+// argmax_n (x_n / T + g_n) with g_n standard Gumbel is an exact draw from softmax(x / T).  g is a pure function of
+// (launch seed, global row m, column n): the fused epilogue (XL_EPI_ROWSAMPLE), its combine and xl_sample_rows perturb the same
+// element identically, whatever the tile shape.
+//
+// INTEGER PART (the tests restate it bit for bit on the host).  All arithmetic modulo 2^32:
+//     seedmix = lo32(seed) ^ hi32(seed) * 0xC2B2AE3D                                   (gumbel_seed_mix, = dropout_seed_mix)
+//     h  = m * 0x9E3779B1 ^ n * 0x85EBCA77 ^ seedmix                                   (all 32 bits of n)
+//     h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16   ("lowbias32")
+//     k  = h >> 9                     (23 random bits)
+//     u  = (2 k + 1) * 2^-24          an odd multiple of 2^-24 in (0, 1): exact in fp32, never 0 or 1
+//     w  = (2 (k ^ 0x7FFFFF) + 1) * 2^-24  = 1 - u, exact as well (2^24 - (2k + 1) = 2 (2^23 - 1 - k) + 1)
+// A launch's seed is  user seed * 0x9E3779B97F4A7C15 + step index  (mod 2^64; host side, engine.sample_launch_seed).
+//
+// FLOAT PART.  g = -log(-log u).  The draws that win a maximum are the large g, where t = -log u is tiny (down to 2^-24): a
+// logarithm of u that is accurate in absolute terms near 1 would leave t with no correct digit there.  So the small side is
+// generated directly, t = -log1p(-w) with w = 1 - u exact, and both logarithms are the ocml functions (log1pf, logf; the build
+// has no fast-math flag), whose documented (OpenCL full profile) bounds are 2 ulp and 3 ulp.
+// G_ABS, the bound on |g_fp32 - g| over the whole grid of u:
+//     t^ = t (1 + d), |d| <= 2 ulp <= 2 * 2^-23 = 2^-22 (t in [2^-24 (1 + 2^-25), 16.64]: normal numbers only)
+//     -log t^ = -log t - log(1 + d): an absolute term <= 2^-22 (1 + 2^-22)
+//     logf's own 3 ulp at |g| <= log(2^24) = 16.64 < 32: ulp <= 2^-19, an absolute term <= 3 * 2^-19
+//     G_ABS = 3 * 2^-19 + 2^-22 (1 + 2^-22) < 5.97e-6            (the constant itself lives with the checks: tests/bounds_sampling.py)
+__device__ __forceinline__ uint32_t gumbel_seed_mix(uint64_t seed) { return (uint32_t)seed ^ (uint32_t)(seed >> 32) * 0xC2B2AE3Du; }
+__device__ __forceinline__ uint32_t gumbel_bits(uint32_t seedmix, uint32_t m, uint32_t n) {
+    uint32_t h = m * 0x9E3779B1u ^ n * 0x85EBCA77u ^ seedmix;
+    h ^= h >> 16; h *= 0x7FEB352Du;
+    h ^= h >> 15; h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ float gumbel_from_bits(uint32_t h) {
+    const uint32_t k = h >> 9;
+    const float w = (float)(2u * (k ^ 0x7FFFFFu) + 1u) * 5.9604644775390625e-8f;      // 1 - u: a 24-bit integer times 2^-24, exact
+    const float t = -log1pf(-w);                                                     // -log u
+    return -logf(t);
+}
+__device__ __forceinline__ float gumbel_noise_mixed(uint32_t seedmix, uint32_t m, uint32_t n) {
+    return gumbel_from_bits(gumbel_bits(seedmix, m, n));
+}
+__device__ __forceinline__ float gumbel_noise(uint64_t seed, uint32_t m, uint32_t n) {
+    return gumbel_noise_mixed(gumbel_seed_mix(seed), m, n);
+}
+
 // ------------------------------------------------------------------ library context (include/xlxmert_hip.h xl_ctx_*)
 // Everything a caller can SET on the library lives in a context object, never in a process global: the dropout step-seed
 // pointer, the deferred-reduction switch and its per-stream pending lists, the slab workspaces registered per stream, and the

@@ -496,6 +496,7 @@ __device__ __forceinline__ void load_bias8(const GemmParams& p, int lane, bool f
 template <int EPI>
 __device__ __forceinline__ uint64_t dropout_seed_of(const GemmParams& p) {
     if constexpr (EPI == XL_EPI_RESIDUAL || EPI == XL_EPI_RESIDUAL_F32) return p.p_drop > 0.0f ? with_step_seed(p.seed, p.step_seed) : 0;
+    else if constexpr (EPI == XL_EPI_ROWSAMPLE) return p.seed;      // the noise seed of the launch (common.h gumbel_noise), as given
     else return 0;
 }
 
@@ -560,6 +561,37 @@ __device__ __forceinline__ void epilogue_rows_fast(const GemmParams& p, const fl
             }
             if (c8 == 0)
                 reinterpret_cast<float4*>(p.aux)[(size_t)(nq >> 6) * p.M + m] = make_float4(mx, se, __int_as_float(idx), 0.f);
+        } else if constexpr (EPI == XL_EPI_ROWSAMPLE) {
+            // (max, sum exp(y - max)) of the segment as XL_EPI_ROWMAX has them, and the Gumbel-max draw s = argmax_n (y_n + g_n) with
+            // its y_s: z = y + g lives in registers across the lane merge (the same fp32 expression that a merge of two stored
+            // records evaluates again from y_s: rowops.hip rowsample_merge); ties go to the lower column
+            const uint32_t sm = gumbel_seed_mix(seed);
+            float mx = v[0];
+#pragma unroll
+            for (int e = 1; e < 8; ++e) mx = fmaxf(mx, v[e]);
+            float se = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) se += __expf(v[e] - mx);
+            float zb = v[0] + gumbel_noise_mixed(sm, (uint32_t)m, (uint32_t)n), ys = v[0];
+            int idx = n;
+#pragma unroll
+            for (int e = 1; e < 8; ++e) {
+                const float z = v[e] + gumbel_noise_mixed(sm, (uint32_t)m, (uint32_t)(n + e));
+                if (z > zb) { zb = z; ys = v[e]; idx = n + e; }
+            }
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                const float omx = __shfl_xor(mx, o, 64), ose = __shfl_xor(se, o, 64);
+                const float oz = __shfl_xor(zb, o, 64), oys = __shfl_xor(ys, o, 64);
+                const int oi = __shfl_xor(idx, o, 64);
+                const float nm = fmaxf(mx, omx);
+                se = se * __expf(mx - nm) + ose * __expf(omx - nm);
+                mx = nm;
+                const bool take = oz > zb || (oz == zb && oi < idx);
+                zb = take ? oz : zb; ys = take ? oys : ys; idx = take ? oi : idx;
+            }
+            if (c8 == 0)
+                reinterpret_cast<float4*>(p.aux)[(size_t)(nq >> 6) * p.M + m] = make_float4(mx, se, __int_as_float(idx), ys);
         } else if (p.out_f32) {
             float* c = reinterpret_cast<float*>(p.C) + m * p.ldc + n;
             *reinterpret_cast<float4*>(c) = make_float4(v[0], v[1], v[2], v[3]);
@@ -808,6 +840,8 @@ hipError_t launch_pp_group(const GroupParams& g, int nblk, hipStream_t st);
 hipError_t launch_pp(const GemmParams& p, int a_kmajor, int b_kmajor, int epik, int bn, int nblk, hipStream_t st, int bm = 256);
 // gemm_pp_res32.hip: the XL_EPI_RESIDUAL_F32 instances of the ping-pong kernel (A K-major; 256x256 tiles, or bm = 128: 128x192 duo tiles)
 hipError_t launch_pp_res32(const GemmParams& p, int b_kmajor, int bm, int nblk, hipStream_t st);
+// gemm_pp_sample.hip: the XL_EPI_ROWSAMPLE instance of the ping-pong kernel (both operands K-major, 256x256 tiles, every tile interior)
+hipError_t launch_pp_sample(const GemmParams& p, int nblk, hipStream_t st);
 // gemm_pp_pair.hip: two problems per launch (gemm_pp_kernel.h gemm_bf16_pp_pair_kernel), 256x256 tiles, A K-major, fast epilogue;
 // hipErrorInvalidValue: no instance for this (layout, epilogue kind) -- forward layout: NONE / RESIDUAL / GELU_DG, dX layout:
 // NONE / RESIDUAL / MULAUX.  tiles0: problem 0's tile count (linear tiles [0, tiles0) are its, the rest problem 1's)

@@ -2231,6 +2231,112 @@ extern "C" int xl_rowmax_combine(const float* ws, int n_seg, int M, float* row_m
     return XL_OK;
 }
 
+// ---- temperature sampling (Gumbel-max; noise: common.h gumbel_noise)
+// Two candidates (s, y_s) of one row: the larger z = y_s + g(seed, m, s) wins, the lower column on a tie.  z is not stored in a
+// segment record: it is this fp32 expression, which is also what the GEMM epilogue compared.
+__device__ __forceinline__ void rowsample_merge(uint32_t sm, uint32_t m, float& mx, float& se, int& s, float& ys, float& z,
+                                                float omx, float ose, int os, float oys) {
+    const float nm = fmaxf(mx, omx);
+    se = se * __expf(mx - nm) + ose * __expf(omx - nm);
+    mx = nm;
+    const float oz = oys + gumbel_noise_mixed(sm, m, (uint32_t)os);
+    const bool take = oz > z || (oz == z && os < s);
+    z = take ? oz : z; ys = take ? oys : ys; s = take ? os : s;
+}
+// second half of the GEMM's XL_EPI_ROWSAMPLE epilogue over the [n_seg][M] records {max, sum exp, s, y_s}: the thread layout of
+// rowmax_combine_kernel (64 rows per block, four threads per row, merged through LDS)
+__global__ __launch_bounds__(256) void rowsample_combine_kernel(const float4* __restrict__ ws, int n_seg, int M, uint64_t seed,
+                                                                float* row_prob, int* row_id, float* row_lse) {
+    __shared__ float4 part[4][64];
+    const int r = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int m = blockIdx.x * 64 + r;
+    const uint32_t sm = gumbel_seed_mix(seed);
+    float mx = -INFINITY, se = 0.f, ys = 0.f, z = -INFINITY;
+    int s = 0x7fffffff;
+    if (m < M)
+        for (int g = q; g < n_seg; g += 4) {
+            const float4 rec = ws[(size_t)g * M + m];
+            rowsample_merge(sm, (uint32_t)m, mx, se, s, ys, z, rec.x, rec.y, __float_as_int(rec.z), rec.w);
+        }
+    part[q][r] = make_float4(mx, se, __int_as_float(s), ys);
+    __syncthreads();
+    if (q != 0 || m >= M) return;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        const float4 o = part[k][r];
+        if (o.y > 0.f) rowsample_merge(sm, (uint32_t)m, mx, se, s, ys, z, o.x, o.y, __float_as_int(o.z), o.w);
+    }
+    const float lse = mx + logf(se);
+    if (row_id) row_id[m] = s;
+    if (row_prob) row_prob[m] = expf(ys - lse);
+    if (row_lse) row_lse[m] = lse;
+}
+
+// The same draw over logits in memory: one wave per row, y = logits * inv_T; pass 1 the maximum and the Gumbel-max candidate of
+// every lane, pass 2 the sum of exp(y - max).
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ logits, int M, int K, int ldl, float inv_T,
+                                                          uint64_t seed, float* row_prob, int* row_id, float* row_lse) {
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const float* x = logits + (size_t)m * ldl;
+    const uint32_t sm = gumbel_seed_mix(seed);
+    float mx = -INFINITY, z = -INFINITY, ys = 0.f;
+    int s = 0x7fffffff;
+    for (int n = lane; n < K; n += 64) {               // ascending columns per lane: a strict > keeps the lower column on a tie
+        const float y = x[n] * inv_T;
+        mx = fmaxf(mx, y);
+        const float zn = y + gumbel_noise_mixed(sm, (uint32_t)m, (uint32_t)n);
+        if (zn > z) { z = zn; ys = y; s = n; }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float oz = __shfl_xor(z, o, 64), oys = __shfl_xor(ys, o, 64);
+        const int os = __shfl_xor(s, o, 64);
+        const bool take = oz > z || (oz == z && os < s);
+        z = take ? oz : z; ys = take ? oys : ys; s = take ? os : s;
+    }
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int n = lane; n < K; n += 64) se += __expf(x[n] * inv_T - mx);
+    se = wave_sum(se);
+    if (lane != 0) return;
+    const float lse = mx + logf(se);
+    if (row_id) row_id[m] = s;
+    if (row_prob) row_prob[m] = expf(ys - lse);
+    if (row_lse) row_lse[m] = lse;
+}
+
+__global__ __launch_bounds__(256) void gumbel_from_bits_kernel(const uint32_t* __restrict__ h, float* __restrict__ g, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) g[i] = gumbel_from_bits(h[i]);
+}
+extern "C" int xl_rowsample_combine(const float* ws, int n_seg, int M, uint64_t seed, float* row_prob, int32_t* row_id, float* row_lse,
+                                    void* stream) {
+    XL_CHECK_ARG(ws && n_seg > 0 && M > 0 && aligned16(ws), XL_ERR_BAD_ARG, "xl_rowsample_combine: bad args");
+    hipLaunchKernelGGL(rowsample_combine_kernel, dim3((M + 63) / 64), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(ws), n_seg, M, seed, row_prob, row_id, row_lse);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
+extern "C" int xl_sample_rows(const float* logits, int M, int K, int ldl, float inv_T, uint64_t seed, float* row_prob, int32_t* row_id,
+                              float* row_lse, void* stream) {
+    XL_CHECK_ARG(logits && M > 0 && K > 0 && ldl >= K && inv_T > 0.f && inv_T < INFINITY, XL_ERR_BAD_ARG,
+                 "xl_sample_rows: M=%d K=%d ldl=%d inv_T=%g", M, K, ldl, (double)inv_T);
+    hipLaunchKernelGGL(sample_rows_kernel, dim3((M + WPB - 1) / WPB), dim3(256), 0, (hipStream_t)stream, logits, M, K, ldl,
+                       inv_T, seed, row_prob, row_id, row_lse);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
+extern "C" int xl_gumbel_from_bits(const uint32_t* h, float* g, int n, void* stream) {
+    XL_CHECK_ARG(h && g && n > 0, XL_ERR_BAD_ARG, "xl_gumbel_from_bits: bad args");
+    hipLaunchKernelGGL(gumbel_from_bits_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h, g, n);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
 extern "C" int xl_gather_labels(const int64_t* labels, const int* rows, int64_t* out, int n_rows, void* stream) {
     XL_CHECK_ARG(labels && rows && out && n_rows > 0, XL_ERR_BAD_ARG, "xl_gather_labels: bad args (n_rows=%d)", n_rows);
     hipLaunchKernelGGL(gather_labels_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, labels, rows, out, n_rows);

@@ -19,7 +19,7 @@ import os
 
 import torch
 
-from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_ROWMAX, EPI_TANH, GemmCall
+from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_ROWMAX, EPI_ROWSAMPLE, EPI_TANH, GemmCall
 
 
 class _Res:
@@ -1989,6 +1989,7 @@ class Engine:
         if getattr(self, "_cent_pad", None) is None or self._cent_pad.shape[0] != Kq:
             self._cent_pad = torch.zeros(Kq, self.F, dtype=self.cdtype, device=self.dev)
             self._bias_pad = torch.full((Kq,), -1e30, dtype=torch.float32, device=self.dev)
+            self._bias_pad_T = None                                    # its copy divided by T: made by _prepare_fused_sample
             self._rowmax_ws = torch.zeros((Kq // 64) * self.MV * 4, dtype=torch.float32, device=self.dev)
         self._cent_pad[:self.K].copy_(self.store.centroids_c)          # (frozen, but set_centroids may have replaced it)
         self._bias_pad[:self.K].copy_(self.hd["bc"][0])
@@ -2001,22 +2002,69 @@ class Engine:
         self.ops.rowmax_combine(self._rowmax_ws, Kq // 64, self.MV, self.row_maxprob, self.row_argmax, self.row_lse)
         return self.row_maxprob, self.row_argmax
 
-    def _predict_step(self, fused):
-        if fused:
+    def _predict_step(self, fused, temperature=None, seed=0):
+        if temperature is not None:
+            self._sample_step(fused, temperature, seed)
+        elif fused:
             self.head_forward(want_logits=False)
             self.predict_codes_fused()
         else:
             self.head_forward()
             self.predict_codes()
 
-    def sample_codes_nar(self, n_steps=4, on_step=None):
+    # Temperature sampling: each position DRAWS its code from softmax(logits / T) instead of taking the mode -- Gumbel-max, the
+    # noise a pure function of (launch seed, global row b*V+v, code), so the fused and the unfused path draw identically.  The
+    # draw fills the buffers of the greedy step (row_argmax = the drawn code, row_maxprob = its tempered probability: the
+    # confidence of the re-masking and of the `confidence` position policy), so everything behind _predict_step is unchanged.
+    TEMPERATURE_MIN, TEMPERATURE_MAX = 1e-3, 1e3     # the range of the pad-column guarantee (include/xlxmert_hip.h XL_EPI_ROWSAMPLE)
+
+    @classmethod
+    def check_temperature(cls, temperature):
+        if temperature is None:
+            return None
+        t = float(temperature)
+        if not math.isfinite(t) or not (cls.TEMPERATURE_MIN <= t <= cls.TEMPERATURE_MAX):
+            raise ValueError(f"temperature {temperature!r}: a finite value in [{cls.TEMPERATURE_MIN}, {cls.TEMPERATURE_MAX}] "
+                             "(None = greedy)")
+        return t
+
+    @staticmethod
+    def sample_launch_seed(seed, step):
+        """noise seed of sampler step `step`: seed * 0x9E3779B97F4A7C15 + step (mod 2^64) -- distinct per step, and for the seeds
+        a caller picks (small integers, 63-bit draws) distinct across (seed, step) pairs"""
+        return (int(seed) * 0x9E3779B97F4A7C15 + int(step)) & 0xFFFFFFFFFFFFFFFF
+
+    def _prepare_fused_sample(self, temperature):
+        """after _prepare_fused_predict: the codebook bias divided by T (once per loop); pad columns keep -1e30, NOT divided"""
+        if self._bias_pad_T is None:
+            self._bias_pad_T = torch.empty_like(self._bias_pad)
+        self._bias_pad_T.copy_(self._bias_pad)
+        self._bias_pad_T[:self.K].mul_(1.0 / temperature)
+
+    def _sample_step(self, fused, temperature, launch_seed):
+        inv_T = 1.0 / temperature
+        if fused:
+            self.head_forward(want_logits=False)
+            Kq = self._cent_pad.shape[0]
+            self.ops.gemm(self.feat, self._cent_pad, None, self._bias_pad_T, None, self._rowmax_ws, self.MV, Kq, self.F, self.F, self.F,
+                          Kq, epilogue=EPI_ROWSAMPLE, alpha=inv_T, seed=launch_seed)
+            self.ops.rowsample_combine(self._rowmax_ws, Kq // 64, self.MV, launch_seed, self.row_maxprob, self.row_argmax, self.row_lse)
+        else:
+            self.head_forward()
+            self.ops.sample_rows(self.logits, self.MV, self.K, self.K, inv_T, launch_seed, self.row_maxprob, self.row_argmax,
+                                 self.row_lse)
+
+    def sample_codes_nar(self, n_steps=4, on_step=None, *, temperature=None, seed=0):
         """Iterative Mask-Predict sampling (ref tasks/imggen_model.py:169-243) without a host round trip between steps:
         re-mask the lowest-confidence positions -> encoder -> codebook head -> softmax-max / argmax -> keep the predictions
         of the masked positions.  Text inputs come from set_inputs (cluster_ids / vis_mask there are placeholders).
         Returns (code_ids [B,V] int64, code features [B*V, F] in the compute dtype, pred_prob [B*V] fp32); the caller
         hands `code.view(B,V,F).permute(0,2,1).view(B,F,g,g)` to the frozen GAN generator (stock PyTorch, ref :254).
         on_step(i): called after step i's update (return_intermediate of the reference, :245-248: materialise_codes() gives the
-        code tensor of that moment)."""
+        code tensor of that moment).
+        temperature (None = greedy, exactly the calls above): every position draws its code from softmax(logits / temperature),
+        reproducibly for one `seed`; the confidence of the re-masking is the tempered probability of the drawn code."""
+        temperature = self.check_temperature(temperature)
         ops, B, V = self.ops, self.B, self.V
         st = self.store
         self.use_codebook, self.has_vmask = True, True
@@ -2024,6 +2072,8 @@ class Engine:
         fused = self.fused_predict_available()
         if fused:
             self._prepare_fused_predict()
+            if temperature is not None:
+                self._prepare_fused_sample(temperature)
         for i in range(n_steps):
             n_mask = int((n_steps - i) / n_steps * V)                      # ref :201-202 (host arithmetic on the step index)
             if i == 0:
@@ -2035,7 +2085,7 @@ class Engine:
                 self.encoder_forward(want_pooled=False)                    # codebook_gather == where(mask, mask_feat, vis_emb(ids))
             finally:
                 self._reuse_lang_stack = False
-            self._predict_step(fused)
+            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i))
             ops.sampler_update(self.row_argmax, self.vmask, self.cid, B * V)
             if on_step is not None:
                 on_step(i)
@@ -2050,11 +2100,13 @@ class Engine:
                                  self.MV, self.F)
         return self.feats
 
-    def sample_codes_ar(self, n_steps=None, mode="confidence", positions=None, trace=None, on_step=None):
+    def sample_codes_ar(self, n_steps=None, mode="confidence", positions=None, trace=None, on_step=None, *, temperature=None, seed=0):
         """Autoregressive sampling (ref tasks/imggen_model.py:49-153): one grid position per image is filled per step --
         the most confident not-yet-visited one ("confidence", the reference's default), position i ("tlbr"), or the host's
         shuffled order popped from the end ("random", positions = that list).  Same device-resident state as
-        sample_codes_nar; `trace` (a list) receives a copy of vis_mask after every step."""
+        sample_codes_nar; `trace` (a list) receives a copy of vis_mask after every step.  temperature / seed: as in sample_codes_nar
+        (the `confidence` policy ranks positions by the tempered probability of their drawn code)."""
+        temperature = self.check_temperature(temperature)
         ops, B, V = self.ops, self.B, self.V
         st = self.store
         n_steps = V if n_steps is None else n_steps
@@ -2068,6 +2120,8 @@ class Engine:
         fused = self.fused_predict_available()
         if fused:
             self._prepare_fused_predict()
+            if temperature is not None:
+                self._prepare_fused_sample(temperature)
         for i in range(n_steps):
             cur = -1
             if mode == "random":
@@ -2080,7 +2134,7 @@ class Engine:
                 self.encoder_forward(want_pooled=False)
             finally:
                 self._reuse_lang_stack = False
-            self._predict_step(fused)
+            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i))
             ops.sampler_ar_update(self.row_maxprob, self.row_argmax, self.visited, self.vmask, self.cid, B, V, cur)
             if trace is not None:
                 trace.append(self.vmask.clone())

@@ -255,6 +255,11 @@ class LxmertPreTrainingHeads(_Named):
         self._bind(store, "cls", [n for n in store.names() if n.startswith("cls.")])
 
 
+def _sample_seed(seed):
+    """the samplers' noise seed: the caller's, or one drawn from torch's default CPU generator (torch.manual_seed governs)"""
+    return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+
+
 class XLxmertForPretraining(nn.Module):
     """ref lxrt/modeling.py:56-308: `.bert`, `.cls` (task_mask_lm or task_matched), `.obj_predict_head` (task_obj_predict),
     `.answer_head` (task_qa), `.mask_feat`, `.vis_emb`; forward(task = 'vis_mask' | 'word_mask' | 'matched' | 'qa')."""
@@ -376,11 +381,14 @@ class XLxmertForPretraining(nn.Module):
         return out_dict
 
     @torch.no_grad()
-    def sample_codes(self, input_ids, n_steps=4, grid_size=8):
+    def sample_codes(self, input_ids, n_steps=4, grid_size=8, *, temperature=None, seed=None):
         """The device part of ImggenModel.sample_image_NAR (ref tasks/imggen_model.py:169-254): Mask-Predict sampling of
         the grid codes, returned as the generator's input `[B, feat_dim, grid, grid]` (fp32) plus the chosen code ids.
-        Tokenisation (before) and the frozen GAN `G(code)` + denorm (after) stay with the caller, as in the reference."""
+        Tokenisation (before) and the frozen GAN `G(code)` + denorm (after) stay with the caller, as in the reference.
+        temperature (None = the reference's greedy choice): draw every code from softmax(logits / temperature); seed=None takes
+        one from torch's default CPU generator (torch.manual_seed governs)."""
         import numpy as np
+        temperature = Engine.check_temperature(temperature)
         if self.vis_emb is None:
             raise RuntimeError("call set_visual_embedding(centroids) first")
         was_training = self.training
@@ -396,7 +404,10 @@ class XLxmertForPretraining(nn.Module):
         eng.set_inputs(input_ids, input_ids > 0, None, torch.from_numpy(pos).to(dev).unsqueeze(0).expand(B, -1, -1),
                        cluster_ids=torch.zeros(B, V, dtype=torch.long, device=dev),
                        vis_mask=torch.ones(B, V, dtype=torch.bool, device=dev))
-        cid, code, _ = eng.sample_codes_nar(n_steps)
+        if temperature is None:
+            cid, code, _ = eng.sample_codes_nar(n_steps)
+        else:
+            cid, code, _ = eng.sample_codes_nar(n_steps, temperature=temperature, seed=_sample_seed(seed))
         out = code.view(B, V, -1).permute(0, 2, 1).reshape(B, -1, grid_size, grid_size).float()
         self.train(was_training)
         return out, cid.clone()
@@ -596,22 +607,30 @@ class ImggenModel(XLxmertForPretraining):
         return self.denorm(self.G(x)).cpu()
 
     @torch.no_grad()
-    def sample_image_NAR(self, sentences, max_text_length=20, n_steps=None, return_intermediate=False):
-        """ref :169-257.  n_steps=None -> grid_size ** 2 (ref :191-192)."""
+    def sample_image_NAR(self, sentences, max_text_length=20, n_steps=None, return_intermediate=False, *, temperature=None,
+                         sample_seed=None):
+        """ref :169-257.  n_steps=None -> grid_size ** 2 (ref :191-192).  temperature (beyond the reference; None = its greedy
+        choice): every position draws its code from softmax(logits / temperature) -- different, reproducible images per caption;
+        sample_seed=None takes a seed from torch's default CPU generator."""
+        temperature = Engine.check_temperature(temperature)
+        kw = {} if temperature is None else {"temperature": temperature, "seed": _sample_seed(sample_seed)}
         eng, B, V = self._prepare(self._input_ids(sentences, max_text_length))
         n_steps = V if n_steps is None else n_steps
         imgs = []
         hook = (lambda i: imgs.append(self._image(eng.materialise_codes(), B))) if return_intermediate else None
-        _, code, _ = eng.sample_codes_nar(n_steps, on_step=hook)
+        _, code, _ = eng.sample_codes_nar(n_steps, on_step=hook, **kw)
         self.code_ids = eng.cid.clone()                             # the chosen codebook ids [B, V] (beyond the reference: handy)
         return imgs if return_intermediate else self._image(code, B)
 
     @torch.no_grad()
     def sample_image_AR(self, sentences, max_text_length=20, position_random=False, position_TLBR=False, position_confidence=True,
-                        n_steps=None, seed=None, return_intermediate=False):
+                        n_steps=None, seed=None, return_intermediate=False, *, temperature=None, sample_seed=None):
         """ref :49-167: the three position policies with the reference's precedence (random, else TLBR, else confidence) and its
-        host-side order for `position_random` (random.Random(seed).shuffle, extended for n_steps > grid ** 2, :77-89)."""
+        host-side order for `position_random` (random.Random(seed).shuffle, extended for n_steps > grid ** 2, :77-89).
+        temperature / sample_seed: as in sample_image_NAR (`seed` keeps meaning the position order)."""
         import random
+        temperature = Engine.check_temperature(temperature)
+        kw = {} if temperature is None else {"temperature": temperature, "seed": _sample_seed(sample_seed)}
         eng, B, V = self._prepare(self._input_ids(sentences, max_text_length))
         n_steps = V if n_steps is None else n_steps
         positions = None
@@ -631,6 +650,6 @@ class ImggenModel(XLxmertForPretraining):
             raise ValueError("sample_image_AR: one of position_random / position_TLBR / position_confidence must be set")
         imgs = []
         hook = (lambda i: imgs.append(self._image(eng.materialise_codes(masked=True), B))) if return_intermediate else None
-        _, code, _ = eng.sample_codes_ar(n_steps, mode, positions=positions, on_step=hook)
+        _, code, _ = eng.sample_codes_ar(n_steps, mode, positions=positions, on_step=hook, **kw)
         self.code_ids = eng.cid.clone()
         return imgs if return_intermediate else self._image(code, B)

@@ -14,6 +14,7 @@ from ._lib import XlError, get_lib
 XL_F32, XL_BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_TANH, EPI_ROWMAX, EPI_GELU_DG, EPI_MULAUX = 0, 1, 2, 3, 4, 5, 6, 7
 EPI_RESIDUAL_F32 = 8            # XL_EPI_RESIDUAL with an fp32 residual and output (the fp32 residual stream); chosen by HipOps.gemm
+EPI_ROWSAMPLE = 9               # XL_EPI_ROWMAX's sibling for temperature sampling: alpha = 1/T, bias / T, seed = the launch's noise seed
 
 TORCH_DTYPE = {XL_F32: torch.float32, XL_BF16: torch.bfloat16}
 _SLAB_WS = {}
@@ -424,6 +425,21 @@ class HipOps:
         """second half of gemm(epilogue=EPI_ROWMAX, aux=ws): per-row argmax / max softmax probability / log-sum-exp."""
         self._call("xl_rowmax_combine", self._p(ws), n_seg, M, self._p(row_maxprob), self._p(row_argmax), self._p(row_lse),
                       self._stream())
+
+    def rowsample_combine(self, ws, n_seg, M, seed, row_prob, row_id, row_lse=None):
+        """second half of gemm(epilogue=EPI_ROWSAMPLE, aux=ws, seed=seed): per row the drawn column, its tempered probability and
+        the log-sum-exp of the tempered logits."""
+        self._call("xl_rowsample_combine", self._p(ws), n_seg, M, int(seed), self._p(row_prob), self._p(row_id), self._p(row_lse),
+                   self._stream())
+
+    def sample_rows(self, logits, M, K, ldl, inv_T, seed, row_prob, row_id, row_lse=None):
+        """the same draw over fp32 logits in memory (xl_sample_rows): y = logits * inv_T, one wave per row."""
+        self._call("xl_sample_rows", self._p(logits), M, K, ldl, float(inv_T), int(seed), self._p(row_prob), self._p(row_id),
+                   self._p(row_lse), self._stream())
+
+    def gumbel_from_bits(self, h, g, n):
+        """test export: g[i] = the float part of the samplers' noise on the hash words h[i] (int32 storage of the uint32 bits)"""
+        self._call("xl_gumbel_from_bits", self._p(h), self._p(g), n, self._stream())
 
     def gather_labels(self, labels, rows, out, n_rows):
         self._call("xl_gather_labels", self._p(labels), self._p(rows), self._p(out), n_rows, self._stream())
