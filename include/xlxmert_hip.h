@@ -373,6 +373,28 @@ int xl_sample_rows(const float* logits, int M, int K, int ldl, float inv_T, uint
                    float* row_lse, void* stream);
 int xl_gumbel_from_bits(const uint32_t* h, float* g, int n, void* stream);
 
+/* Truncated sampling: xl_sample_rows with top-k, top-p (nucleus) and min-p cuts; one workgroup per row, K <= 65536, only columns
+ * < K of a row are read (ldl >= K), finite logits.  For row m:  y_n = logits[m, n] * inv_T (ONE fp32 multiply; -0 counts as +0),
+ * mx = max_n y_n, Z = sum_n exp(y_n - mx) over ALL K columns, lse = mx + log Z.
+ *  1. rank        columns ordered by (y descending, column ascending): a total order, ties go to the lower column
+ *  2. candidates  the first k_c = min(K, top_k) ranks, top_k in [1, XL_TRUNC_MAX_CAND]; a caller without a top-k passes
+ *                 XL_TRUNC_MAX_CAND: top-p and min-p act WITHIN at most 256 candidates (row_kept[m] == 256 reveals the cap)
+ *  3. min-p       log_min_p = fp32(log(min_p)), -inf = off: a candidate is kept iff y_n >= mx + log_min_p (one fp32 add)
+ *  4. top-p       top_p >= 1 = off (not evaluated).  c_r = sum_{j<r} exp(y_j - mx) over the candidates in rank order, added
+ *                 sequentially in fp32: rank r is kept iff c_r < top_p * Z -- the shortest prefix whose mass, relative to the FULL
+ *                 softmax, reaches top_p; rank 0 is always kept
+ *  5. kept set    all three cuts are prefixes of the rank order: the first k_s >= 1 ranks
+ *  6. draw        s = argmax over the kept n of (y_n + g(seed, m, n)), g the noise of xl_sample_rows (global row m, launch seed), the
+ *                 lower column on a tie: xl_sample_rows' draw whenever that draw lies in the kept set (the two kernels round the sum
+ *                 differently -- xl_sample_rows contracts multiply and add -- so a near-tie of two z within an ulp may fall either way)
+ *  7. outputs     row_id[m] = s; row_lse[m] = lse; row_prob[m] = exp(y_s - lse), the tempered probability under the FULL softmax
+ *                 (not renormalised over the kept set: it stays a confidence to rank positions by, and top_k = 1 at T = 1 is the
+ *                 greedy sampler); row_kept[m] = k_s.  Any output may be NULL.
+ * One seed reproduces all four outputs bit for bit (no floating-point atomics anywhere). */
+#define XL_TRUNC_MAX_CAND 256
+int xl_sample_rows_trunc(const float* logits, int M, int K, int ldl, float inv_T, uint64_t seed, int top_k, float top_p,
+                         float log_min_p, float* row_prob, int32_t* row_id, float* row_lse, int32_t* row_kept, void* stream);
+
 /* ---------------------------------------------------------------- optimizer side (ref lxmert_pretrain.py:343-364)
  * sumsq[0] += sum g^2 over n fp32 elements.  Deterministic: block partials are added in a fixed order by the last block to
  * arrive, so every rank of a data-parallel job derives the same clip factor from the same reduced gradients (an atomic per block

@@ -1,8 +1,10 @@
 """One arm of the T = 4 Mask-Predict sampler (bf16, fused head) and nothing else, for a profiler: same engine set-up as the sampler
 rows of tools/task_bench.py.
-Usage: rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/sampler_profile.py [--temperature T [--seed S]] [--bs B] [--loops N]
+Usage: rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/sampler_profile.py [--temperature T [--seed S]] [--top-k K]
+                                                                            [--top-p P] [--min-p Q] [--bs B] [--loops N]
        python tools/prof_summary.py DIR/NAME_results.db
-Without --temperature the loop is the greedy one.  One pass per arm: the per-kernel averages of the two summaries are compared."""
+Without --temperature and without a truncation argument the loop is the greedy one.  One pass per arm: the per-kernel averages of
+the summaries are compared."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -17,6 +19,9 @@ from xlxmert_amd.trainer import init_reference_weights
 ap = argparse.ArgumentParser()
 ap.add_argument("--temperature", type=float, default=None)
 ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--top-k", type=int, default=None)
+ap.add_argument("--top-p", type=float, default=None)
+ap.add_argument("--min-p", type=float, default=None)
 ap.add_argument("--bs", type=int, default=256)
 ap.add_argument("--loops", type=int, default=12)
 args = ap.parse_args()
@@ -32,10 +37,12 @@ inp = O.make_inputs(oc, 4, B, 20, 8)
 eng.set_inputs(inp["input_ids"].cuda(), inp["attention_mask"].cuda(), None, inp["visual_pos"].cuda(),
                cluster_ids=torch.zeros(B, 64, dtype=torch.long, device=dev), vis_mask=torch.ones(B, 64, dtype=torch.bool, device=dev))
 assert eng.fused_predict_available()
+trunc = {k: v for k, v in (("top_k", args.top_k), ("top_p", args.top_p), ("min_p", args.min_p)) if v is not None}
 for _ in range(args.loops):
-    if args.temperature is None:
+    if args.temperature is None and not trunc:
         eng.sample_codes_nar(4)
     else:
-        eng.sample_codes_nar(4, temperature=args.temperature, seed=args.seed)
+        eng.sample_codes_nar(4, temperature=args.temperature, seed=args.seed, **trunc)
 torch.cuda.synchronize()
-print(f"{args.loops} loops of 4 steps at bs {B}, " + ("greedy" if args.temperature is None else f"temperature {args.temperature}, seed {args.seed}"))
+print(f"{args.loops} loops of 4 steps at bs {B}, " + ("greedy" if args.temperature is None and not trunc else
+                                                     f"temperature {args.temperature}, seed {args.seed}, truncation {trunc or None}"))

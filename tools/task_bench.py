@@ -1,8 +1,10 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py [--rows all|sampler] [--temperature T [--seed S]]
+Usage: python tools/task_bench.py [--rows all|sampler] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
 --temperature: the sampler rows are timed greedy AND with temperature sampling, alternating in this process (rounds of 8 loops
-each; the line gives the median and the min..max spread of both)."""
+each; the line gives the median and the min..max spread of both).
+--top-k / --top-p / --min-p (any of them): a third arm in the same alternation, the truncated sampler at that temperature (1 if
+--temperature is not given; the untruncated arm then runs at 1 as well)."""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -15,8 +17,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rows", choices=("all", "sampler"), default="all")
 ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
 ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
+ap.add_argument("--top-k", type=int, default=None, help="truncated arm: at most K candidates (1..256)")
+ap.add_argument("--top-p", type=float, default=None, help="truncated arm: nucleus mass in (0, 1]")
+ap.add_argument("--min-p", type=float, default=None, help="truncated arm: probability floor relative to the mode, in (0, 1]")
 ap.add_argument("--rounds", type=int, default=5, help="greedy / sampled alternations (with --temperature)")
 args = ap.parse_args()
+trunc = {k: v for k, v in (("top_k", args.top_k), ("top_p", args.top_p), ("min_p", args.min_p)) if v is not None}
+if trunc and args.temperature is None:
+    args.temperature = 1.0
 
 cfg, oc = XLxmertConfig(), O.OracleConfig()
 dev = "cuda"
@@ -74,11 +82,16 @@ for B in (64, 256):
     print(f"sampler T=4     bs {B:4d}: {dt * 1e3:7.2f} ms  {B / dt:9.0f} images/s (codes for the GAN decoder)")
     if args.temperature is not None:
         runs = {"greedy": [], "sampled": []}
+        if trunc:
+            runs["truncated"] = []
         for _ in range(args.rounds):
             runs["greedy"].append(timed(lambda: eng.sample_codes_nar(4), warm=1))
             runs["sampled"].append(timed(lambda: eng.sample_codes_nar(4, temperature=args.temperature, seed=args.seed), warm=1))
+            if trunc:
+                runs["truncated"].append(timed(lambda: eng.sample_codes_nar(4, temperature=args.temperature, seed=args.seed, **trunc), warm=1))
         for k, v in runs.items():
             v = sorted(v)
-            print(f"  {k:8s} bs {B:4d}: median {v[len(v) // 2] * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}"
-                  + (f"  (temperature {args.temperature}, seed {args.seed})" if k == "sampled" else ""))
+            print(f"  {k:9s} bs {B:4d}: median {v[len(v) // 2] * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}"
+                  + (f"  (temperature {args.temperature}, seed {args.seed})" if k == "sampled" else "")
+                  + (f"  ({', '.join(f'{a} {b}' for a, b in trunc.items())})" if k == "truncated" else ""))
     del eng, store

@@ -2337,6 +2337,252 @@ extern "C" int xl_gumbel_from_bits(const uint32_t* h, float* g, int n, void* str
     return XL_OK;
 }
 
+// ---- truncated sampling (top-k / top-p / min-p; semantics: include/xlxmert_hip.h xl_sample_rows_trunc)
+// One 256-thread workgroup per row; thread t owns the columns n = t (mod 256) in every pass, so the cached keys need no barrier.
+//   keys      y = logits * inv_T (one multiply, -0 -> +0) as order-preserving uint32; K <= TRUNC_CACHE_MAX: kept in LDS, the row is
+//             read from memory once; larger rows are read again in every pass
+//   prefilter every thread's maximum is a distinct element, so the smallest of the 256 (or K) thread maxima, keyL, has at least
+//             k_c = min(K, top_k) <= min(K, 256) elements at or above it: the k_c-th largest key is >= keyL, and only the
+//             "survivors" key >= keyL enter the selection (about an eighth of a Gaussian row)
+//   select    d = (key - keyL) << clz(keyMax - keyL) is monotone in key and uses all 32 bits, so the survivors spread over the 256
+//             bins of the first digit whatever their exponents are: 4-pass radix select (8-bit LDS histograms, integer atomics:
+//             counts do not depend on the order) of the k_c-th largest d; it stops early when a bin is taken whole
+//   ties      if more elements equal the threshold than are still to be taken, the lowest columns win: two more passes select the
+//             column threshold the same way (hence K <= 65536)
+//   sort      the k_c candidates (key, ~column) as one uint64 in LDS, bitonic network, descending: rank order
+//   cuts      min-p in parallel (a prefix of the rank order), top-p by ONE thread adding exp(y - max) in rank order (the fixed order
+//             is the contract: the kept count is reproducible bit for bit)
+//   draw      the noise of the kept ranks only; argmax with sample_rows_kernel's tie rule
+constexpr int TRUNC_CACHE_MAX = 12288;          // columns whose keys are kept in LDS (48 KB)
+constexpr int TRUNC_MAX_K = 65536;
+
+__device__ __forceinline__ uint32_t trunc_key(float y) {
+    const uint32_t b = __float_as_uint(y);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float trunc_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// inclusive sum over the 256 threads in thread order (red: 4 words of LDS)
+__device__ __forceinline__ uint32_t trunc_scan_incl(uint32_t v, uint32_t* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    if (lane == 63) red[w] = v;
+    __syncthreads();
+    uint32_t off = 0;
+    for (int i = 0; i < w; ++i) off += red[i];
+    __syncthreads();
+    return v + off;
+}
+
+__global__ __launch_bounds__(256) void sample_rows_trunc_kernel(const float* __restrict__ logits, int K, int ldl, float inv_T,
+                                                                uint64_t seed, int top_k, float top_p, float log_min_p, int cached,
+                                                                float* row_prob, int* row_id, float* row_lse, int* row_kept) {
+    extern __shared__ uint32_t skeys[];
+    __shared__ uint32_t hist[256];
+    __shared__ unsigned long long cand[XL_TRUNC_MAX_CAND];
+    __shared__ float ebuf[XL_TRUNC_MAX_CAND];
+    __shared__ uint32_t red[4];
+    __shared__ float redf[12];
+    __shared__ uint32_t sel[4];
+    __shared__ uint32_t ncand;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int m = blockIdx.x;
+    const float* x = logits + (size_t)m * ldl;
+    auto load_key = [&](int n) -> uint32_t {
+        float y = __fmul_rn(x[n], inv_T);            // one multiply, never contracted into a later add
+        y = y == 0.f ? 0.f : y;                      // -0 -> +0
+        return trunc_key(y);
+    };
+    auto key_at = [&](int n) -> uint32_t { return cached ? skeys[n] : load_key(n); };
+
+    // keys, the row maximum and the prefilter bound
+    uint32_t tmax = 0;                               // (below every finite value's key)
+    auto to_key = [&](float v) -> uint32_t {
+        float y = __fmul_rn(v, inv_T);
+        y = y == 0.f ? 0.f : y;
+        return trunc_key(y);
+    };
+    int n0 = t;
+    for (; n0 + 7 * 256 < K; n0 += 8 * 256) {        // eight loads in flight per thread: the only pass that waits for memory
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = x[n0 + j * 256];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t k = to_key(v[j]);
+            if (cached) skeys[n0 + j * 256] = k;
+            tmax = max(tmax, k);
+        }
+    }
+    for (; n0 < K; n0 += 256) {
+        const uint32_t k = load_key(n0);
+        if (cached) skeys[n0] = k;
+        tmax = max(tmax, k);
+    }
+    uint32_t vmax = tmax, vmin = t < K ? tmax : 0xFFFFFFFFu;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        vmax = max(vmax, (uint32_t)__shfl_xor(vmax, o, 64));
+        vmin = min(vmin, (uint32_t)__shfl_xor(vmin, o, 64));
+    }
+    if (lane == 0) { red[w] = vmax; hist[w] = vmin; }
+    if (t == 0) ncand = 0;
+    cand[t] = 0ull;                                  // sorts behind every real candidate
+    __syncthreads();
+    const uint32_t keyMx = max(max(red[0], red[1]), max(red[2], red[3]));
+    const uint32_t keyL = min(min(hist[0], hist[1]), min(hist[2], hist[3]));
+    const float mx = trunc_unkey(keyMx);
+    __syncthreads();
+
+    // Z over all K columns: serial per thread, butterfly per wave, the four waves in order
+    float se = 0.f;
+    for (int n = t; n < K; n += 256) se += __expf(trunc_unkey(key_at(n)) - mx);
+    se = wave_sum(se);
+    if (lane == 0) redf[w] = se;
+    __syncthreads();
+    const float Z = ((redf[0] + redf[1]) + redf[2]) + redf[3];
+
+    // radix select of the k_c-th largest d among the survivors
+    const uint32_t k_c = (uint32_t)min(K, top_k);
+    const uint32_t range = keyMx - keyL;
+    const int sh = range ? __clz((int)range) : 0;
+    uint32_t prefix = 0, r = k_c, cnt = 0;
+    bool whole = false;                              // the threshold bin is taken whole: no tie to break
+    for (int p = 0; p < 4 && !whole; ++p) {
+        const int s = 24 - 8 * p;
+        const uint32_t himask = p == 0 ? 0u : 0xFFFFFFFFu << (s + 8);
+        hist[t] = 0;
+        __syncthreads();
+        for (int n = t; n < K; n += 256) {
+            const uint32_t k = key_at(n);
+            if (k < keyL) continue;
+            const uint32_t d = (k - keyL) << sh;
+            if ((d & himask) == prefix) atomicAdd(&hist[(d >> s) & 255u], 1u);
+        }
+        __syncthreads();
+        const uint32_t v = hist[255 - t];            // thread order = descending bins
+        const uint32_t incl = trunc_scan_incl(v, red);
+        if (incl >= r && incl - v < r) { sel[0] = 255 - t; sel[1] = r - (incl - v); sel[2] = v; }
+        __syncthreads();
+        prefix |= sel[0] << s;
+        r = sel[1];
+        cnt = sel[2];
+        whole = cnt == r;
+    }
+    const uint32_t dT = prefix;
+    uint32_t colT = 0xFFFFFFFFu;
+    if (!whole) {                                    // cnt > r elements equal dT: the r lowest columns (high byte, then low byte)
+        uint32_t chi = 0;
+        for (int p = 0; p < 2; ++p) {
+            hist[t] = 0;
+            __syncthreads();
+            for (int n = t; n < K; n += 256) {
+                const uint32_t k = key_at(n);
+                if (k < keyL || ((k - keyL) << sh) != dT) continue;
+                if (p == 0) atomicAdd(&hist[(uint32_t)n >> 8], 1u);
+                else if (((uint32_t)n >> 8) == chi) atomicAdd(&hist[n & 255], 1u);
+            }
+            __syncthreads();
+            const uint32_t v = hist[t];              // thread order = ascending bins
+            const uint32_t incl = trunc_scan_incl(v, red);
+            if (incl >= r && incl - v < r) { sel[0] = t; sel[1] = r - (incl - v); }
+            __syncthreads();
+            if (p == 0) chi = sel[0];
+            else colT = (chi << 8) | sel[0];
+            r = sel[1];
+        }
+    }
+
+    // the k_c candidates, in any order, then sorted by (key descending, column ascending)
+    for (int n = t; n < K; n += 256) {
+        const uint32_t k = key_at(n);
+        if (k < keyL) continue;
+        const uint32_t d = (k - keyL) << sh;
+        if (d > dT || (d == dT && (uint32_t)n <= colT)) {
+            const uint32_t pos = atomicAdd(&ncand, 1u);
+            if (pos < (uint32_t)XL_TRUNC_MAX_CAND) cand[pos] = ((unsigned long long)k << 32) | (0xFFFFFFFFu - (uint32_t)n);
+        }
+    }
+    __syncthreads();
+    for (int kk = 2; kk <= XL_TRUNC_MAX_CAND; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            const int q = t ^ j;
+            if (q > t) {
+                const unsigned long long a = cand[t], b = cand[q];
+                if ((a < b) == ((t & kk) == 0)) { cand[t] = b; cand[q] = a; }
+            }
+            __syncthreads();
+        }
+
+    // cuts: thread t is rank t
+    const unsigned long long c = cand[t];
+    const uint32_t col = 0xFFFFFFFFu - (uint32_t)c;
+    const float y = trunc_unkey((uint32_t)(c >> 32));
+    const bool valid = (uint32_t)t < k_c;
+    ebuf[t] = valid ? __expf(y - mx) : 0.f;
+    const uint32_t k_m = (uint32_t)__syncthreads_count(valid && y >= mx + log_min_p);      // (rank 0: y == mx, always kept)
+    if (top_p < 1.f) {
+        if (t == 0) {
+            const float lim = __fmul_rn(top_p, Z);
+            float acc = 0.f;
+            uint32_t n_keep = 0;
+            for (uint32_t q = 0; q < k_m; ++q) {
+                if (q > 0 && !(acc < lim)) break;
+                ++n_keep;
+                acc += ebuf[q];
+            }
+            sel[3] = n_keep;
+        }
+        __syncthreads();
+    }
+    const uint32_t k_s = top_p < 1.f ? sel[3] : k_m;
+
+    // draw among the kept ranks
+    float z = -INFINITY, ys = y;
+    uint32_t s = 0xFFFFFFFFu;
+    if ((uint32_t)t < k_s) { z = y + gumbel_noise(seed, (uint32_t)m, col); s = col; }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float oz = __shfl_xor(z, o, 64), oys = __shfl_xor(ys, o, 64);
+        const uint32_t os = __shfl_xor(s, o, 64);
+        const bool take = oz > z || (oz == z && os < s);
+        z = take ? oz : z; ys = take ? oys : ys; s = take ? os : s;
+    }
+    if (lane == 0) { redf[w] = z; redf[4 + w] = ys; redf[8 + w] = __uint_as_float(s); }
+    __syncthreads();
+    if (t != 0) return;
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+        const float oz = redf[i], oys = redf[4 + i];
+        const uint32_t os = __float_as_uint(redf[8 + i]);
+        const bool take = oz > z || (oz == z && os < s);
+        z = take ? oz : z; ys = take ? oys : ys; s = take ? os : s;
+    }
+    const float lse = mx + logf(Z);
+    if (row_id) row_id[m] = (int)s;
+    if (row_prob) row_prob[m] = expf(ys - lse);
+    if (row_lse) row_lse[m] = lse;
+    if (row_kept) row_kept[m] = (int)k_s;
+}
+
+extern "C" int xl_sample_rows_trunc(const float* logits, int M, int K, int ldl, float inv_T, uint64_t seed, int top_k, float top_p,
+                                    float log_min_p, float* row_prob, int32_t* row_id, float* row_lse, int32_t* row_kept, void* stream) {
+    XL_CHECK_ARG(logits && M > 0 && K > 0 && K <= TRUNC_MAX_K && ldl >= K && inv_T > 0.f && inv_T < INFINITY, XL_ERR_BAD_ARG,
+                 "xl_sample_rows_trunc: M=%d K=%d (at most %d) ldl=%d inv_T=%g", M, K, TRUNC_MAX_K, ldl, (double)inv_T);
+    XL_CHECK_ARG(top_k >= 1 && top_k <= XL_TRUNC_MAX_CAND && top_p > 0.f && log_min_p <= 0.f, XL_ERR_BAD_ARG,
+                 "xl_sample_rows_trunc: top_k=%d (1..%d) top_p=%g (> 0) log_min_p=%g (<= 0, -inf = off)", top_k, XL_TRUNC_MAX_CAND,
+                 (double)top_p, (double)log_min_p);
+    const int cached = K <= TRUNC_CACHE_MAX;
+    hipLaunchKernelGGL(sample_rows_trunc_kernel, dim3(M), dim3(256), cached ? (size_t)K * sizeof(uint32_t) : 0, (hipStream_t)stream,
+                       logits, K, ldl, inv_T, seed, top_k, top_p, log_min_p, cached, row_prob, row_id, row_lse, row_kept);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
 extern "C" int xl_gather_labels(const int64_t* labels, const int* rows, int64_t* out, int n_rows, void* stream) {
     XL_CHECK_ARG(labels && rows && out && n_rows > 0, XL_ERR_BAD_ARG, "xl_gather_labels: bad args (n_rows=%d)", n_rows);
     hipLaunchKernelGGL(gather_labels_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, labels, rows, out, n_rows);

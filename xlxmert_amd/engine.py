@@ -2002,8 +2002,10 @@ class Engine:
         self.ops.rowmax_combine(self._rowmax_ws, Kq // 64, self.MV, self.row_maxprob, self.row_argmax, self.row_lse)
         return self.row_maxprob, self.row_argmax
 
-    def _predict_step(self, fused, temperature=None, seed=0):
-        if temperature is not None:
+    def _predict_step(self, fused, temperature=None, seed=0, trunc=None):
+        if trunc is not None:
+            self._sample_step_trunc(temperature, seed, trunc)
+        elif temperature is not None:
             self._sample_step(fused, temperature, seed)
         elif fused:
             self.head_forward(want_logits=False)
@@ -2054,7 +2056,39 @@ class Engine:
             self.ops.sample_rows(self.logits, self.MV, self.K, self.K, inv_T, launch_seed, self.row_maxprob, self.row_argmax,
                                  self.row_lse)
 
-    def sample_codes_nar(self, n_steps=4, on_step=None, *, temperature=None, seed=0):
+    # Truncated sampling: top-k, top-p (nucleus) and min-p next to the temperature (include/xlxmert_hip.h xl_sample_rows_trunc states
+    # the semantics).  Any of the three given: the step materialises the fp32 logits (head_forward) and draws with
+    # xl_sample_rows_trunc, for fp32 and bf16 alike -- also where the fused predict path is available: truncation needs a row's
+    # logits ranked, which the fused epilogue never has in memory.  Same noise function and launch seed as the temperature path: a
+    # truncated draw equals the untruncated one whenever that lies in the kept set.  row_maxprob stays the probability under the
+    # FULL tempered softmax (a confidence for the re-masking and the `confidence` policy); row_kept holds the kept-set sizes.
+    # top-p and min-p act within at most TRUNC_MAX_CAND = 256 candidates (row_kept == 256 reveals the cap).
+    TRUNC_MAX_CAND = 256
+
+    @classmethod
+    def check_truncation(cls, top_k, top_p, min_p):
+        """None (no truncation argument given), or (top_k, top_p, log_min_p) as xl_sample_rows_trunc takes them"""
+        if top_k is None and top_p is None and min_p is None:
+            return None
+        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not (1 <= top_k <= cls.TRUNC_MAX_CAND)):
+            raise ValueError(f"top_k {top_k!r}: an int in [1, {cls.TRUNC_MAX_CAND}] (None = {cls.TRUNC_MAX_CAND} candidates)")
+        for name, v in (("top_p", top_p), ("min_p", min_p)):
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not (0.0 < v <= 1.0):
+                raise ValueError(f"{name} {v!r}: a finite float in (0, 1] (None = off)")
+        return (cls.TRUNC_MAX_CAND if top_k is None else top_k, 1.0 if top_p is None else float(top_p),
+                -math.inf if min_p is None else math.log(float(min_p)))
+
+    def _sample_step_trunc(self, temperature, launch_seed, trunc):
+        if getattr(self, "row_kept", None) is None:
+            self.row_kept = torch.zeros(self.MV, dtype=torch.int32, device=self.dev)
+        top_k, top_p, log_min_p = trunc
+        self.head_forward()
+        self.ops.sample_rows_trunc(self.logits, self.MV, self.K, self.K, 1.0 / (1.0 if temperature is None else temperature), launch_seed,
+                                   top_k, top_p, log_min_p, self.row_maxprob, self.row_argmax, self.row_lse, self.row_kept)
+
+    def sample_codes_nar(self, n_steps=4, on_step=None, *, temperature=None, seed=0, top_k=None, top_p=None, min_p=None):
         """Iterative Mask-Predict sampling (ref tasks/imggen_model.py:169-243) without a host round trip between steps:
         re-mask the lowest-confidence positions -> encoder -> codebook head -> softmax-max / argmax -> keep the predictions
         of the masked positions.  Text inputs come from set_inputs (cluster_ids / vis_mask there are placeholders).
@@ -2063,13 +2097,16 @@ class Engine:
         on_step(i): called after step i's update (return_intermediate of the reference, :245-248: materialise_codes() gives the
         code tensor of that moment).
         temperature (None = greedy, exactly the calls above): every position draws its code from softmax(logits / temperature),
-        reproducibly for one `seed`; the confidence of the re-masking is the tempered probability of the drawn code."""
+        reproducibly for one `seed`; the confidence of the re-masking is the tempered probability of the drawn code.
+        top_k / top_p / min_p (any given: truncated sampling, temperature None meaning 1): the draw is restricted to the kept set
+        of check_truncation's comment; self.row_kept holds its sizes."""
         temperature = self.check_temperature(temperature)
+        trunc = self.check_truncation(top_k, top_p, min_p)
         ops, B, V = self.ops, self.B, self.V
         st = self.store
         self.use_codebook, self.has_vmask = True, True
         self.cid.zero_()
-        fused = self.fused_predict_available()
+        fused = trunc is None and self.fused_predict_available()
         if fused:
             self._prepare_fused_predict()
             if temperature is not None:
@@ -2085,7 +2122,7 @@ class Engine:
                 self.encoder_forward(want_pooled=False)                    # codebook_gather == where(mask, mask_feat, vis_emb(ids))
             finally:
                 self._reuse_lang_stack = False
-            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i))
+            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i), trunc)
             ops.sampler_update(self.row_argmax, self.vmask, self.cid, B * V)
             if on_step is not None:
                 on_step(i)
@@ -2100,13 +2137,15 @@ class Engine:
                                  self.MV, self.F)
         return self.feats
 
-    def sample_codes_ar(self, n_steps=None, mode="confidence", positions=None, trace=None, on_step=None, *, temperature=None, seed=0):
+    def sample_codes_ar(self, n_steps=None, mode="confidence", positions=None, trace=None, on_step=None, *, temperature=None, seed=0,
+                        top_k=None, top_p=None, min_p=None):
         """Autoregressive sampling (ref tasks/imggen_model.py:49-153): one grid position per image is filled per step --
         the most confident not-yet-visited one ("confidence", the reference's default), position i ("tlbr"), or the host's
         shuffled order popped from the end ("random", positions = that list).  Same device-resident state as
         sample_codes_nar; `trace` (a list) receives a copy of vis_mask after every step.  temperature / seed: as in sample_codes_nar
-        (the `confidence` policy ranks positions by the tempered probability of their drawn code)."""
+        (the `confidence` policy ranks positions by the tempered probability of their drawn code); top_k / top_p / min_p likewise."""
         temperature = self.check_temperature(temperature)
+        trunc = self.check_truncation(top_k, top_p, min_p)
         ops, B, V = self.ops, self.B, self.V
         st = self.store
         n_steps = V if n_steps is None else n_steps
@@ -2117,7 +2156,7 @@ class Engine:
             self.visited = torch.zeros(B, V, dtype=torch.uint8, device=self.dev)
         self.visited.zero_()
         positions = list(positions) if positions is not None else None
-        fused = self.fused_predict_available()
+        fused = trunc is None and self.fused_predict_available()
         if fused:
             self._prepare_fused_predict()
             if temperature is not None:
@@ -2134,7 +2173,7 @@ class Engine:
                 self.encoder_forward(want_pooled=False)
             finally:
                 self._reuse_lang_stack = False
-            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i))
+            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i), trunc)
             ops.sampler_ar_update(self.row_maxprob, self.row_argmax, self.visited, self.vmask, self.cid, B, V, cur)
             if trace is not None:
                 trace.append(self.vmask.clone())

@@ -260,6 +260,20 @@ def _sample_seed(seed):
     return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
 
 
+def _truncation_kw(top_k, top_p, min_p):
+    """the truncation keywords that were given, validated (Engine.check_truncation); {} = none: the call lists of before"""
+    Engine.check_truncation(top_k, top_p, min_p)
+    return {k: v for k, v in (("top_k", top_k), ("top_p", top_p), ("min_p", min_p)) if v is not None}
+
+
+def _sampling_kw(temperature, sample_seed, top_k, top_p, min_p):
+    """keywords of Engine.sample_codes_nar / _ar for the ImggenModel surface; {} = the greedy loop"""
+    trunc = _truncation_kw(top_k, top_p, min_p)
+    if temperature is None and not trunc:
+        return {}
+    return {"temperature": temperature, "seed": _sample_seed(sample_seed), **trunc}
+
+
 class XLxmertForPretraining(nn.Module):
     """ref lxrt/modeling.py:56-308: `.bert`, `.cls` (task_mask_lm or task_matched), `.obj_predict_head` (task_obj_predict),
     `.answer_head` (task_qa), `.mask_feat`, `.vis_emb`; forward(task = 'vis_mask' | 'word_mask' | 'matched' | 'qa')."""
@@ -381,14 +395,16 @@ class XLxmertForPretraining(nn.Module):
         return out_dict
 
     @torch.no_grad()
-    def sample_codes(self, input_ids, n_steps=4, grid_size=8, *, temperature=None, seed=None):
+    def sample_codes(self, input_ids, n_steps=4, grid_size=8, *, temperature=None, seed=None, top_k=None, top_p=None, min_p=None):
         """The device part of ImggenModel.sample_image_NAR (ref tasks/imggen_model.py:169-254): Mask-Predict sampling of
         the grid codes, returned as the generator's input `[B, feat_dim, grid, grid]` (fp32) plus the chosen code ids.
         Tokenisation (before) and the frozen GAN `G(code)` + denorm (after) stay with the caller, as in the reference.
         temperature (None = the reference's greedy choice): draw every code from softmax(logits / temperature); seed=None takes
-        one from torch's default CPU generator (torch.manual_seed governs)."""
+        one from torch's default CPU generator (torch.manual_seed governs).  top_k / top_p / min_p (any given; temperature None
+        then means 1): the draw is truncated as Engine.check_truncation describes."""
         import numpy as np
         temperature = Engine.check_temperature(temperature)
+        trunc = _truncation_kw(top_k, top_p, min_p)
         if self.vis_emb is None:
             raise RuntimeError("call set_visual_embedding(centroids) first")
         was_training = self.training
@@ -404,10 +420,10 @@ class XLxmertForPretraining(nn.Module):
         eng.set_inputs(input_ids, input_ids > 0, None, torch.from_numpy(pos).to(dev).unsqueeze(0).expand(B, -1, -1),
                        cluster_ids=torch.zeros(B, V, dtype=torch.long, device=dev),
                        vis_mask=torch.ones(B, V, dtype=torch.bool, device=dev))
-        if temperature is None:
+        if temperature is None and not trunc:
             cid, code, _ = eng.sample_codes_nar(n_steps)
         else:
-            cid, code, _ = eng.sample_codes_nar(n_steps, temperature=temperature, seed=_sample_seed(seed))
+            cid, code, _ = eng.sample_codes_nar(n_steps, temperature=temperature, seed=_sample_seed(seed), **trunc)
         out = code.view(B, V, -1).permute(0, 2, 1).reshape(B, -1, grid_size, grid_size).float()
         self.train(was_training)
         return out, cid.clone()
@@ -608,12 +624,14 @@ class ImggenModel(XLxmertForPretraining):
 
     @torch.no_grad()
     def sample_image_NAR(self, sentences, max_text_length=20, n_steps=None, return_intermediate=False, *, temperature=None,
-                         sample_seed=None):
+                         sample_seed=None, top_k=None, top_p=None, min_p=None):
         """ref :169-257.  n_steps=None -> grid_size ** 2 (ref :191-192).  temperature (beyond the reference; None = its greedy
         choice): every position draws its code from softmax(logits / temperature) -- different, reproducible images per caption;
-        sample_seed=None takes a seed from torch's default CPU generator."""
+        sample_seed=None takes a seed from torch's default CPU generator.  top_k / top_p / min_p (any given; temperature None then
+        means 1): the draw keeps to the top_k most probable codes, the shortest prefix of mass top_p, the codes of at least min_p
+        times the mode's probability (Engine.check_truncation)."""
         temperature = Engine.check_temperature(temperature)
-        kw = {} if temperature is None else {"temperature": temperature, "seed": _sample_seed(sample_seed)}
+        kw = _sampling_kw(temperature, sample_seed, top_k, top_p, min_p)
         eng, B, V = self._prepare(self._input_ids(sentences, max_text_length))
         n_steps = V if n_steps is None else n_steps
         imgs = []
@@ -624,13 +642,14 @@ class ImggenModel(XLxmertForPretraining):
 
     @torch.no_grad()
     def sample_image_AR(self, sentences, max_text_length=20, position_random=False, position_TLBR=False, position_confidence=True,
-                        n_steps=None, seed=None, return_intermediate=False, *, temperature=None, sample_seed=None):
+                        n_steps=None, seed=None, return_intermediate=False, *, temperature=None, sample_seed=None, top_k=None,
+                        top_p=None, min_p=None):
         """ref :49-167: the three position policies with the reference's precedence (random, else TLBR, else confidence) and its
         host-side order for `position_random` (random.Random(seed).shuffle, extended for n_steps > grid ** 2, :77-89).
-        temperature / sample_seed: as in sample_image_NAR (`seed` keeps meaning the position order)."""
+        temperature / sample_seed / top_k / top_p / min_p: as in sample_image_NAR (`seed` keeps meaning the position order)."""
         import random
         temperature = Engine.check_temperature(temperature)
-        kw = {} if temperature is None else {"temperature": temperature, "seed": _sample_seed(sample_seed)}
+        kw = _sampling_kw(temperature, sample_seed, top_k, top_p, min_p)
         eng, B, V = self._prepare(self._input_ids(sentences, max_text_length))
         n_steps = V if n_steps is None else n_steps
         positions = None

@@ -437,6 +437,12 @@ class HipOps:
         self._call("xl_sample_rows", self._p(logits), M, K, ldl, float(inv_T), int(seed), self._p(row_prob), self._p(row_id),
                    self._p(row_lse), self._stream())
 
+    def sample_rows_trunc(self, logits, M, K, ldl, inv_T, seed, top_k, top_p, log_min_p, row_prob, row_id, row_lse=None, row_kept=None):
+        """sample_rows restricted to the first row_kept[m] ranks of (y descending, column ascending): at most top_k (1..256)
+        candidates, cut by min-p (log_min_p = log(min_p), -inf = off) and top-p (>= 1 = off) -- xl_sample_rows_trunc."""
+        self._call("xl_sample_rows_trunc", self._p(logits), M, K, ldl, float(inv_T), int(seed), int(top_k), float(top_p), float(log_min_p),
+                   self._p(row_prob), self._p(row_id), self._p(row_lse), self._p(row_kept), self._stream())
+
     def gumbel_from_bits(self, h, g, n):
         """test export: g[i] = the float part of the samplers' noise on the hash words h[i] (int32 storage of the uint32 bits)"""
         self._call("xl_gumbel_from_bits", self._p(h), self._p(g), n, self._stream())
