@@ -280,6 +280,35 @@ int xl_sampler_update(const int* pred_ids, const void* vis_mask, int64_t* code_i
  * `visited` uint8 [B,V] is updated). */
 int xl_sampler_ar_update(const float* prob, const int* pred_ids, void* visited, void* vis_mask, int64_t* code_ids,
                          int B, int V, int fixed_pos, void* stream);
+/* Mask-Predict CAPTION sampler: the word-side twin of the loop above over the MLM head (the reference trains that head with
+ * Mask-Predict masking, ref pretrain/lxmert_data.py:510,551, and runs the loop on the visual side only, tasks/imggen_model.py:
+ * 199-243).  Row b of the token matrix [B, L] is [CLS], P prefix ids, n_b free positions, [SEP], [PAD] to L: the free positions are
+ * P+1 <= l < P+1+n_b, the real ones l < P+n_b+2.  xl_caption_step runs between two forwards, one launch, one wave per caption
+ * (L <= 64), after step `step` of `n_steps` (0 <= step < n_steps), on
+ *   row_prob / row_id   fp32 / int32, per row of the head's input matrix: probability and id of the predicted (or drawn) token;
+ *                       the row of position (b, l) is b*L + l, or lang_off[b] + l with packed language rows (lang_off: int32
+ *                       [B+1], NULL = dense) -- the same row that the samplers' noise function is given
+ *   lengths             int32 [B], n_b.  The host cannot check them without a round trip: the kernel CLAMPS n_b to [0, L-2-P], and with
+ *                       lang_off also to the rows that example b owns (lang_off[b+1] - lang_off[b] - 2 - P), so no row of another
+ *                       caption is ever read.  n_b = 0 after clamping: the row only gets its fed_ids / word_mask / conf / score = 0.
+ *   tokens, fed_ids     int64 [B, L];  word_mask uint8 [B, L];  conf fp32 [B, L];  score fp32 [B]
+ * in this order:
+ *   1 commit    tokens[b,l] = row_id at the free positions with word_mask set.  Nothing else is written to tokens.
+ *   2 conf      conf[b,l] = row_prob at EVERY free position (the latest forward's probability of its prediction there, ref
+ *               imggen_model.py:232-235 pred_prob); 0 at the other positions.
+ *   3 score     score[b] = (1/n_b) sum over the free positions of log conf[b,l] (logf, added by a fixed-order wave butterfly: the same
+ *               bits on every run); after the last step it is the caption's mean log-probability.
+ *   4 repeats   suppress_repeats != 0: conf[b,l] = -1 at the free positions with tokens[b,l] == tokens[b,l-1], evaluated on the
+ *               committed tokens of all positions at once (l-1 may be a prefix position): repeats are re-masked first.
+ *   5 re-mask   step + 1 < n_steps: n_mask = (n_b * (n_steps - step - 1)) / n_steps in INTEGER division (exact, computed per row on
+ *               the device; the reference's image loop uses the float int(ratio * V)); word_mask = 1 at the first n_mask free
+ *               positions ranked by (conf ascending, l ascending), 0 at every other position of the row.  n_mask = 0 is legal.
+ *               step + 1 == n_steps: word_mask is left as the last forward read it.
+ *   6 fed ids   fed_ids[b,l] = word_mask[b,l] ? mask_token_id : tokens[b,l] for l < P+n_b+2, 0 ([PAD]) beyond.
+ * XL_ERR_BAD_ARG without a launch: a NULL buffer other than lang_off, L > 64, P < 0, L-2-P < 1, step outside [0, n_steps). */
+int xl_caption_step(const float* row_prob, const int* row_id, const int* lang_off, const int* lengths, int64_t* tokens,
+                    int64_t* fed_ids, void* word_mask, float* conf, float* score, int B, int L, int P, int step, int n_steps,
+                    int mask_token_id, int suppress_repeats, void* stream);
 
 /* ---------------------------------------------------------------- attention core (HF:247-263)
  * per (b,h): O = softmax(Q K^T * scale, keys with key_mask==0 excluded) V ; nq, nk <= 64 on the on-chip kernels (the path's

@@ -1,6 +1,8 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py [--rows all|sampler] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+Usage: python tools/task_bench.py [--rows all|sampler|caption] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+--rows caption: the Mask-Predict caption sampler alone (bs 256, L = 20, T = 10, ragged lengths): ms per batch and captions/s, greedy on
+the fused and on the logits predict path and with the visual stack recomputed every step, in one alternation with the arms below.
 --temperature: the sampler rows are timed greedy AND with temperature sampling, alternating in this process (rounds of 8 loops
 each; the line gives the median and the min..max spread of both).
 --top-k / --top-p / --min-p (any of them): a third arm in the same alternation, the truncated sampler at that temperature (1 if
@@ -14,7 +16,7 @@ from xlxmert_amd.config import XLxmertConfig
 from xlxmert_amd.trainer import PretrainStep, word_rows_of
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--rows", choices=("all", "sampler"), default="all")
+ap.add_argument("--rows", choices=("all", "sampler", "caption"), default="all")
 ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
 ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
 ap.add_argument("--top-k", type=int, default=None, help="truncated arm: at most K candidates (1..256)")
@@ -68,7 +70,7 @@ from xlxmert_amd.engine import Engine
 from xlxmert_amd.ops import HipOps
 from xlxmert_amd.params import ParamStore
 from xlxmert_amd.trainer import init_reference_weights
-for B in (64, 256):
+for B in (64, 256) if args.rows != "caption" else ():
     store = ParamStore(cfg, dev, torch.bfloat16, task="vis_mask")
     init_reference_weights(store, 1)
     g = torch.Generator().manual_seed(0)
@@ -95,3 +97,50 @@ for B in (64, 256):
                   + (f"  (temperature {args.temperature}, seed {args.seed})" if k == "sampled" else "")
                   + (f"  ({', '.join(f'{a} {b}' for a, b in trunc.items())})" if k == "truncated" else ""))
     del eng, store
+
+
+def caption_row(B=256, L=20, T=10):
+    store = ParamStore(cfg, dev, torch.bfloat16, task="word_mask")
+    init_reference_weights(store, 1)
+    g = torch.Generator().manual_seed(0)
+    store.set_centroids(torch.randn(cfg.num_clusters, cfg.visual_feat_dim, generator=g).relu())
+    eng = Engine(cfg, store, HipOps(torch.bfloat16), B, L, 64, need_lang=True)
+    eng.sync_compute_weights()
+    lens = torch.randint(4, L - 1, (B,), generator=g)                    # 4 .. 18 free tokens
+    pos = torch.arange(L).view(1, L)
+    ids = torch.zeros(B, L, dtype=torch.long)
+    ids[:, 0] = 101
+    ids[pos == lens.view(B, 1) + 1] = 102
+    att = pos < lens.view(B, 1) + 2
+    inp = O.make_inputs(oc, 4, B, L, 8)
+    eng.set_inputs(ids.cuda(), att.cuda(), None, inp["visual_pos"].cuda(), cluster_ids=torch.randint(0, cfg.num_clusters, (B, 64), generator=g).cuda(),
+                   lang_rows=att.reshape(-1).nonzero().reshape(-1).cuda(), lang_off=torch.cat([lens.new_zeros(1), (lens + 2).cumsum(0)]).cuda())
+
+    def loop(reuse=True, fused=True, **kw):
+        eng.reuse_vis_stack = reuse
+        os.environ["XL_FUSED_PREDICT"] = "1" if fused else "0"
+        try:
+            eng.sample_words_nar(lens, T, **kw)
+        finally:
+            eng.reuse_vis_stack = True
+            os.environ["XL_FUSED_PREDICT"] = "1"
+    arms = {"greedy": {}, "greedy logits path": dict(fused=False), "greedy no vis reuse": dict(reuse=False)}
+    if args.temperature is not None:
+        arms["sampled"] = dict(temperature=args.temperature, seed=args.seed)
+        arms["sampled logits path"] = dict(temperature=args.temperature, seed=args.seed, fused=False)
+    if trunc:
+        arms["truncated"] = dict(temperature=args.temperature, seed=args.seed, **trunc)
+    runs = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for k, kw in arms.items():
+            runs[k].append(timed(lambda: loop(**kw), n=4, warm=1))
+    print(f"caption T={T}    bs {B:4d}, L {L}, {eng.ML} head rows ({'packed' if eng.packed else 'dense'}), fused predict "
+          f"{'available' if eng.lang_heads.fused_predict_available() else 'not available'}")
+    for k, v in runs.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        print(f"  {k:20s}: median {med * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}  {B / med:9.0f} captions/s")
+
+
+if args.rows in ("all", "caption"):
+    caption_row()

@@ -1666,6 +1666,59 @@ __global__ __launch_bounds__(256) void sampler_ar_update_kernel(const float* __r
     }
 }
 
+// Mask-Predict caption step (include/xlxmert_hip.h xl_caption_step states the six rules): the word-side twin of remask_lowest +
+// sampler_update, one wave per caption, lane l = token position (L <= 64).  Everything a lane decides it decides from values that
+// shuffles hand it: no LDS, no atomics; the score is a fixed-order butterfly sum.
+__global__ __launch_bounds__(256) void caption_step_kernel(const float* __restrict__ row_prob, const int* __restrict__ row_id,
+                                                           const int* __restrict__ lang_off, const int* __restrict__ lengths,
+                                                           int64_t* __restrict__ tokens, int64_t* __restrict__ fed_ids,
+                                                           uint8_t* __restrict__ word_mask, float* __restrict__ conf,
+                                                           float* __restrict__ score, int B, int L, int P, int step, int n_steps,
+                                                           int mask_token_id, int suppress_repeats) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    int n = min(max(lengths[b], 0), L - 2 - P);                      // free tokens of this caption, clamped into the layout
+    int row0 = b * L;                                                // first row of the caption in the head's input matrix
+    if (lang_off != nullptr) {
+        row0 = lang_off[b];
+        n = min(n, max(lang_off[b + 1] - row0 - 2 - P, 0));          // never read a row of the next caption
+    }
+    const bool in_row = lane < L;
+    const bool is_free = lane >= P + 1 && lane < P + 1 + n;
+    const size_t i = (size_t)b * L + (in_row ? lane : 0);
+    int64_t tok = in_row ? tokens[i] : -1;
+    // 1. commit the prediction where the position was masked in this forward
+    if (is_free && word_mask[i] != 0) {
+        tok = row_id[row0 + lane];
+        tokens[i] = tok;
+    }
+    // 2. confidence of the latest forward at every free position
+    float c = is_free ? row_prob[row0 + lane] : 0.f;
+    // 3. mean log-probability over the free positions (before the repeat rule rewrites any confidence)
+    float s = is_free ? logf(c) : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) score[b] = n > 0 ? s / (float)n : 0.f;
+    // 4. a free token equal to its left neighbour (committed tokens, all positions at once) is re-masked first
+    const int64_t left = __shfl_up(tok, 1, 64);
+    if (suppress_repeats && is_free && tok == left) c = -1.0f;
+    if (in_row) conf[i] = c;
+    // 5. the mask of the next forward: the n_mask lowest (confidence, position) among the free positions
+    uint8_t m = in_row ? word_mask[i] : 0;
+    if (step + 1 < n_steps) {
+        const int n_mask = (int)(((long long)n * (n_steps - step - 1)) / n_steps);
+        int rank = 0;
+        for (int j = P + 1; j < P + 1 + n; ++j) {
+            const float other = __shfl(c, j, 64);
+            rank += (other < c || (other == c && j < lane)) ? 1 : 0;
+        }
+        m = (is_free && rank < n_mask) ? 1 : 0;
+        if (in_row) word_mask[i] = m;
+    }
+    // 6. the ids the next forward reads
+    if (in_row) fed_ids[i] = lane < P + n + 2 ? (m ? (int64_t)mask_token_id : tok) : 0;
+}
+
 }  // namespace xl
 
 using namespace xl;
@@ -2586,6 +2639,21 @@ extern "C" int xl_sample_rows_trunc(const float* logits, int M, int K, int ldl, 
 extern "C" int xl_gather_labels(const int64_t* labels, const int* rows, int64_t* out, int n_rows, void* stream) {
     XL_CHECK_ARG(labels && rows && out && n_rows > 0, XL_ERR_BAD_ARG, "xl_gather_labels: bad args (n_rows=%d)", n_rows);
     hipLaunchKernelGGL(gather_labels_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, labels, rows, out, n_rows);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
+extern "C" int xl_caption_step(const float* row_prob, const int* row_id, const int* lang_off, const int* lengths, int64_t* tokens,
+                               int64_t* fed_ids, void* word_mask, float* conf, float* score, int B, int L, int P, int step,
+                               int n_steps, int mask_token_id, int suppress_repeats, void* stream) {
+    XL_CHECK_ARG(row_prob && row_id && lengths && tokens && fed_ids && word_mask && conf && score, XL_ERR_BAD_ARG,
+                 "xl_caption_step: null argument (only lang_off may be NULL) B=%d L=%d", B, L);
+    XL_CHECK_ARG(B > 0 && L > 0 && L <= 64 && P >= 0 && L - 2 - P >= 1 && n_steps >= 1 && step >= 0 && step < n_steps && mask_token_id >= 0,
+                 XL_ERR_BAD_ARG, "xl_caption_step: B=%d L=%d (<= 64) P=%d (L-2-P >= 1) step=%d n_steps=%d mask_token_id=%d", B, L, P, step,
+                 n_steps, mask_token_id);
+    hipLaunchKernelGGL(caption_step_kernel, dim3((B + WPB - 1) / WPB), dim3(256), 0, (hipStream_t)stream, row_prob, row_id, lang_off,
+                       lengths, tokens, fed_ids, (uint8_t*)word_mask, conf, score, B, L, P, step, n_steps, mask_token_id,
+                       suppress_repeats);
     XL_CHECK_LAUNCH();
     return XL_OK;
 }

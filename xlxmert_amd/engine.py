@@ -600,6 +600,88 @@ class LangHeads:
             ops.gemm(dpre, self.wt, d_lang, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **e.rkw)
         return self.loss
 
+    # ---- prediction over the vocabulary (caption sampler, Engine.sample_words_nar): the word-side twin of Engine._predict_step.
+    # The head runs on the rows of the last cross layer's language output AS THEY LIE -- packed rows lang_off[b] + l (rounded up to the
+    # row tile with zero rows) or dense rows b*L + l -- and leaves per row the predicted / drawn token id, its probability and the
+    # log-sum-exp.  Banned ids are -1e30 in the decoder bias, the mechanism of the codebook's pad columns: every path below (fused,
+    # logits, truncated) excludes them without a line of kernel code.
+    def fused_predict_available(self):
+        e = self.e
+        return (e.cdtype == torch.bfloat16 and e.ML % 256 == 0 and e.d % 8 == 0 and hasattr(e.ops, "rowmax_combine")
+                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
+
+    def _prepare_predict(self, banned_ids):
+        """buffers of the predict paths (row capacity MLc: a packed row count is rounded up to the row tile, which may exceed B*L)
+        and the decoder bias with the banned ids at -1e30"""
+        e, d = self.e, self.e.d
+        Mc = e.MLc
+        if getattr(self, "p_hn", None) is None:
+            own = Mc > e.MLd
+            self.p_pre, self.p_h, self.p_hn = (e.act(Mc, d) for _ in range(3)) if own else (self.pre, self.h, self.hn)
+            self.p_mean, self.p_rstd = (e.f32(Mc), e.f32(Mc)) if own else (self.mean, self.rstd)
+            self.p_scores = torch.zeros(Mc, self.Vp, dtype=torch.float32, device=e.dev) if own else self.scores
+            self.row_prob, self.row_lse = e.f32(Mc), e.f32(Mc)
+            self.row_id = torch.zeros(Mc, dtype=torch.int32, device=e.dev)
+            self.row_kept = torch.zeros(Mc, dtype=torch.int32, device=e.dev)
+            self.vb_ban = torch.zeros(self.Vp, dtype=torch.float32, device=e.dev)
+        self.vb_ban[:self.Vn].copy_(self.vb)
+        if self.Vp > self.Vn:
+            self.vb_ban[self.Vn:].fill_(-1e30)
+        ban = torch.as_tensor(banned_ids, dtype=torch.int64).reshape(-1)
+        if ban.numel() and (int(ban.min()) < 0 or int(ban.max()) >= self.Vn):
+            raise ValueError(f"banned_ids outside the vocabulary [0, {self.Vn})")
+        if ban.numel() >= self.Vn or ban.unique().numel() >= self.Vn:
+            raise ValueError("banned_ids leaves no token to predict")
+        self.vb_ban[ban.to(e.dev)] = -1e30
+
+    def _prepare_fused_predict(self):
+        """after _prepare_predict: the tied word-embedding matrix as a bf16 operand padded to a multiple of 256 rows (30522 -> 30720,
+        zero rows), the banned bias padded with -1e30, the segment workspace of the row-max / row-sample epilogues"""
+        e = self.e
+        Vq = (self.Vn + 255) // 256 * 256
+        if getattr(self, "_emb_pad", None) is None:
+            self._emb_pad = torch.zeros(Vq, e.d, dtype=e.cdtype, device=e.dev)
+            self._bias_pad = torch.full((Vq,), -1e30, dtype=torch.float32, device=e.dev)
+            self._bias_pad_T = torch.empty_like(self._bias_pad)
+            self._seg_ws = torch.zeros((Vq // 64) * e.MLc * 4, dtype=torch.float32, device=e.dev)
+        self._emb_pad[:self.Vn].copy_(e.store.cview("bert.embeddings.word_embeddings.weight"))
+        self._bias_pad[:self.Vn].copy_(self.vb_ban[:self.Vn])
+
+    def _prepare_fused_sample(self, temperature):
+        """the padded bias divided by T (once per loop); banned and pad columns keep -1e30, NOT divided (Engine._prepare_fused_sample)"""
+        self._bias_pad_T.copy_(torch.where(self._bias_pad > -1e29, self._bias_pad * (1.0 / temperature), self._bias_pad))
+
+    def predict(self, lang, M, fused, temperature=None, launch_seed=0, trunc=None):
+        """lang: the head's input rows [M, d].  Fills row_id / row_prob / row_lse[:M]: greedy (softmax-max / argmax), a draw from
+        softmax(logits / temperature), or a truncated draw (always through the logits, as on the image side)."""
+        e, d, Vn, Vp = self.e, self.e.d, self.Vn, self.Vp
+        ops, st = e.ops, e.store
+        ops.block = "head"
+        hn = self.p_hn[:M]
+        ops.gemm(lang, self.wt, self.p_h[:M], self.bt, None, self.p_pre[:M], M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
+        ops.layernorm_fwd(self.p_h[:M], self.g, self.b, hn, self.p_mean, self.p_rstd, M, d, 1e-12)
+        if fused and trunc is None:
+            Vq = self._emb_pad.shape[0]
+            if temperature is None:
+                ops.gemm(hn, self._emb_pad, None, self._bias_pad, None, self._seg_ws, M, Vq, d, d, d, Vq, epilogue=EPI_ROWMAX)
+                ops.rowmax_combine(self._seg_ws, Vq // 64, M, self.row_prob, self.row_id, self.row_lse)
+            else:
+                ops.gemm(hn, self._emb_pad, None, self._bias_pad_T, None, self._seg_ws, M, Vq, d, d, d, Vq, epilogue=EPI_ROWSAMPLE,
+                         alpha=1.0 / temperature, seed=launch_seed)
+                ops.rowsample_combine(self._seg_ws, Vq // 64, M, launch_seed, self.row_prob, self.row_id, self.row_lse)
+            return
+        ops.gemm(hn, st.cview("bert.embeddings.word_embeddings.weight"), self.p_scores, self.vb_ban, None, None,
+                 M, Vn, d, d, d, Vp, out_f32=True)
+        inv_T = 1.0 / (1.0 if temperature is None else temperature)
+        if trunc is not None:
+            top_k, top_p, log_min_p = trunc
+            ops.sample_rows_trunc(self.p_scores, M, Vn, Vp, inv_T, launch_seed, top_k, top_p, log_min_p, self.row_prob, self.row_id,
+                                  self.row_lse, self.row_kept)
+        elif temperature is not None:
+            ops.sample_rows(self.p_scores, M, Vn, Vp, inv_T, launch_seed, self.row_prob, self.row_id, self.row_lse)
+        else:
+            ops.ce_fwd_bwd(self.p_scores, None, None, None, None, self.row_lse, self.row_id, self.row_prob, M, Vn, Vp, Vp, 1.0)
+
     # ---- matched
     def rel_fwd(self, pooled):
         e, d, B = self.e, self.e.d, self.e.B
@@ -1613,29 +1695,10 @@ class Engine:
             sa.fwd(x, mid)
             ffn.fwd(mid, y)
 
-    def _encoder_forward(self, want_pooled=True, ffn_rows=None):
-        cfg, st, ops, d = self.cfg, self.store, self.ops, self.d
-        ML, MV = self.ML, self.MV
-        X0 = self.X[0]
-        last = self.x_layers[-1]
-        if ffn_rows is not None and not (self.compact_last_ffn and last["vis_on"] and not (self.pair_blocks and last["lang_on"])):
-            ffn_rows = None
-        self._ffn_rows_run = ffn_rows
-        for blk in self.x_layers:
-            if blk["vis_on"]:
-                blk["ffn_v"].rows = None
-        self.fork()
-        # samplers: the text does not change between refinement steps and, without dropout, neither does the output of the
-        # language stack (embeddings + l_layers self-attention layers: it never sees the visual tokens) -- it still sits in
-        # the language rows of X[0] from the loop's first pass (no later layer writes there), so the later passes skip it.  Exact.
-        skip_lang = getattr(self, "_reuse_lang_stack", False) and self.p_hid == 0 and self.p_attn == 0
-        pairs = [] if skip_lang else self._stack_pairs()
-        n_lang_alone = cfg.l_layers - len(pairs)
-        n_vis_alone = cfg.r_layers - len(pairs)
-        if not skip_lang:
-            with self.lang_stream():            # ---- language stack (HF:516-521) on the side stream: all of it, or the layers
-                self._language_stack_forward(n_lang_alone)      # that have no visual partner (_stack_pairs)
-        # ---- visual feature encoder + relational stack (HF:513, 524-529) on the main stream
+    def _visual_stack_forward(self, n_layers):
+        """visual feature encoder + the first n_layers relational layers (HF:513, 524-529) on the main stream; the last layer leaves
+        the visual rows of the first cross layer's input in the visual rows of X[0]."""
+        cfg, st, ops, d, MV = self.cfg, self.store, self.ops, self.d, self.MV
         self._pr("visn")
         if self.use_codebook:
             ops.codebook_gather(self.cid, self.vmask if self.has_vmask else None, st.centroids_c, st.view("mask_feat"),
@@ -1656,11 +1719,41 @@ class Engine:
             self.dropout_stream(self.vis0, MV, self.seed(1))
         elif self.res32:
             ops.cast_from_f32(self.vis0.f, self.vis0.h, MV * d)
-        for i, (sa, ffn) in enumerate(self.vis_layers[:n_vis_alone]):
+        for i, (sa, ffn) in enumerate(self.vis_layers[:n_layers]):
             self._pr(("vis", i))
             x, mid, y = self._vis_layer_io(i)
             sa.fwd(x, mid)
             ffn.fwd(mid, y)
+
+    def _encoder_forward(self, want_pooled=True, ffn_rows=None):
+        cfg, st, ops, d = self.cfg, self.store, self.ops, self.d
+        ML, MV = self.ML, self.MV
+        X0 = self.X[0]
+        last = self.x_layers[-1]
+        if ffn_rows is not None and not (self.compact_last_ffn and last["vis_on"] and not (self.pair_blocks and last["lang_on"])):
+            ffn_rows = None
+        self._ffn_rows_run = ffn_rows
+        for blk in self.x_layers:
+            if blk["vis_on"]:
+                blk["ffn_v"].rows = None
+        self.fork()
+        # samplers: the text does not change between refinement steps and, without dropout, neither does the output of the
+        # language stack (embeddings + l_layers self-attention layers: it never sees the visual tokens) -- it still sits in
+        # the language rows of X[0] from the loop's first pass (no later layer writes there), so the later passes skip it.  Exact.
+        skip_lang = getattr(self, "_reuse_lang_stack", False) and self.p_hid == 0 and self.p_attn == 0
+        # caption sampler, the mirror image: the picture does not change between refinement steps and neither does the output of
+        # the feature encoder + r_layers visual stack (they never see the text) -- it still sits in the visual rows of X[0] from
+        # the loop's first pass (no later layer writes there), so the later passes skip them.  Exact under the same condition.
+        skip_vis = getattr(self, "_reuse_vis_stack", False) and self.p_hid == 0 and self.p_attn == 0
+        assert not (skip_lang and skip_vis)
+        pairs = [] if skip_lang or skip_vis else self._stack_pairs()
+        n_lang_alone = cfg.l_layers - len(pairs)
+        n_vis_alone = cfg.r_layers - len(pairs)
+        if not skip_lang:
+            with self.lang_stream():            # ---- language stack (HF:516-521) on the side stream: all of it, or the layers
+                self._language_stack_forward(n_lang_alone)      # that have no visual partner (_stack_pairs)
+        if not skip_vis:
+            self._visual_stack_forward(n_vis_alone)
         self.join()
         for iv, il in pairs:                # ---- a visual and a language layer per step, their contractions two per launch
             self._pr(("vis", iv))
@@ -1699,7 +1792,7 @@ class Engine:
                 self.join()
         Xl = self.X[-1]
         self.lang_final, self.vis_final = _h(self.lr(Xl)), _h(self.vr(Xl))      # (the heads read the bf16 copy of an fp32 stream)
-        if self.packed and self.need_lang:          # language_output in the reference's [B, L, d] layout for whoever reads it
+        if self.packed and self.need_lang and not getattr(self, "_packed_head", False):   # language_output in the reference's [B, L, d] layout
             self.lang_final = self._dense_lang(self.lang_final, self.lang_pad)
         self._pr("heads")                   # pooler and every head on top of the encoder
         if want_pooled and self.need_lang:
@@ -2181,6 +2274,91 @@ class Engine:
                 on_step(i)
         ops.codebook_gather(self.cid, self.vmask, st.centroids_c, st.view("mask_feat"), self.feats, self.MV, self.F)
         return self.cid, self.feats, self.row_maxprob
+
+    # ------------------------------------------------------------ caption sampler (Mask-Predict over the MLM head)
+    CAPTION_MAX_L = 64              # xl_caption_step: one lane per token position
+    reuse_vis_stack = True          # False: every step recomputes the visual stack (A/B of the saving, tools/task_bench.py)
+
+    def sample_words_nar(self, lengths, n_steps=10, prefix_len=0, on_step=None, *, temperature=None, seed=0, top_k=None, top_p=None,
+                         min_p=None, suppress_repeats=False, mask_token_id=103, banned_ids=None):
+        """Mask-Predict caption decoding, the word-side twin of sample_codes_nar (include/xlxmert_hip.h xl_caption_step states the
+        rules; DESIGN.md "N2 notes"), without a host round trip between steps.  set_inputs has staged the visual side (real grid
+        features or un-masked cluster ids) and the token layout: row b = [CLS], prefix_len prefix ids, lengths[b] free positions
+        (whatever they hold: the loop feeds mask_token_id there), [SEP], [PAD]; attention_mask = l < prefix_len + lengths[b] + 2.
+        lengths: an int, or ints [B] (a host sequence / CPU tensor is range-checked here: 1 <= n <= L - 2 - prefix_len; a device
+        tensor cannot be without a round trip and is clamped by the kernel).  banned_ids: token ids that are never predicted
+        (default: every id below 999, the specials of bert-base-uncased).  temperature / seed / top_k / top_p / min_p: as in
+        sample_codes_nar; the noise row of position (b, l) is its row in the head's input matrix, b*L + l dense and loff[b] + l packed,
+        so one seed reproduces a run bit for bit for one batch and packing.  Steps after the first reuse the visual stack.
+        Returns (tokens [B, L] int64, score [B] fp32: mean log-probability of the free tokens under the last forward, conf [B, L] fp32:
+        the last forward's confidences); on_step(i) is called after step i's update."""
+        temperature = self.check_temperature(temperature)
+        trunc = self.check_truncation(top_k, top_p, min_p)
+        ops, B, L = self.ops, self.B, self.L
+        lh = self.lang_heads
+        if lh is None or not lh.has_mlm or not self.need_lang:
+            raise RuntimeError("sample_words_nar needs the MLM head: a store with task 'word_mask' or 'all' (cls.predictions.*) and an "
+                               "engine built with need_lang=True")
+        if getattr(self, "embeds_mode", False):
+            raise ValueError("sample_words_nar feeds token ids: set_inputs(input_ids=...), not inputs_embeds")
+        P, T = int(prefix_len), int(n_steps)
+        if L > self.CAPTION_MAX_L:
+            raise ValueError(f"caption sampler: text length {L} > {self.CAPTION_MAX_L}")
+        if P < 0 or L - 2 - P < 1:
+            raise ValueError(f"prefix_len {prefix_len!r}: need 0 <= prefix_len <= L - 3 = {L - 3}")
+        if T < 1:
+            raise ValueError(f"n_steps {n_steps!r}: at least 1")
+        if not (isinstance(lengths, torch.Tensor) and lengths.device.type != "cpu"):
+            lens = torch.as_tensor(lengths).reshape(-1)
+            if lens.is_floating_point() or lens.dtype == torch.bool:
+                raise ValueError(f"lengths {lengths!r}: an int or ints [B]")
+            lens = lens.to(torch.int64)
+            if lens.numel() == 1:
+                lens = lens.expand(B)
+            if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > L - 2 - P:
+                raise ValueError(f"lengths {lengths!r}: an int or ints [B = {B}] with 1 <= n <= L - 2 - prefix_len = {L - 2 - P}")
+        else:
+            lens = lengths.reshape(-1)
+            if lens.numel() != B:
+                raise ValueError(f"lengths: {lens.numel()} entries for a batch of {B}")
+        if getattr(self, "cap_len", None) is None:
+            self.cap_len = torch.zeros(B, dtype=torch.int32, device=self.dev)
+            self.cap_tokens = torch.zeros(B, L, dtype=torch.int64, device=self.dev)
+            self.word_mask = torch.zeros(B, L, dtype=torch.uint8, device=self.dev)
+            self.cap_conf, self.cap_score = self.f32(B, L), self.f32(B)
+            self._cap_pos = torch.arange(L, dtype=torch.int32, device=self.dev).view(1, L)
+        self.cap_len.copy_(lens, non_blocking=True)
+        if banned_ids is None:
+            banned_ids = torch.arange(min(999, self.cfg.vocab_size - 1))
+        lh._prepare_predict(banned_ids)
+        packed = self.packed
+        # step 0's state, by the host (sample_codes_nar: vmask.fill_(1)): every free position masked, tokens = the layout with [MASK] there
+        free = (self._cap_pos > P) & (self._cap_pos < P + 1 + self.cap_len.view(B, 1))
+        self.word_mask.copy_(free)
+        self.ids.masked_fill_(free, int(mask_token_id))
+        self.cap_tokens.copy_(self.ids)
+        self.cap_conf.zero_()
+        self._packed_head = packed
+        try:
+            fused = trunc is None and lh.fused_predict_available()
+            if fused:
+                lh._prepare_fused_predict()
+                if temperature is not None:
+                    lh._prepare_fused_sample(temperature)
+            for i in range(T):
+                self._reuse_vis_stack = i > 0 and self.reuse_vis_stack          # the picture is the same in every step
+                try:
+                    self.encoder_forward(want_pooled=False)
+                finally:
+                    self._reuse_vis_stack = False
+                lh.predict(self.lang_final, self.ML, fused, temperature, self.sample_launch_seed(seed, i), trunc)
+                ops.caption_step(lh.row_prob, lh.row_id, self.loff if packed else None, self.cap_len, self.cap_tokens, self.ids,
+                                 self.word_mask, self.cap_conf, self.cap_score, B, L, P, i, T, int(mask_token_id), suppress_repeats)
+                if on_step is not None:
+                    on_step(i)
+        finally:
+            self._packed_head = False
+        return self.cap_tokens, self.cap_score, self.cap_conf
 
     # ------------------------------------------------------------ backward
     def zero_accumulated_grads(self):

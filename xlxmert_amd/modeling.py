@@ -428,6 +428,93 @@ class XLxmertForPretraining(nn.Module):
         self.train(was_training)
         return out, cid.clone()
 
+    @torch.no_grad()
+    def sample_caption_ids(self, visual_feats=None, visual_pos=None, *, cluster_ids=None, lengths, prefix_ids=None, n_steps=10,
+                           max_text_length=20, temperature=None, seed=None, top_k=None, top_p=None, min_p=None, suppress_repeats=False,
+                           banned_ids=None, return_intermediate=False, mask_token_id=103, cls_token_id=101, sep_token_id=102,
+                           first_word_id=999):
+        """Caption an image by Mask-Predict decoding over the MLM head (Engine.sample_words_nar; the reference trains the head for
+        it, pretrain/lxmert_data.py --word_mask_predict, and has the loop on the visual side only).  The picture is given as real
+        grid features `visual_feats` [B, V, F] or as `cluster_ids` [B, V] (e.g. what sample_codes just produced), both un-masked;
+        visual_pos [B, V, 4] defaults to the boxes of a square grid.  Row b of the result is [CLS], prefix_ids (the same for every
+        row, e.g. the ids of "a picture of"), lengths[b] predicted tokens, [SEP], [PAD] up to max_text_length (<= 64; [PAD] = id 0).
+        lengths: an int (every row), an int tensor [B] (one per row), or a python list of C CANDIDATE lengths: every image is then
+        decoded once per candidate (a batch of B*C rows) and the candidate with the highest score is returned -- Mask-Predict's
+        length-candidate rule.  Each must satisfy 1 <= n <= max_text_length - 2 - len(prefix_ids).
+        banned_ids (default: every id below first_word_id, the specials of bert-base-uncased) are never predicted.
+        temperature / seed / top_k / top_p / min_p: as in sample_codes.  suppress_repeats: re-mask a token equal to its left neighbour
+        first.  Tokenising a prefix and decoding ids to text stay with the caller.
+        Returns (token_ids [B, L] int64, score [B] fp32 = mean log-probability of the predicted tokens under the last forward); with
+        candidate lengths also the chosen length per image [B]; with return_intermediate also the list of token matrices after
+        every step (all candidates: [B*C, L], image-major)."""
+        temperature = Engine.check_temperature(temperature)
+        trunc = _truncation_kw(top_k, top_p, min_p)
+        if not self.task_mask_lm:
+            raise RuntimeError("sample_caption_ids on a model built without task_mask_lm (no `cls` MLM head)")
+        if (visual_feats is None) == (cluster_ids is None):
+            raise ValueError("give the picture either as visual_feats or as cluster_ids")
+        if cluster_ids is not None and self.vis_emb is None:
+            raise RuntimeError("cluster_ids given but the model has no codebook: call set_visual_embedding(centroids) first")
+        vis = visual_feats if cluster_ids is None else cluster_ids
+        B, V = vis.shape[0], vis.shape[1]
+        dev = vis.device
+        L = int(max_text_length)
+        prefix = [int(t) for t in (prefix_ids.tolist() if isinstance(prefix_ids, torch.Tensor) else (prefix_ids or ()))]
+        P = len(prefix)
+        cand = isinstance(lengths, (list, tuple))
+        C = len(lengths) if cand else 1
+        if cand:
+            lens = torch.as_tensor(lengths, dtype=torch.int64).reshape(1, C).expand(B, C).reshape(-1)
+        else:
+            lens = torch.as_tensor(lengths, dtype=torch.int64).cpu().reshape(-1)
+            lens = lens.expand(B) if lens.numel() == 1 else lens
+        if L > Engine.CAPTION_MAX_L or L - 2 - P < 1:
+            raise ValueError(f"max_text_length {max_text_length}: at most {Engine.CAPTION_MAX_L} and at least len(prefix_ids) + 3")
+        if lens.numel() != B * C or int(lens.min()) < 1 or int(lens.max()) > L - 2 - P:
+            raise ValueError(f"lengths {lengths!r}: ints with 1 <= n <= max_text_length - 2 - len(prefix_ids) = {L - 2 - P} "
+                             "(an int, a tensor [B], or a list of candidate lengths)")
+        if visual_pos is None:
+            g = int(round(V ** 0.5))
+            if g * g != V:
+                raise ValueError(f"visual_pos is needed for {V} visual tokens (not a square grid)")
+            idx = torch.arange(V)
+            i, j = (idx // g).float(), (idx % g).float()                   # ref utils.box_position
+            visual_pos = torch.stack([j / g, i / g, (j + 1) / g, (i + 1) / g], 1).unsqueeze(0).expand(B, -1, -1)
+        if C > 1:
+            vis = vis.repeat_interleave(C, 0)
+            visual_pos = visual_pos.repeat_interleave(C, 0)
+        # the token layout, on the host: [CLS] prefix [MASK] x n [SEP] [PAD] ...; packed-row list and offsets next to it (no round trip)
+        pos = torch.arange(L).view(1, L)
+        n = lens.view(-1, 1)
+        ids = torch.zeros(B * C, L, dtype=torch.int64)
+        ids[:, 0] = cls_token_id
+        if P:
+            ids[:, 1:P + 1] = torch.tensor(prefix, dtype=torch.int64)
+        ids[(pos > P) & (pos < P + 1 + n)] = mask_token_id
+        ids[pos.expand(B * C, L) == P + 1 + n] = sep_token_id
+        att = pos < P + n + 2
+        was_training = self.training
+        self.eval()
+        eng = self._step_engine(B * C, L, V)
+        rows = att.reshape(-1).nonzero().reshape(-1)
+        off = torch.cat([lens.new_zeros(1), (lens + P + 2).cumsum(0)])
+        eng.set_inputs(ids.to(dev), att.to(dev), None, visual_pos.to(dev), cluster_ids=vis if cluster_ids is not None else None,
+                       visual_feats=vis if cluster_ids is None else None, lang_rows=rows.to(dev), lang_off=off.to(dev))
+        if banned_ids is None:
+            banned_ids = torch.arange(min(int(first_word_id), self.config.vocab_size))
+        steps = []
+        kw = {} if temperature is None and not trunc else {"temperature": temperature, "seed": _sample_seed(seed), **trunc}
+        tok, score, _ = eng.sample_words_nar(lens, n_steps, P, (lambda i: steps.append(eng.cap_tokens.clone())) if return_intermediate else None,
+                                             suppress_repeats=suppress_repeats, mask_token_id=mask_token_id, banned_ids=banned_ids, **kw)
+        self.train(was_training)
+        tok, score = tok.clone(), score.clone()
+        out = (tok, score)
+        if cand:                                # the length-candidate rule: per image the candidate with the highest score (host arithmetic)
+            best = score.view(B, C).argmax(1)
+            pick = torch.arange(B, device=score.device) * C + best
+            out = (tok[pick], score[pick], lens.to(score.device).view(B, C)[torch.arange(B, device=score.device), best])
+        return out + (steps,) if return_intermediate else out
+
     def _step_engine(self, B, L, V):
         key = (B, L, V, self.training, "step")
         if self.bert._geom != key:

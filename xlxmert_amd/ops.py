@@ -371,6 +371,14 @@ class HipOps:
         self._call("xl_sampler_ar_update", self._p(prob), self._p(pred_ids), self._p(visited), self._p(vis_mask),
                       self._p(code_ids), B, V, int(fixed_pos), self._stream())
 
+    def caption_step(self, row_prob, row_id, lang_off, lengths, tokens, fed_ids, word_mask, conf, score, B, L, P, step, n_steps,
+                     mask_token_id, suppress_repeats=False):
+        """one Mask-Predict caption step between two forwards (xl_caption_step: commit, confidence, score, repeat rule, re-mask,
+        fed ids); lang_off: int32 [B+1] offsets of packed language rows, None = dense rows b*L+l."""
+        self._call("xl_caption_step", self._p(row_prob), self._p(row_id), self._p(lang_off), self._p(lengths), self._p(tokens),
+                   self._p(fed_ids), self._p(word_mask), self._p(conf), self._p(score), B, L, int(P), int(step), int(n_steps),
+                   int(mask_token_id), int(bool(suppress_repeats)), self._stream())
+
     # -- attention core
     def sdpa_keep_bits_bytes(self, B, H, nq, nk, dh):
         """bytes of the buffer in which sdpa_fwd leaves its dropout decisions for sdpa_bwd (0: this geometry / dtype runs on kernels
