@@ -309,6 +309,38 @@ int xl_sampler_ar_update(const float* prob, const int* pred_ids, void* visited, 
 int xl_caption_step(const float* row_prob, const int* row_id, const int* lang_off, const int* lengths, int64_t* tokens,
                     int64_t* fed_ids, void* word_mask, float* conf, float* score, int B, int L, int P, int step, int n_steps,
                     int mask_token_id, int suppress_repeats, void* stream);
+/* IN-PAINTING grid step: the image loops above with part of the grid GIVEN.  free_mask (uint8 [B, V], constant over a loop) marks the
+ * cells that are sampled (non-zero); a cell with free_mask == 0 holds a caller's code and is never written in code_ids.  The count
+ * n_b of free cells of row b is taken on the device (one ballot, no host round trip); n_b = 0 is legal.  xl_grid_step runs after the
+ * predict of step `step` of `n_steps` (0 <= step < n_steps), one launch, one wave per image (V <= 64), on
+ *   row_prob / row_id   fp32 / int32 [B*V], row b*V + v: probability and id of the predicted (or drawn) code (row_maxprob / row_argmax
+ *                       of the three predict paths; the same row that the samplers' noise function is given)
+ *   order               int32 [B, V] or NULL, read in XL_GRID_AR_ORDER only
+ *   code_ids int64 [B, V];  vis_mask uint8 [B, V] (non-zero: the forward read mask_feat there);  conf fp32 [B, V];  score fp32 [B]
+ * mode XL_GRID_NAR (Mask-Predict: xl_sampler_update + xl_remask_lowest over the free cells), in this order:
+ *   1 commit    code_ids[b,v] = row_id where free && vis_mask.  Nothing else is written to code_ids.
+ *   2 conf      conf[b,v] = row_prob at EVERY free cell, 0 at the given ones.
+ *   3 score     score[b] = (1/n_b) sum over the free cells of log conf[b,v] (logf, added by a fixed-order wave butterfly: the same
+ *               bits on every run); 0 when n_b == 0.
+ *   4 re-mask   step + 1 < n_steps: n_mask = (n_b * (n_steps - step - 1)) / n_steps in INTEGER division, per row (for n_b = 64 it
+ *               equals the image loop's float int(ratio * V) at every n_steps <= 64); vis_mask = 1 at the first n_mask free cells
+ *               ranked by (conf ascending, v ascending), 0 at every other cell of the row, given cells included.  n_mask = 0 is legal.
+ *               step + 1 == n_steps: vis_mask is left as the last forward read it.
+ * modes XL_GRID_AR_CONF / XL_GRID_AR_ORDER (xl_sampler_ar_update over the free cells: one cell per image per step):
+ *   candidates  the cells with free && vis_mask.  A row WITHOUT a candidate writes nothing to code_ids, vis_mask or conf.
+ *   choice      XL_GRID_AR_CONF: the candidate with the highest row_prob, ties to the lower v.  XL_GRID_AR_ORDER: the candidate with
+ *               the lowest (order[b,v], v); order == NULL: raster order (v itself).  Duplicate order values are legal.
+ *   fill        at the chosen cell: code_ids = row_id, vis_mask = 0, conf = row_prob.
+ *   score       score[b] = (1/n_b) sum over free && !vis_mask (after the fill) of log conf[b,v]: each filled cell under the forward that
+ *               filled it -- after the last cell the image's mean log-probability under the fill order; 0 when n_b == 0.  It is
+ *               refreshed in every row, with or without a candidate.
+ * XL_ERR_BAD_ARG without a launch: a NULL buffer other than order, V < 1 or V > 64, B < 1, mode outside 0..2, step outside
+ * [0, n_steps). */
+#define XL_GRID_NAR 0
+#define XL_GRID_AR_CONF 1
+#define XL_GRID_AR_ORDER 2
+int xl_grid_step(const float* row_prob, const int* row_id, const void* free_mask, const int* order, int64_t* code_ids, void* vis_mask,
+                 float* conf, float* score, int B, int V, int mode, int step, int n_steps, void* stream);
 
 /* ---------------------------------------------------------------- attention core (HF:247-263)
  * per (b,h): O = softmax(Q K^T * scale, keys with key_mask==0 excluded) V ; nq, nk <= 64 on the on-chip kernels (the path's

@@ -1,8 +1,10 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py [--rows all|sampler|caption] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
 --rows caption: the Mask-Predict caption sampler alone (bs 256, L = 20, T = 10, ragged lengths): ms per batch and captions/s, greedy on
 the fused and on the logits predict path and with the visual stack recomputed every step, in one alternation with the arms below.
+--rows inpaint: Engine.inpaint_codes alone (bs 256, Mask-Predict T = 4, half of every grid free): ms per batch, greedy (and drawn, with
+--temperature), alternating in this process with the `sampler` row's loop (sample_codes_nar(4) on the same engine), its yardstick.
 --temperature: the sampler rows are timed greedy AND with temperature sampling, alternating in this process (rounds of 8 loops
 each; the line gives the median and the min..max spread of both).
 --top-k / --top-p / --min-p (any of them): a third arm in the same alternation, the truncated sampler at that temperature (1 if
@@ -16,7 +18,7 @@ from xlxmert_amd.config import XLxmertConfig
 from xlxmert_amd.trainer import PretrainStep, word_rows_of
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--rows", choices=("all", "sampler", "caption"), default="all")
+ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint"), default="all")
 ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
 ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
 ap.add_argument("--top-k", type=int, default=None, help="truncated arm: at most K candidates (1..256)")
@@ -70,7 +72,7 @@ from xlxmert_amd.engine import Engine
 from xlxmert_amd.ops import HipOps
 from xlxmert_amd.params import ParamStore
 from xlxmert_amd.trainer import init_reference_weights
-for B in (64, 256) if args.rows != "caption" else ():
+for B in (64, 256) if args.rows in ("all", "sampler") else ():
     store = ParamStore(cfg, dev, torch.bfloat16, task="vis_mask")
     init_reference_weights(store, 1)
     g = torch.Generator().manual_seed(0)
@@ -142,5 +144,38 @@ def caption_row(B=256, L=20, T=10):
         print(f"  {k:20s}: median {med * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}  {B / med:9.0f} captions/s")
 
 
+def inpaint_row(B=256, T=4):
+    store = ParamStore(cfg, dev, torch.bfloat16, task="vis_mask")
+    init_reference_weights(store, 1)
+    g = torch.Generator().manual_seed(0)
+    store.set_centroids(torch.randn(cfg.num_clusters, cfg.visual_feat_dim, generator=g).relu())
+    eng = Engine(cfg, store, HipOps(torch.bfloat16), B, 20, 64, need_lang=False)
+    eng.sync_compute_weights()
+    inp = O.make_inputs(oc, 4, B, 20, 8)
+    eng.set_inputs(inp["input_ids"].cuda(), inp["attention_mask"].cuda(), None, inp["visual_pos"].cuda(),
+                   cluster_ids=torch.zeros(B, 64, dtype=torch.long, device=dev), vis_mask=torch.ones(B, 64, dtype=torch.bool, device=dev))
+    init = torch.randint(0, cfg.num_clusters, (B, 64), generator=g).cuda()
+    free = torch.zeros(B, 64, dtype=torch.uint8)
+    for b in range(B):                                                   # half of every grid, other cells per image
+        free[b, torch.randperm(64, generator=g)[:32]] = 1
+    free = free.cuda()
+    arms = {"sampler greedy": lambda: eng.sample_codes_nar(T), "inpaint greedy": lambda: eng.inpaint_codes(init, free, T)}
+    if args.temperature is not None:
+        kw = dict(temperature=args.temperature, seed=args.seed)
+        arms["sampler sampled"] = lambda: eng.sample_codes_nar(T, **kw)
+        arms["inpaint sampled"] = lambda: eng.inpaint_codes(init, free, T, **kw)
+    runs = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for k, fn in arms.items():
+            runs[k].append(timed(fn, warm=1))
+    print(f"inpaint T={T}    bs {B:4d}, 32 of 64 cells free, fused predict {'available' if eng.fused_predict_available() else 'not available'}")
+    for k, v in runs.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        print(f"  {k:16s}: median {med * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}  {B / med:9.0f} images/s")
+
+
 if args.rows in ("all", "caption"):
     caption_row()
+if args.rows == "inpaint":
+    inpaint_row()

@@ -1719,6 +1719,76 @@ __global__ __launch_bounds__(256) void caption_step_kernel(const float* __restri
     if (in_row) fed_ids[i] = lane < P + n + 2 ? (m ? (int64_t)mask_token_id : tok) : 0;
 }
 
+// In-painting grid step (include/xlxmert_hip.h xl_grid_step states the rules): remask_lowest + sampler_update (mode 0) or
+// sampler_ar_update (modes 1, 2) restricted to the cells that free_mask marks, one wave per image, lane v = grid position
+// (V <= 64).  The free count n_b is a ballot; as in caption_step_kernel every decision comes from shuffled values: no LDS, no
+// atomics, the score a fixed-order butterfly sum.  A given cell (free_mask == 0) is never written in code_ids.
+__global__ __launch_bounds__(256) void grid_step_kernel(const float* __restrict__ row_prob, const int* __restrict__ row_id,
+                                                        const uint8_t* __restrict__ free_mask, const int* __restrict__ order,
+                                                        int64_t* __restrict__ code_ids, uint8_t* __restrict__ vis_mask,
+                                                        float* __restrict__ conf, float* __restrict__ score, int B, int V,
+                                                        int mode, int step, int n_steps) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const bool in_row = lane < V;
+    const size_t i = (size_t)b * V + (in_row ? lane : 0);
+    const bool is_free = in_row && free_mask[i] != 0;
+    const unsigned long long free_bits = __ballot(is_free);
+    const int n = __popcll(free_bits);                               // free cells of this image
+    const bool masked = in_row && vis_mask[i] != 0;
+    const float p = is_free ? row_prob[i] : 0.f;
+    if (mode == XL_GRID_NAR) {
+        // 1. commit the prediction where the cell was masked in this forward
+        if (is_free && masked) code_ids[i] = row_id[i];
+        // 2. confidence of the latest forward at every free cell, 0 at the given ones
+        if (in_row) conf[i] = p;
+        // 3. mean log-probability over the free cells
+        float s = is_free ? logf(p) : 0.f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) score[b] = n > 0 ? s / (float)n : 0.f;
+        // 4. the mask of the next forward: the n_mask lowest (confidence, cell) among the free cells
+        if (step + 1 < n_steps) {
+            const int n_mask = (int)(((long long)n * (n_steps - step - 1)) / n_steps);
+            int rank = 0;
+            for (int j = 0; j < V; ++j) {
+                const float other = __shfl(p, j, 64);
+                rank += (((free_bits >> j) & 1ull) && (other < p || (other == p && j < lane))) ? 1 : 0;
+            }
+            if (in_row) vis_mask[i] = (is_free && rank < n_mask) ? 1 : 0;
+        }
+        return;
+    }
+    // modes 1, 2: one candidate (free and still masked) per image is filled -- the most confident one, or the first in `order`
+    const bool cand = is_free && masked;
+    const bool any = __ballot(cand) != 0ull;
+    float best = cand ? p : -1.0f;                                   // XL_GRID_AR_CONF key (a probability: never below 0)
+    int key = cand ? (mode == XL_GRID_AR_ORDER && order != nullptr ? order[i] : 0) : 0;
+    int arg = cand ? lane : 64;                                      // 64: no candidate, loses every comparison
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int ok = __shfl_xor(key, o, 64), oa = __shfl_xor(arg, o, 64);
+        bool take;
+        if (oa == 64 || arg == 64) take = arg == 64 && oa != 64;
+        else if (mode == XL_GRID_AR_CONF) take = ob > best || (ob == best && oa < arg);
+        else take = ok < key || (ok == key && oa < arg);
+        if (take) { best = ob; key = ok; arg = oa; }
+    }
+    const bool chosen = any && lane == arg;
+    if (chosen) {
+        code_ids[i] = row_id[i];
+        vis_mask[i] = 0;
+        conf[i] = p;
+    }
+    // mean log-probability of the cells filled so far, each under the forward that filled it
+    const bool filled = is_free && (!masked || chosen);
+    float s = filled ? logf(chosen ? p : conf[i]) : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) score[b] = n > 0 ? s / (float)n : 0.f;
+}
+
 }  // namespace xl
 
 using namespace xl;
@@ -2654,6 +2724,18 @@ extern "C" int xl_caption_step(const float* row_prob, const int* row_id, const i
     hipLaunchKernelGGL(caption_step_kernel, dim3((B + WPB - 1) / WPB), dim3(256), 0, (hipStream_t)stream, row_prob, row_id, lang_off,
                        lengths, tokens, fed_ids, (uint8_t*)word_mask, conf, score, B, L, P, step, n_steps, mask_token_id,
                        suppress_repeats);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
+extern "C" int xl_grid_step(const float* row_prob, const int* row_id, const void* free_mask, const int* order, int64_t* code_ids,
+                            void* vis_mask, float* conf, float* score, int B, int V, int mode, int step, int n_steps, void* stream) {
+    XL_CHECK_ARG(row_prob && row_id && free_mask && code_ids && vis_mask && conf && score, XL_ERR_BAD_ARG,
+                 "xl_grid_step: null argument (only order may be NULL) B=%d V=%d", B, V);
+    XL_CHECK_ARG(B > 0 && V > 0 && V <= 64 && mode >= XL_GRID_NAR && mode <= XL_GRID_AR_ORDER && n_steps >= 1 && step >= 0 && step < n_steps,
+                 XL_ERR_BAD_ARG, "xl_grid_step: B=%d V=%d (1..64) mode=%d (0..2) step=%d n_steps=%d", B, V, mode, step, n_steps);
+    hipLaunchKernelGGL(grid_step_kernel, dim3((B + WPB - 1) / WPB), dim3(256), 0, (hipStream_t)stream, row_prob, row_id,
+                       (const uint8_t*)free_mask, order, code_ids, (uint8_t*)vis_mask, conf, score, B, V, mode, step, n_steps);
     XL_CHECK_LAUNCH();
     return XL_OK;
 }

@@ -2275,6 +2275,86 @@ class Engine:
         ops.codebook_gather(self.cid, self.vmask, st.centroids_c, st.view("mask_feat"), self.feats, self.MV, self.F)
         return self.cid, self.feats, self.row_maxprob
 
+    # ------------------------------------------------------------ in-painting (the image loops with part of the grid given)
+    GRID_MODES = {"nar": 0, "confidence": 1, "tlbr": 2, "order": 2}     # XL_GRID_NAR / XL_GRID_AR_CONF / XL_GRID_AR_ORDER
+
+    def inpaint_codes(self, init_codes, free_mask, n_steps=4, mode="nar", order=None, on_step=None, *, temperature=None, seed=0,
+                      top_k=None, top_p=None, min_p=None):
+        """Sample the FREE cells of the grid around given codes (include/xlxmert_hip.h xl_grid_step states the rules; DESIGN.md "N2
+        notes"), without a host round trip between steps.  set_inputs has staged the text as for sample_codes_nar.
+        init_codes [B, V] int: the codes of the given cells (whatever the free cells hold is ignored); a host tensor / sequence is
+        range-checked against [0, K) at the given cells, a device tensor is clamped into it.  free_mask [B, V]: non-zero = sampled;
+        rows may have any number of free cells, none included (such a row comes back untouched, score 0).
+        mode "nar": Mask-Predict over the free cells, n_steps refinement steps with the per-row integer schedule.  "confidence" /
+        "tlbr" / "order": one free cell per image per step -- the most confident one, raster order, or ascending `order` [B, V] (int,
+        e.g. a permutation per image); n_steps=None = the largest free count of the batch (one host read before the loop), fewer
+        leave cells masked (mask_feat in the returned features, as in sample_codes_ar).
+        temperature / seed / top_k / top_p / min_p: as in sample_codes_nar -- the same predict paths, launch seeds and noise rows
+        b*V + v, so with every cell free the loop reproduces sample_codes_nar / sample_codes_ar bit for bit.
+        Returns (code_ids [B, V] int64, code features [B*V, F], score [B] fp32: mean log-probability of the sampled cells, conf [B, V]
+        fp32: the probability each sampled cell was last predicted / filled with); on_step(i) is called after step i's update."""
+        temperature = self.check_temperature(temperature)
+        trunc = self.check_truncation(top_k, top_p, min_p)
+        ops, B, V = self.ops, self.B, self.V
+        st = self.store
+        if mode not in self.GRID_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(self.GRID_MODES)}")
+        gmode = self.GRID_MODES[mode]
+        if V > 64:
+            raise ValueError(f"inpaint_codes: {V} grid cells > 64 (xl_grid_step: one lane per cell)")
+        host_codes = not (isinstance(init_codes, torch.Tensor) and init_codes.device.type != "cpu")
+        init_codes, free_mask = torch.as_tensor(init_codes), torch.as_tensor(free_mask)
+        if tuple(init_codes.shape) != (B, V) or init_codes.is_floating_point() or init_codes.dtype == torch.bool:
+            raise ValueError(f"init_codes: int codes of shape [B = {B}, V = {V}] (got {init_codes.dtype} {tuple(init_codes.shape)})")
+        if tuple(free_mask.shape) != (B, V):
+            raise ValueError(f"free_mask: shape [B = {B}, V = {V}] (got {tuple(free_mask.shape)})")
+        if (order is not None) != (mode == "order"):
+            raise ValueError(f"order: needed by mode 'order' and by no other (mode {mode!r})")
+        if order is not None:
+            order = torch.as_tensor(order)
+            if tuple(order.shape) != (B, V) or order.is_floating_point() or order.dtype == torch.bool:
+                raise ValueError(f"order: ints of shape [B = {B}, V = {V}] (got {order.dtype} {tuple(order.shape)})")
+        free = free_mask != 0
+        if host_codes and bool((~free.cpu() & ((init_codes < 0) | (init_codes >= self.K))).any()):
+            raise ValueError(f"init_codes: a given cell holds a code outside [0, {self.K})")
+        if n_steps is None:
+            n_steps = int(free.sum(1).max())                               # the one host read, before the loop
+        T = int(n_steps)
+        if T < (1 if gmode == 0 else 0):
+            raise ValueError(f"n_steps {n_steps!r}: at least 1")
+        if getattr(self, "grid_free", None) is None:
+            self.grid_free = torch.zeros(B, V, dtype=torch.uint8, device=self.dev)
+            self.grid_conf, self.grid_score = self.f32(B, V), self.f32(B)
+            self.grid_order = torch.zeros(B, V, dtype=torch.int32, device=self.dev)
+        self.use_codebook, self.has_vmask = True, True
+        self.grid_free.copy_(free)
+        self.cid.copy_(init_codes)
+        self.cid.clamp_(0, self.K - 1).masked_fill_(self.grid_free != 0, 0)   # free cells start from code 0, as sample_codes_nar's do
+        self.vmask.copy_(self.grid_free)                                    # step 0: every free cell masked
+        self.grid_conf.zero_()
+        self.grid_score.zero_()
+        if order is not None:
+            self.grid_order.copy_(order)
+        fused = trunc is None and self.fused_predict_available()
+        if fused:
+            self._prepare_fused_predict()
+            if temperature is not None:
+                self._prepare_fused_sample(temperature)
+        for i in range(T):
+            self._reuse_lang_stack = i > 0                                 # the text is the same in every step
+            try:
+                self.encoder_forward(want_pooled=False)
+            finally:
+                self._reuse_lang_stack = False
+            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i), trunc)
+            ops.grid_step(self.row_maxprob, self.row_argmax, self.grid_free, self.grid_order if order is not None else None, self.cid,
+                          self.vmask, self.grid_conf, self.grid_score, B, V, gmode, i, T)
+            if on_step is not None:
+                on_step(i)
+        ops.codebook_gather(self.cid, None if gmode == 0 else self.vmask, st.centroids_c, st.view("mask_feat"), self.feats, self.MV,
+                            self.F)
+        return self.cid, self.feats, self.grid_score, self.grid_conf
+
     # ------------------------------------------------------------ caption sampler (Mask-Predict over the MLM head)
     CAPTION_MAX_L = 64              # xl_caption_step: one lane per token position
     reuse_vis_stack = True          # False: every step recomputes the visual stack (A/B of the saving, tools/task_bench.py)

@@ -515,6 +515,69 @@ class XLxmertForPretraining(nn.Module):
             out = (tok[pick], score[pick], lens.to(score.device).view(B, C)[torch.arange(B, device=score.device), best])
         return out + (steps,) if return_intermediate else out
 
+    @staticmethod
+    def _grid_pos(grid_size, B, dev):
+        """ref utils.box_position as [B, V, 4] on `dev`"""
+        idx = torch.arange(grid_size * grid_size)
+        i, j, g = (idx // grid_size).float(), (idx % grid_size).float(), float(grid_size)
+        return torch.stack([j / g, i / g, (j + 1) / g, (i + 1) / g], 1).to(dev).unsqueeze(0).expand(B, -1, -1)
+
+    def _inpaint(self, input_ids, init_codes, free_mask, n_steps, grid_size, mode, order, temperature, seed, top_k, top_p, min_p,
+                 n_candidates, on_step=None):
+        """the loop behind inpaint_codes / ImggenModel.inpaint_image: (code ids [B, V], code features [B, V, F], score [B], conf [B, V])
+        of the best replica per image.  on_step(eng, i) sees all B * n_candidates rows (image-major)."""
+        temperature = Engine.check_temperature(temperature)
+        trunc = _truncation_kw(top_k, top_p, min_p)
+        if self.vis_emb is None:
+            raise RuntimeError("call set_visual_embedding(centroids) first")
+        C = int(n_candidates)
+        if C < 1:
+            raise ValueError(f"n_candidates {n_candidates!r}: at least 1")
+        if C > 1 and temperature is None and not trunc:
+            raise ValueError("n_candidates > 1 needs a temperature or a truncation argument: greedy replicas would be identical")
+        B, L = input_ids.shape
+        V = grid_size * grid_size
+        dev = input_ids.device
+        init_codes, free_mask = torch.as_tensor(init_codes), torch.as_tensor(free_mask)
+        for name, t in (("init_codes", init_codes), ("free_mask", free_mask)) + ((("order", torch.as_tensor(order)),) if order is not None else ()):
+            if tuple(t.shape) != (B, V):
+                raise ValueError(f"{name}: shape [B = {B}, V = {V}] (got {tuple(t.shape)})")
+        if order is not None:
+            order = torch.as_tensor(order)
+        if C > 1:                                               # replicas: other rows b*V + v of the noise function, so other draws
+            input_ids = input_ids.repeat_interleave(C, 0)
+            init_codes, free_mask = init_codes.repeat_interleave(C, 0), free_mask.repeat_interleave(C, 0)
+            order = None if order is None else order.repeat_interleave(C, 0)
+        was_training = self.training
+        self.eval()
+        eng = self._step_engine(B * C, L, V)
+        eng.set_inputs(input_ids, input_ids > 0, None, self._grid_pos(grid_size, B * C, dev),
+                       cluster_ids=torch.zeros(B * C, V, dtype=torch.long, device=dev),
+                       vis_mask=torch.ones(B * C, V, dtype=torch.bool, device=dev))
+        kw = {} if temperature is None and not trunc else {"temperature": temperature, "seed": _sample_seed(seed), **trunc}
+        hook = None if on_step is None else (lambda i: on_step(eng, i))
+        cid, code, score, conf = eng.inpaint_codes(init_codes, free_mask, n_steps, mode, order, hook, **kw)
+        self.train(was_training)
+        cid, code, score, conf = cid.clone(), code.view(B * C, V, -1), score.clone(), conf.clone()
+        if C > 1:                                               # per image the replica with the highest score (host arithmetic)
+            pick = torch.arange(B, device=score.device) * C + score.view(B, C).argmax(1)
+            cid, code, score, conf = cid[pick], code[pick], score[pick], conf[pick]
+        return cid, code, score, conf
+
+    @torch.no_grad()
+    def inpaint_codes(self, input_ids, init_codes, free_mask, n_steps=4, grid_size=8, *, mode="nar", order=None, temperature=None,
+                      seed=None, top_k=None, top_p=None, min_p=None, n_candidates=1):
+        """In-painting: sample the grid cells that `free_mask` [B, V] marks (non-zero) around the given codes `init_codes` [B, V] (e.g.
+        the cluster ids of a real image, xlxmert_amd.io) under the caption `input_ids` -- Engine.inpaint_codes.  mode "nar" (Mask-Predict,
+        n_steps refinements), "confidence" / "tlbr" / "order" (one cell per image per step; n_steps=None = as many as the fullest
+        mask needs; `order` [B, V] ints for "order").  temperature / seed / top_k / top_p / min_p: as in sample_codes.
+        n_candidates = C > 1: every image is sampled C times (a batch of B*C rows, each with its own noise) and the replica with the
+        highest score is returned; it needs a temperature or a truncation argument.
+        Returns (code ids [B, V] int64, score [B] fp32: mean log-probability of the sampled cells, conf [B, V] fp32)."""
+        cid, _, score, conf = self._inpaint(input_ids, init_codes, free_mask, n_steps, grid_size, mode, order, temperature, seed, top_k,
+                                            top_p, min_p, n_candidates)
+        return cid, score, conf
+
     def _step_engine(self, B, L, V):
         key = (B, L, V, self.training, "step")
         if self.bert._geom != key:
@@ -759,3 +822,22 @@ class ImggenModel(XLxmertForPretraining):
         _, code, _ = eng.sample_codes_ar(n_steps, mode, positions=positions, on_step=hook, **kw)
         self.code_ids = eng.cid.clone()
         return imgs if return_intermediate else self._image(code, B)
+
+    @torch.no_grad()
+    def inpaint_image(self, sentences, init_codes, free_mask, max_text_length=20, n_steps=None, mode="nar", return_intermediate=False,
+                      *, order=None, temperature=None, sample_seed=None, top_k=None, top_p=None, min_p=None, n_candidates=1):
+        """In-paint an image (beyond the reference): the cells that free_mask [B, V] marks are sampled around the given codes init_codes
+        [B, V] under the caption (XLxmertForPretraining.inpaint_codes; n_steps=None = the largest free count), and the generator set
+        by set_image_generator renders the result.  return_intermediate: the list of image batches after every step (all
+        B * n_candidates rows, image-major; cells still masked hold mask_feat) -- the last entry of the list is NOT reduced to the
+        best replica, the plain return value is.  self.code_ids / inpaint_score / inpaint_conf keep the chosen ids, scores and
+        confidences."""
+        ids = self._input_ids(sentences, max_text_length)
+        if self.G is None:
+            raise RuntimeError("call set_image_generator(G) first (ref tasks/imggen_model.py:41)")
+        imgs = []
+        hook = (lambda eng, i: imgs.append(self._image(eng.materialise_codes(masked=mode != "nar"), eng.B))) if return_intermediate else None
+        cid, code, score, conf = self._inpaint(ids, init_codes, free_mask, n_steps, self.grid_size, mode, order, temperature, sample_seed,
+                                               top_k, top_p, min_p, n_candidates, hook)
+        self.code_ids, self.inpaint_score, self.inpaint_conf = cid, score, conf
+        return imgs if return_intermediate else self._image(code.reshape(-1, code.shape[-1]), cid.shape[0])

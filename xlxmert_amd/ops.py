@@ -379,6 +379,12 @@ class HipOps:
                    self._p(fed_ids), self._p(word_mask), self._p(conf), self._p(score), B, L, int(P), int(step), int(n_steps),
                    int(mask_token_id), int(bool(suppress_repeats)), self._stream())
 
+    def grid_step(self, row_prob, row_id, free_mask, order, code_ids, vis_mask, conf, score, B, V, mode, step, n_steps):
+        """one in-painting step after a predict (xl_grid_step: mode 0 commit, confidence, score, re-mask over the free cells; modes 1 / 2
+        fill one free cell per image by confidence / by `order`, int32 [B, V] or None = raster order)."""
+        self._call("xl_grid_step", self._p(row_prob), self._p(row_id), self._p(free_mask), self._p(order), self._p(code_ids),
+                   self._p(vis_mask), self._p(conf), self._p(score), B, V, int(mode), int(step), int(n_steps), self._stream())
+
     # -- attention core
     def sdpa_keep_bits_bytes(self, B, H, nq, nk, dh):
         """bytes of the buffer in which sdpa_fwd leaves its dropout decisions for sdpa_bwd (0: this geometry / dtype runs on kernels
