@@ -344,7 +344,32 @@ def sumsq_bound(g, ref, threads=512 * 256):
     return U32 * abs(ref) + SLACK * (k_eff + 1) * U32 * float((g.double() ** 2).sum()) + TINY
 
 
-def adamw_bounds(p_ref, m_ref, v_ref, g, m0, v0, step, clip, beta1, beta2, eps, lr, wd):
+def adamw_chunk_step(lr, beta1, beta2, t):
+    """xl_adamw with chunk_steps: the step size of a chunk at its own update count t >= 1,
+        step = lr sqrt(1 - b2^t) / (1 - b1^t),    b^t = exp2f(t log2f(b)) in fp32  (csrc/optim.hip adamw_kernel).
+    Error of b^t, relative: t U32 (b reaches the kernel as fp32: (b (1 + d))^t), ln 2 |t log2 b| 3 U32 (log2f 2 ulp and the
+    multiply by t move the exponent of exp2f absolutely), EXP_ULP U32 (exp2f).  THE CANCELLATION TERM: 1 - b^t divides that absolute
+    error by 1 - b^t -- 1000 x at b2 = 0.999, t = 1 -- and adds its own rounding U32.  step: half of b2's, all of b1's, and 4 U32
+    (sqrt, two multiplies / divides, lr).  Returns (float64 step per element, its relative error per element)."""
+    t = t.double()
+    rel = torch.zeros_like(t)
+    for b, w in ((beta1, 1.0), (beta2, 0.5)):
+        bt = b ** t
+        e_pow = bt * (t * U32 + math.log(2.0) * (t * abs(math.log2(b))) * 3 * U32 + EXP_ULP * U32)
+        rel = rel + w * (e_pow / (1.0 - bt) + U32)
+    step = lr * torch.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    return step, rel + 4 * U32
+
+
+def ln_bwd_bias_bound(t, dx_ref, prev, ref):
+    """dbias_prev += column sums of dx (of the dropped dx with dropout): the kernel adds the fp32 value BEFORE its store, so a
+    summand carries its fp32 term t only (ln_bwd_bounds' t; with dropout keep t + U32 |dx_dropped| for the multiply by the keep
+    scale), no output rounding; M-deep fp32 sum through slabs or atomics (K_eff = M + 1) and the += ."""
+    M = dx_ref.shape[0]
+    return SLACK * t.sum(0) + SLACK * (M + 1) * U32 * (dx_ref.abs().sum(0) + prev.abs()) + U32 * ref.abs() + TINY
+
+
+def adamw_bounds(p_ref, m_ref, v_ref, g, m0, v0, step, clip, beta1, beta2, eps, lr, wd, step_rel=0.0):
     """xl_adamw in fp32 (everything below is relative to the float64 values on the same inputs):
       gg = g clip            clip = min(1, max_norm / (sqrt(sumsq) grad_scale + 1e-6)): 4 U32 (sqrt, add, div, mul)
       m = b1 m0 + (1-b1) gg   U32 (b1 |m0| + (1-b1) |gg| (5 + 1) + b1 |gg|) + U32 |m|
@@ -354,6 +379,7 @@ def adamw_bounds(p_ref, m_ref, v_ref, g, m0, v0, step, clip, beta1, beta2, eps, 
       upd = step m / (sqrt(v) + eps): step (lr sqrt(1 - b2^t) / (1 - b1^t) in fp32: 4 U32), m, sqrt (1/2 of v's + 1 U32), add, div
             (v_rcp + mul: 2 U32) -> |upd| (4 + e_m + e_v / 2 + 5) U32-relative
       p = p0 - upd - lr wd p': |upd| and |lr wd p| errors plus 3 U32 |p|.
+    step may be a tensor (one step size per element: chunk_steps) with the relative error step_rel of adamw_chunk_step.
     Returns bounds of p, m, v."""
     gg = (g * clip).abs()
     em = U32 * (beta1 * m0.abs() + (1 - beta1) * gg * 6 + beta1 * gg) + U32 * m_ref.abs()
@@ -363,7 +389,7 @@ def adamw_bounds(p_ref, m_ref, v_ref, g, m0, v0, step, clip, beta1, beta2, eps, 
     upd = (step * m_ref / den).abs()
     rel_v = ev / v_ref.abs().clamp(min=1e-300)
     rel_den = (0.5 * rel_v * sv + 2 * U32 * sv) / den
-    e_upd = upd * (9 * U32 + rel_den) + (step / den).abs() * em
+    e_upd = upd * (9 * U32 + rel_den + step_rel) + (step / den).abs() * em
     ep = e_upd + 3 * U32 * p_ref.abs() + abs(lr * wd) * 2 * U32 * p_ref.abs()
     return U32 * p_ref.abs() + SLACK * ep + TINY, U32 * m_ref.abs() + SLACK * em + TINY, U32 * v_ref.abs() + SLACK * ev + TINY
 

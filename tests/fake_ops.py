@@ -63,6 +63,15 @@ def keep_scale_torch(seed, row, col, p_drop):
     return (draw >= thr).to(torch.float32) * float(np.float32(1.0 / (1.0 - p_drop)))
 
 
+def ce_in_regs(logits, dlogits, K, ldl, lddl):
+    """xl_ce_fwd_bwd (csrc/rowops.hip): may a row stay in registers (ce_row_kernel)?  Otherwise the scalar ce_kernel.  The register
+    kernels treat the slots K .. K8 (K rounded up to 8) of a row as -inf and WRITE their gradient, zeros."""
+    K8 = (K + 7) // 8 * 8
+    al = lambda t: t.data_ptr() % 16 == 0                 # noqa: E731
+    return bool(K8 <= 32768 and ldl >= K8 and ldl % 4 == 0 and (dlogits is None or (lddl >= K8 and lddl % 8 == 0))
+                and al(logits) and (dlogits is None or al(dlogits)))
+
+
 def _rc(M, N, device):
     return torch.arange(M, device=device)[:, None], torch.arange(N, device=device)[None, :]
 
@@ -435,7 +444,11 @@ class FakeOps:
             row_argmax.copy_(lg.argmax(1).int())
         if row_maxprob is not None:
             row_maxprob.copy_(torch.exp(lg.max(1).values - lse))
+        if dlogits is not None and K % 8 and ce_in_regs(logits, dlogits, K, ldl, lddl):
+            v2(dlogits, M, (K + 7) // 8 * 8, lddl)[:, K:].zero_()          # the register kernels write a row's slots K .. K8
         if labels is None:
+            if dlogits is not None:
+                v2(dlogits, M, K, lddl).zero_()                            # no labels: no valid row, a zero gradient
             return
         lab = labels.view(-1)
         valid = lab != -100
@@ -530,7 +543,7 @@ class FakeOps:
         v[:n].copy_(torch.where(act, v_new, v[:n]))
         p[:n].copy_(torch.where(act, p_new, p[:n]))
         if p_compute is not None and p_compute.data_ptr() != p.data_ptr():
-            p_compute[:n].copy_(p[:n])
+            p_compute[:n].copy_(torch.where(act, p[:n].to(p_compute.dtype), p_compute[:n]))     # (a skipped chunk's copy is not touched)
         if zero_grad:
             # bit 2: "the next backward overwrites this chunk": the kernel leaves such a gradient as it is; the host restatement
             # POISONS it, so that any path that reads or accumulates into a kept chunk without overwriting it first shows up as NaN

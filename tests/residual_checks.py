@@ -13,6 +13,12 @@ from fake_ops import keep_scale
 from fake_ops_res import FakeOpsRes
 
 KB.REDUCE_OUTS.setdefault("layernorm_bwd_res", ("dgamma", "dbeta", "dbias_prev"))
+# the views the two entry points may write (the recorder holds the rest of every output's storage bit-identical: "outside view")
+KB.ROW_OUTS.setdefault("layernorm_fwd_res", lambda a: [KB._t(a["y32"], a["M"], a["N"]), KB._t(a["y16"], a["M"], a["N"]),
+                                                       KB._t(a["mean"], a["M"]), KB._t(a["rstd"], a["M"])])
+KB.ROW_OUTS.setdefault("layernorm_bwd_res", lambda a: [KB._t(a["dx"], a["M"], a["N"]), KB._t(a["dx_dropped"], a["M"], a["N"]),
+                                                       KB._t(a["dgamma"], a["N"]), KB._t(a["dbeta"], a["N"]),
+                                                       KB._t(a["dbias_prev"], a["N"]), KB._whole(a["ws"])])
 _v2 = KB._v2
 
 
@@ -32,7 +38,7 @@ class RecorderRes(KB.Recorder):
         self._ref.layernorm_fwd_res(**s)
         x, y = _v2(s["x"], M, N, N).clone(), _v2(s["y32"], M, N, N)
         by, bm, br = BD.ln_fwd_bounds(x, s["gamma"].double(), y, s["mean"][:M], s["rstd"][:M], torch.float32)
-        kern = "ln_fwd_res_kernel"
+        kern = self._kern
         got32, got16 = _v2(a["y32"], M, N, N), _v2(a["y16"], M, N, N)
         assert a["y32"].dtype == torch.float32 and a["y16"].dtype == torch.bfloat16
         return [("y32", BD.check(got32, y, by, "layernorm_fwd_res y32"), kern),
@@ -54,7 +60,7 @@ class RecorderRes(KB.Recorder):
         self._ref.layernorm_bwd_res(**s)
         dx = _v2(s["dx"], M, N, N)
         bdx, t, bdg, bdb = BD.ln_bwd_bounds(dy, x, s["gamma"].double(), mean, rstd, dx, torch.float32)
-        kern = "ln_bwd_res_kernel"
+        kern = self._kern
         got_dx, got_dd = _v2(a["dx"], M, N, N), _v2(a["dx_dropped"], M, N, N)
         res = [("dx", BD.check(got_dx, dx, bdx, "layernorm_bwd_res dx"), kern)]
         self._sum_out(res, "dgamma", a["dgamma"], s["dgamma"], prev["dgamma"], bdg + BD.U32 * (s["dgamma"].abs() + prev["dgamma"].abs()), kern)
@@ -70,7 +76,7 @@ class RecorderRes(KB.Recorder):
                                                                   "layernorm_bwd_res dx_dropped bits"), kern))
         if a["dbias_prev"] is not None:
             ref = s["dbias_prev"]
-            bb = (BD.U16 * dd.abs() + BD.SLACK * keep * t).sum(0) + BD.SLACK * (M + 1) * BD.U32 * (
-                dd.abs().sum(0) + prev["dbias_prev"].abs()) + BD.U32 * ref.abs() + BD.TINY
+            # (the sum takes the fp32 value before the bf16 store of dx_dropped: bounds.ln_bwd_bias_bound)
+            bb = BD.ln_bwd_bias_bound(keep * t + BD.U32 * dd.abs(), dd, prev["dbias_prev"], ref)
             self._sum_out(res, "dbias_prev", a["dbias_prev"], ref, prev["dbias_prev"], bb, kern)
         return res

@@ -1019,3 +1019,307 @@ def test_gemm_edge_cases_reject_plausible_kernel_faults(fault, family):
     assert len(rec.failures) == ops.applied, (fault, ops.applied, len(rec.failures), rec.failures[:3])
     word = {"store_in_pad_column": "outside", "store_in_row_m": "outside"}.get(fault, "beyond their bound")
     assert all(word in f for f in rec.failures), rec.failures[:3]
+
+
+# ------------------------------------------------------------------------------------------------------------------ row-kernel dispatch edges
+# tests/test_rowop_edges_bounds_gpu.py over the host restatement: the same calls (tests/rowop_edge_cases.py), the same recorder, the
+# same label assertions (the labels depend on the arguments only).
+ROWOP_EDGE_RUNS = {
+    **{f"{fam}-{dt}": (f"run_{fam}", (dt,)) for fam in ("layernorm", "visn_ln", "embeddings", "colsums", "deferred", "cross_entropy",
+                                                         "elementwise", "optimizer") for dt in ("bf16", "fp32")},
+    "layernorm_res": ("run_layernorm_res", ())}
+
+
+class HonestRowOps(FakeOps):
+    """FakeOps as a KERNEL stand-in: the restatement poisons the gradient of an AdamW chunk flagged keep (bit 2) with NaN so that a
+    reader of it shows up in the engine tests; the kernel leaves it as it is, and so does this"""
+
+    def adamw(self, p, g, m, v, p_compute, decay_flags, sumsq, lr_and_steps, n, beta1, beta2, eps, weight_decay, max_norm,
+              grad_scale=1.0, chunk_steps=None, zero_grad=False):
+        g0 = g[:n].clone()
+        super().adamw(p, g, m, v, p_compute, decay_flags, sumsq, lr_and_steps, n, beta1, beta2, eps, weight_decay, max_norm,
+                      grad_scale=grad_scale, chunk_steps=chunk_steps, zero_grad=zero_grad)
+        g[:n].copy_(torch.where(torch.isnan(g[:n]), g0, g[:n]))
+
+
+def _rowop_fake(fn, dt):
+    from fake_ops_res import FakeOpsRes
+    return FakeOpsRes(torch.bfloat16) if fn == "run_layernorm_res" else HonestRowOps({"bf16": torch.bfloat16, "fp32": torch.float32}[dt])
+
+
+@pytest.mark.parametrize("run", list(ROWOP_EDGE_RUNS))
+def test_rowop_edge_cases_pass_over_the_host_restatement(run):
+    """an honest implementation (fp32 arithmetic on bf16 / fp32 storage that reads the logical extents only and stores into the
+    logical views only) is inside every bound at the inputs of the edge cases, guard rows included, and every sweep reaches the
+    kernel labels the GPU tests expect; in the cross-entropy family every row but the planted ties admits ONE argmax column on
+    the float64 logits alone (asserted inside run_cross_entropy)"""
+    import test_rowop_edges_bounds_gpu as R
+    fn, args = ROWOP_EDGE_RUNS[run]
+    dt = args[0] if args else "bf16"
+    getattr(R, fn)(*(R.DTYPES[a] for a in args), ops=_rowop_fake(fn, dt), dev="cpu")
+
+
+class FaultyRowOps(HonestRowOps):
+    """the host restatement with ONE row-kernel / optimizer fault, applied at every call it can apply to (`applied` counts the calls
+    whose result it changed):
+      ln_stats_padded_width           LayerNorm statistics divided by the row length rounded up to whole 64-lane passes
+      ln_last_vector_out_of_variance  the last live vector of a ragged row is left out of the variance
+      second_stage_drops_last_slab    the second stage of a column sum leaves slab G - 1 out
+      second_stage_stores             the second stage stores its sum instead of adding it to the destination
+      ce_pad_slots_in_sum             the slots K .. K8 of a row enter the log-sum-exp of the register kernels
+      ce_tie_highest_index            ties of the row maximum are resolved to the highest index
+      ce_rows_past_cap_stale          the register kernels leave the rows past their grid cap unwritten
+      embed_33rd_dropped              the sorted embedding backward drops the 33rd occurrence of a token (a chunk boundary)
+      embed_9th_type_match_dropped    the token-type kernel drops the 9th match of a 64-row chunk
+      adamw_flags_wrong_chunk         AdamW indexes its flags by chunks of 128 elements
+      adamw_second_pass_missing       AdamW stops after one pass of its grid (256 blocks x 1024 threads x 4 elements)
+      adamw_clip_ignores_grad_scale   the clip compares max_norm with the norm of the UNSCALED gradient
+      sumsq_drops_tail                the n & 3 elements behind the last whole float4 are left out
+      sumsq_overwrites                *out = sum instead of *out += sum
+      schedule_off_by_one             the schedule is evaluated at the 1-based index of the update instead of the completed updates
+      store_in_pad_column             one store lands in the first pad column of dlogits
+      store_in_row_m                  one store lands in row M of y"""
+
+    def __init__(self, fault, dtype=torch.bfloat16):
+        super().__init__(dtype)
+        self.fault, self.applied = fault, 0
+
+    def layernorm_fwd(self, x, gamma, beta, y, mean, rstd, M, N, eps):
+        f = self.fault
+        V = 8 if x.dtype == torch.bfloat16 else 4
+        Np = -(-N // (64 * V)) * 64 * V
+        xx = torch.as_strided(x, (M, N), (N, 1)).float()
+        if f == "ln_stats_padded_width" and Np != N:
+            mu = xx.sum(1, keepdim=True) / Np
+            var = ((xx - mu) ** 2).sum(1, keepdim=True) / Np
+        elif f == "ln_last_vector_out_of_variance" and Np != N and N > V:
+            mu = xx.mean(1, keepdim=True)
+            var = ((xx - mu)[:, :N - V] ** 2).sum(1, keepdim=True) / N
+        else:
+            super().layernorm_fwd(x, gamma, beta, y, mean, rstd, M, N, eps)
+            if f == "store_in_row_m":
+                torch.as_strided(y, (1,), (1,), y.storage_offset() + M * N).zero_()
+                self.applied += 1
+            return
+        r = 1.0 / torch.sqrt(var + eps)
+        torch.as_strided(y, (M, N), (N, 1)).copy_((xx - mu) * r * gamma.float() + beta.float())
+        mean[:M].copy_(mu[:, 0])
+        rstd[:M].copy_(r[:, 0])
+        self.applied += 1
+
+    def _colsum(self, x, mask, out, M, N, ldx, ws):
+        rpb = 128
+        if ws is not None:
+            while -(-M // rpb) > 128:
+                rpb *= 2
+        G = -(-M // rpb)
+        xx = torch.as_strided(x, (M, N), (ldx, 1)).float()
+        if mask is not None:
+            xx = xx * (mask.view(-1, 1) != 0)
+        if self.fault == "second_stage_drops_last_slab" and ws is not None and G > 1 and bool((xx[(G - 1) * rpb:] != 0).any()):
+            xx = xx[:(G - 1) * rpb]
+            self.applied += 1
+        o = torch.as_strided(out, (N,), (1,))
+        if self.fault == "second_stage_stores" and ws is not None:
+            o.copy_(xx.sum(0))
+            self.applied += 1
+        else:
+            o.add_(xx.sum(0))
+
+    def colsum(self, x, out, M, N, ldx, ws=None):
+        self._colsum(x, None, out, M, N, ldx, ws)
+
+    def masked_colsum(self, x, mask, out, M, N, ldx, ws=None):
+        self._colsum(x, mask, out, M, N, ldx, ws)
+
+    def ce_fwd_bwd(self, logits, labels, counts, dlogits, loss_out, row_lse, row_argmax, row_maxprob, M, K, ldl, lddl, grad_scale=1.0):
+        from fake_ops import ce_in_regs
+        f = self.fault
+        K8 = (K + 7) // 8 * 8
+        regs = ce_in_regs(logits, dlogits, K, ldl, lddl)
+        cap = None if not regs else 1024 if K8 > 10240 else 2048
+        vecs = [t for t in (row_lse, row_argmax, row_maxprob) if t is not None]
+        stale = f == "ce_rows_past_cap_stale" and cap is not None and M > cap and (dlogits is not None or vecs)
+        if stale:
+            old = [t[cap:M].clone() for t in vecs]
+            old_dl = torch.as_strided(dlogits, (M, K8), (lddl, 1))[cap:].clone() if dlogits is not None else None
+        if f == "ce_pad_slots_in_sum" and regs and K % 8 and bool((torch.as_strided(logits, (M, K8), (ldl, 1))[:, K:] > 0).any()):
+            super().ce_fwd_bwd(logits, labels, counts, dlogits, loss_out, row_lse, row_argmax, row_maxprob, M, K8, ldl, lddl, grad_scale)
+            if dlogits is not None:
+                torch.as_strided(dlogits, (M, K8), (lddl, 1))[:, K:].zero_()
+            self.applied += 1
+            return
+        super().ce_fwd_bwd(logits, labels, counts, dlogits, loss_out, row_lse, row_argmax, row_maxprob, M, K, ldl, lddl, grad_scale)
+        if f == "ce_tie_highest_index" and row_argmax is not None:
+            lg = torch.as_strided(logits, (M, K), (ldl, 1))
+            last = (K - 1 - (lg == lg.amax(1, keepdim=True)).flip(1).float().argmax(1)).int()
+            if bool((last != row_argmax).any()):
+                row_argmax.copy_(last)
+                self.applied += 1
+        if stale:
+            for t, o in zip(vecs, old):
+                t[cap:M].copy_(o)
+            if dlogits is not None:
+                torch.as_strided(dlogits, (M, K8), (lddl, 1))[cap:].copy_(old_dl)
+            self.applied += 1
+        if f == "store_in_pad_column" and dlogits is not None and lddl > (K8 if regs else K):
+            dlogits.view(-1)[K8 if regs else K] = 0
+            self.applied += 1
+
+    def embed_bwd(self, dpre, ids, tt, dword, dpos, dtype_tab, B, L, N, order=None, n_types=2):
+        super().embed_bwd(dpre, ids, tt, dword, dpos, dtype_tab, B, L, N, order=order, n_types=n_types)
+        M = B * L
+        d, idf = torch.as_strided(dpre, (M, N), (N, 1)).float(), ids.view(-1)
+        hit = False
+        if self.fault == "embed_33rd_dropped" and order is not None:
+            for tok in idf.unique().tolist():
+                rows = (idf == tok).nonzero()[:, 0]              # ascending rows: the order inside the token's run
+                if tok != 0 and len(rows) >= 33:
+                    dword[tok] -= d[rows[32]]
+                    hit = True
+        if self.fault == "embed_9th_type_match_dropped" and tt is not None and n_types > 1:
+            per = ((M + 3) // 4 + 63) // 64 * 64                 # a wave's quarter of the rows, in 64-row chunks
+            ttf = tt.view(-1)
+            for t in range(1, n_types):
+                for w in range(4):
+                    for c0 in range(w * per, min(M, (w + 1) * per), 64):
+                        rows = c0 + (ttf[c0:min(c0 + 64, M, (w + 1) * per)] == t).nonzero()[:, 0]
+                        if len(rows) >= 9:
+                            dtype_tab[t] -= d[rows[8]]
+                            hit = True
+        self.applied += int(hit)
+
+    def adamw(self, p, g, m, v, p_compute, decay_flags, sumsq, lr_and_steps, n, beta1, beta2, eps, weight_decay, max_norm,
+              grad_scale=1.0, chunk_steps=None, zero_grad=False):
+        f = self.fault
+        kw = dict(grad_scale=grad_scale, chunk_steps=chunk_steps, zero_grad=zero_grad)
+        rest = (lr_and_steps, n, beta1, beta2, eps, weight_decay, max_norm)
+        state = [t for t in (p, g, m, v, p_compute) if t is not None]
+        chunks = n // 256
+        if f == "adamw_flags_wrong_chunk" and decay_flags is not None and chunks > 1:
+            halves = []
+            for h in (0, 1):                  # the flags the first / second 128 elements of every chunk would read
+                fl = decay_flags[(2 * torch.arange(chunks) + h) % chunks]
+                c = [t.clone() for t in state]
+                super().adamw(c[0], c[1], c[2], c[3], c[4] if p_compute is not None else None, fl, sumsq, *rest, **kw)
+                halves.append(c)
+            first = (torch.arange(n) % 256) < 128
+            for i, t in enumerate(state):
+                t[:n].copy_(torch.where(first, halves[0][i][:n], halves[1][i][:n]))
+            self.applied += 1
+            return
+        one_pass = 256 * 1024 * 4
+        before = [t[one_pass:n].clone() for t in state] if (f == "adamw_second_pass_missing" and n > one_pass) else None
+        if f == "adamw_clip_ignores_grad_scale" and max_norm > 0 and sumsq is not None and grad_scale != 1.0:
+            honest = min(1.0, max_norm / (math.sqrt(float(sumsq[0])) * grad_scale + 1e-6))
+            sumsq = sumsq / grad_scale ** 2
+            self.applied += int(min(1.0, max_norm / (math.sqrt(float(sumsq[0])) * grad_scale + 1e-6)) != honest)
+        super().adamw(p, g, m, v, p_compute, decay_flags, sumsq, *rest, **kw)
+        if before is not None:
+            changed = any(not torch.equal(t[one_pass:n], b) for t, b in zip(state, before))
+            for t, b in zip(state, before):
+                t[one_pass:n].copy_(b)
+            self.applied += int(changed)
+
+    def sumsq(self, g, out, n, scratch=None):
+        if self.fault == "sumsq_drops_tail" and n & 3:
+            n -= n & 3
+            self.applied += 1
+        prev = out[0].clone()
+        super().sumsq(g, out, n, scratch)
+        if self.fault == "sumsq_overwrites":
+            out[0] -= prev
+            self.applied += 1
+
+    def schedule_step(self, step, base_lr, warmup_steps, total_steps, beta1, beta2, lr_and_steps):
+        super().schedule_step(step, base_lr, warmup_steps, total_steps, beta1, beta2, lr_and_steps)
+        if self.fault == "schedule_off_by_one":
+            t = int(step[0])
+            f = t / max(1, warmup_steps) if t < warmup_steps else max(0.0, (total_steps - t) / max(1, total_steps - warmup_steps))
+            if torch.tensor(base_lr * f, dtype=lr_and_steps.dtype) != lr_and_steps[0]:
+                lr_and_steps[0] = base_lr * f
+                self.applied += 1
+
+
+ROW_FAULTS = {
+    "ln_stats_padded_width": "layernorm", "ln_last_vector_out_of_variance": "layernorm", "store_in_row_m": "layernorm",
+    "second_stage_drops_last_slab": "colsums", "second_stage_stores": "colsums",
+    "ce_pad_slots_in_sum": "cross_entropy", "ce_tie_highest_index": "cross_entropy", "ce_rows_past_cap_stale": "cross_entropy",
+    "store_in_pad_column": "cross_entropy",
+    "embed_33rd_dropped": "embeddings", "embed_9th_type_match_dropped": "embeddings",
+    "adamw_flags_wrong_chunk": "optimizer", "adamw_second_pass_missing": "optimizer", "adamw_clip_ignores_grad_scale": "optimizer",
+    "sumsq_drops_tail": "optimizer", "sumsq_overwrites": "optimizer", "schedule_off_by_one": "optimizer"}
+# reduced sweeps (the faults do not depend on the large shapes, except where a family says so)
+ROW_FAULT_SWEEPS = {"layernorm": dict(Ns=(8, 504, 512, 520, 2056), bwd_M=(7,), cap_N=(), dma=()),
+                    "colsums": dict(Ms=(1, 127, 129, 16385)),
+                    "cross_entropy": dict(Ks=(50, 1003, 4096), big=((2049, 50),)),
+                    "embeddings": dict(Ns=(8, 520)),
+                    "optimizer": dict(sumsq_n=(1, 3, 4, 1027, 524291))}
+
+
+@pytest.mark.parametrize("fault", list(ROW_FAULTS))
+def test_rowop_edge_cases_reject_plausible_kernel_faults(fault):
+    """the same recorder run as the honest pass, over an implementation with one fault: it must fail at EVERY call the fault
+    changed (each such call shows the fault on its own), and only there"""
+    import test_rowop_edges_bounds_gpu as R
+    family = ROW_FAULTS[fault]
+    ops = FaultyRowOps(fault)
+    rec, n = getattr(R, "run_" + family)(torch.bfloat16, ops=ops, dev="cpu", **ROW_FAULT_SWEEPS[family])
+    assert len(rec.checked) + len(rec.failures) == n and ops.applied > 0, (len(rec.checked), len(rec.failures), n, ops.applied)
+    print(f"{fault}: applied at {ops.applied} of {n} calls, {len(rec.failures)} failed")
+    assert len(rec.failures) == ops.applied, (fault, ops.applied, len(rec.failures), rec.failures[:3])
+    word = "outside" if fault.startswith("store_in") else "beyond their bound|differ|not admissible"
+    import re
+    assert all(re.search(word, f) for f in rec.failures), rec.failures[:3]
+
+
+class Refused(RuntimeError):
+    pass
+
+
+class RejectingRowOps(HonestRowOps):
+    """the argument checks the launchers make before any launch (csrc/rowops.hip CHECK_ROW / DISPATCH_NIT, csrc/optim.hip), restated:
+    (-1) XL_ERR_BAD_SHAPE, (-3) XL_ERR_UNALIGNED"""
+
+    def _row(self, what, N, limit=8):
+        V = 8 if self.dtype == torch.bfloat16 else 4
+        if N <= 0 or N % V:
+            raise Refused(f"{what} failed (-1): row length {N} must be a multiple of {V}")
+        if -(-N // (64 * V)) > limit:
+            raise Refused(f"{what} failed (-1): row length {N} too large")
+
+    def layernorm_fwd(self, x, gamma, beta, y, mean, rstd, M, N, eps):
+        self._row("xl_layernorm_fwd", N)
+        super().layernorm_fwd(x, gamma, beta, y, mean, rstd, M, N, eps)
+
+    def layernorm_fwd_res(self, x, gamma, beta, y32, y16, mean, rstd, M, N, eps):
+        if N <= 0 or N % 4:
+            raise Refused(f"xl_layernorm_fwd_res failed (-1): row length {N}")
+        if x.data_ptr() % 16 or y32.data_ptr() % 16 or y16.data_ptr() % 8:
+            raise Refused("xl_layernorm_fwd_res failed (-3): unaligned rows")
+        raise AssertionError("not reached by the rejected family")
+
+    def visn_ln_fwd(self, xv, pos, wbox, bbox, gv, bv, gb, bb, y, mean_v, rstd_v, mean_b, rstd_b, M, N, P, eps):
+        self._row("xl_visn_ln_fwd", N)
+        if not 1 <= P <= 8:
+            raise Refused(f"xl_visn_ln_fwd failed (-1): pos dim {P} not in 1..8")
+        super().visn_ln_fwd(xv, pos, wbox, bbox, gv, bv, gb, bb, y, mean_v, rstd_v, mean_b, rstd_b, M, N, P, eps)
+
+    def embed_bwd(self, dpre, ids, tt, dword, dpos, dtype_tab, B, L, N, order=None, n_types=2):
+        self._row("xl_embed_bwd", N)
+        if N > 1024:
+            raise Refused(f"xl_embed_bwd failed (-1): hidden size {N} > 1024")
+        super().embed_bwd(dpre, ids, tt, dword, dpos, dtype_tab, B, L, N, order=order, n_types=n_types)
+
+    def adamw(self, p, g, m, v, p_compute, decay_flags, sumsq, lr_and_steps, n, *a, **kw):
+        if n <= 0 or n % 256:
+            raise Refused(f"xl_adamw failed (-1): n={n} must be a positive multiple of 256")
+        if any(t.data_ptr() % 16 for t in (p, g, m, v)):
+            raise Refused("xl_adamw failed (-3): unaligned buffer")
+        super().adamw(p, g, m, v, p_compute, decay_flags, sumsq, lr_and_steps, n, *a, **kw)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp32"])
+def test_rowop_rejected_calls_raise_and_write_nothing_over_the_restated_argument_checks(dt):
+    import test_rowop_edges_bounds_gpu as R
+    R.run_rejected(R.DTYPES[dt], ops=RejectingRowOps(R.DTYPES[dt]), dev="cpu", error=Refused)

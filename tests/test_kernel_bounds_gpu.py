@@ -34,7 +34,7 @@ import torch
 
 import bounds as BD
 import lxmert_oracle as O
-from fake_ops import FakeOps, keep_scale
+from fake_ops import FakeOps, ce_in_regs, keep_scale
 
 pytestmark = pytest.mark.gpu
 
@@ -226,6 +226,250 @@ def sdpa_kernel(direction, nq, nk, dh, lds, aligned, tr_read=True, dtype=torch.b
 SDPA_KERNELS = tuple(f"sdpa_{d}_{k}" for d in ("fwd", "bwd") for k in ("mfma", "flash", "long", "generic"))
 
 
+# ------------------------------------------------------------------------------------------- row kernels and optimizer: dispatch
+def _env_int(k, d):
+    import os
+    e = os.environ.get(k)
+    try:
+        return int(e) if e not in (None, "") else d
+    except ValueError:
+        return 0                                          # (atoi)
+
+
+def _tn(t):
+    return "none" if t is None else {torch.bfloat16: "bf16", torch.float32: "f32"}.get(t.dtype, str(t.dtype))
+
+
+def _vec(t):
+    return 8 if t.dtype == torch.bfloat16 else 4
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _nit(N, per, steps=(1, 2, 4, 8)):
+    """DISPATCH_NIT / DISPATCH_NIT_RES: ceil(N / per) rounded up to the next instantiated count; None: XL_ERR_BAD_SHAPE"""
+    n = _cdiv(N, per)
+    return next((k for k in steps if n <= k), None)
+
+
+def _ws(a, key="ws"):
+    return " workspace" if a.get(key) is not None else " atomics"
+
+
+def _k_layernorm_bwd(a):
+    M, N, x = a["M"], a["N"], a["x"]
+    blocks = _cdiv(M, 8)
+    dma = (_env_int("XL_LN_BWD_DMA", 1) and x.dtype == torch.bfloat16 and N <= 1024 and N % 8 == 0
+           and M >= _env_int("XL_LN_BWD_DMA_MIN_ROWS", 2 * 512 * 8) and M * N * 2.0 < 2.0e9 and _al16(a["dy"]) and _al16(x))
+    name = f"ln_bwd_dma_kernel<{1 if N <= 512 else 2}>" if dma else f"ln_bwd_kernel<{_tn(x)}> NIT={_nit(N, 64 * _vec(x))}"
+    return name + (" grid-capped" if blocks > 512 else "") + _ws(a)
+
+
+def _k_visn(direction):
+    def f(a):
+        M, N, P, xv = a["M"], a["N"], a["P"], a["xv"]
+        lds = P <= 4 and N <= 128 * _vec(xv)
+        cap = 512 if (direction == "fwd" and lds) else 256 if direction == "bwd" else None
+        blocks = _cdiv(M, 8 if lds else 4)
+        name = (f"visn_ln_{direction}_lds_kernel<{_tn(xv)}> NIT={1 if N <= 64 * _vec(xv) else 2}" if lds
+                else f"visn_ln_{direction}_kernel<{_tn(xv)}> NIT={_nit(N, 64 * _vec(xv))}")
+        name += " grid-capped" if (cap is not None and blocks > cap) else ""
+        return name + (_ws(a) if direction == "bwd" else "")
+    return f
+
+
+def _k_embed_bwd(a):
+    d = a["dpre"]
+    passes = _nit(a["N"], 64 * _vec(d), (1, 2, 4))
+    return (f"embed_bwd_{'sorted_' if a['order'] is not None else ''}kernel<{_tn(d)}> passes={passes}"
+            + (" + type kernel" if (a["tt"] is not None and a["n_types"] > 1) else "") + " + pos kernel")
+
+
+def _k_colsum(masked):
+    def f(a):
+        M, rpb = a["M"], 128
+        if a["ws"] is not None:
+            while _cdiv(M, rpb) > 128:
+                rpb *= 2
+        return f"colsum_kernel<{_tn(a['x'])}>{' masked' if masked else ''} rows_per_block={rpb} slabs={_cdiv(M, rpb)}" + _ws(a)
+    return f
+
+
+def _k_ce(a):
+    M, K, dl = a["M"], a["K"], a["dlogits"]
+    K8 = (K + 7) // 8 * 8
+    if not ce_in_regs(a["logits"], dl, K, a["ldl"], a["lddl"]):
+        name, cap = "ce_kernel (scalar)", None
+    elif K8 > 256 * 8 * 5:
+        name, cap = "ce_row_kernel<4,1024>", 1024
+    elif K8 > 256 * 8 * 2:
+        name, cap = "ce_row_kernel<5,256>", 2048
+    else:
+        name, cap = "ce_row_kernel<2,256>", 2048
+    return name + (" row loop" if (cap is not None and M > cap) else "") + f" dlogits {_tn(dl)}"
+
+
+def _k_sumsq(a):
+    n = a["n"]
+    n4 = n >> 2
+    grid = min(max(_cdiv(n4, 256), 1), 512)
+    stride = grid * 256
+    unrolled = n4 > 3 * stride                                  # thread 0 enters the 4x unrolled loop
+    rounds = _cdiv(n4 - 3 * stride, 4 * stride) if unrolled else 0
+    single = n4 > 4 * stride * rounds                           # ... and is left with i < n4 behind it
+    return f"sumsq_kernel grid={grid}" + (" unrolled" if unrolled else "") + (" single" if single else "") + (" tail" if n & 3 else "")
+
+
+def _k_adamw(a):
+    n4 = a["n"] >> 2
+    mb = _env_int("XL_ADAMW_BLOCKS", 256)
+    grid = min(mb if mb > 0 else 256, _cdiv(n4, 1024))
+    return (f"adamw_kernel passes={_cdiv(n4, grid * 1024)} compute copy {_tn(a['p_compute'])}"
+            + (" flags" if a["decay_flags"] is not None else "") + (" chunk_steps" if a["chunk_steps"] is not None else "")
+            + (" clip" if (a["max_norm"] > 0 and a["sumsq"] is not None) else "") + (" zero_grad" if a["zero_grad"] else ""))
+
+
+def _k_schedule(a):
+    done = int(a["step"][0])
+    if done < a["warmup_steps"]:
+        return "schedule_step_kernel warm-up"
+    return "schedule_step_kernel decay" + (" clamped" if done >= a["total_steps"] else "")
+
+
+_ROWOP = {
+    "layernorm_fwd": lambda a: f"ln_fwd_kernel<{_tn(a['x'])}> NIT={_nit(a['N'], 64 * _vec(a['x']))}",
+    "layernorm_bwd": _k_layernorm_bwd,
+    "layernorm_fwd_res": lambda a: f"ln_fwd_res_kernel NIT={_nit(a['N'], 256, (1, 2, 3, 4, 8))}",
+    "layernorm_bwd_res": lambda a: (f"ln_bwd_res_kernel NIT={_nit(a['N'], 256, (1, 2, 3, 4, 8))}"
+                                    + (" grid-capped" if _cdiv(a["M"], 8) > 512 else "") + _ws(a)),
+    "visn_ln_fwd": _k_visn("fwd"), "visn_ln_bwd": _k_visn("bwd"),
+    "embed_ln_fwd": lambda a: f"embed_ln_fwd_kernel<{_tn(a['word'])}> NIT={_nit(a['N'], 64 * _vec(a['word']))}",
+    "embed_bwd": _k_embed_bwd,
+    "colsum": _k_colsum(False), "masked_colsum": _k_colsum(True),
+    "ce_fwd_bwd": _k_ce,
+    "sumsq": _k_sumsq, "adamw": _k_adamw, "schedule_step": _k_schedule,
+    "codebook_gather": lambda a: f"codebook_gather_kernel<{_tn(a['feats'])}>" + (" masked" if a["vis_mask"] is not None else ""),
+    "dropout": lambda a: f"dropout_kernel<{_tn(a['x'])}>",
+    "gelu_bwd": lambda a: f"gelu_bwd_kernel<{_tn(a['dx'])}> (A-S erf)",
+    "tanh_bwd": lambda a: f"tanh_bwd_kernel<{_tn(a['dx'])}>",
+    "bce_logits_fwd_bwd": lambda a: "bce_logits_kernel" + (f" dlogits {_tn(a['dlogits'])}" if a["dlogits"] is not None else " (no gradient)"),
+    "gather_rows": lambda a: f"move_rows_kernel<{_tn(a['src'])}> gather",
+    "scatter_rows": lambda a: f"move_rows_kernel<{_tn(a['src'])}> scatter",
+    "gather_labels": lambda a: "gather_labels_kernel",
+    "mask_counts": lambda a: "mask_counts_kernel",
+    "featloss_fwd_bwd": lambda a: (f"featloss_kernel<{_tn(a['pred'])}>" + (" rows" if a["rows"] is not None else "")
+                                   + (" targets" if a["targets"] is not None else " centroids")),
+    "cast_from_f32": lambda a: f"cast_from_f32_kernel<{_tn(a['dst'])}>",
+    "cast_to_f32": lambda a: f"cast_to_f32_kernel<{_tn(a['src'])}>",
+    "take_f32": lambda a: "take_f32_kernel", "put_f32": lambda a: "put_f32_kernel",
+    "rowmax_combine": lambda a: "rowmax_combine_kernel", "remask_lowest": lambda a: "remask_lowest_kernel",
+    "sampler_update": lambda a: "sampler_update_kernel",
+    "sampler_ar_update": lambda a: "sampler_ar_update_kernel " + ("(fixed position)" if a["fixed_pos"] >= 0 else "(most confident)"),
+}
+
+
+def rowop_kernel(name, a):
+    """the kernel(s) an entry point of csrc/rowops.hip / csrc/optim.hip launches for the arguments `a` (the call's tensors and
+    scalars by parameter name), as gemm_kernel restates csrc/gemm.hip: the kernel's name and template arguments and what the launcher
+    branches on --
+      NIT=k          DISPATCH_NIT / DISPATCH_NIT2 / DISPATCH_NIT_RES: 64-lane passes over a row (None: the launcher rejects N)
+      grid-capped    the grid is capped (LayerNorm backward 512 blocks of 8 rows, feature-encoder backward 256 blocks), blocks loop
+      workspace / atomics   the column sums leave through partial slabs and reduce_partials_kernel, or through atomics
+      ln_bwd_dma_kernel<1|2>   bf16, N <= 512 | 1024, N % 8 == 0, M >= 8192 rows, < 2e9 bytes, dy and x on 16 bytes
+      visn_ln_*_lds_kernel      P <= 4 and N <= 128 VEC
+      embed_bwd_[sorted_]kernel passes=1|2|4 [+ type kernel] + pos kernel
+      colsum_kernel rows_per_block=R slabs=G   (R doubles until G <= 128 with a workspace)
+      ce_row_kernel<4,1024> / <5,256> / <2,256> [row loop]  or  ce_kernel (scalar)
+      sumsq_kernel grid=G [unrolled] [single] [tail];  adamw_kernel passes=k ...;  schedule_step_kernel warm-up / decay [clamped]
+    An entry point without a branch is labelled by its kernel and element type."""
+    f = _ROWOP.get(name)
+    return f(a) if f is not None else name
+
+
+def _t(t, *shape):
+    """(tensor, shape, contiguous strides) of an output view, None for an absent tensor"""
+    if t is None:
+        return None
+    st, acc = [], 1
+    for n in reversed(shape):
+        st.append(acc)
+        acc *= n
+    return (t, tuple(shape), tuple(reversed(st)))
+
+
+def _t2(t, rows, cols, ld):
+    return None if t is None else (t, (rows, cols), (ld, 1))
+
+
+def _whole(t):
+    return None if t is None else (t, tuple(t.shape), tuple(t.stride()))
+
+
+def _o_ce(a):
+    K = a["K"]
+    Kw = (K + 7) // 8 * 8 if ce_in_regs(a["logits"], a["dlogits"], K, a["ldl"], a["lddl"]) else K      # the register kernels zero K..K8
+    M = a["M"]
+    return [_t2(a["dlogits"], M, Kw, a["lddl"]), _t(a["loss_out"], 1), _t(a["row_lse"], M), _t(a["row_argmax"], M), _t(a["row_maxprob"], M)]
+
+
+def _o_ln_bwd(a):
+    M, N = a["M"], a["N"]
+    dropped = a["dx_dropped"] is not None and a["p_drop"] > 0            # (p_drop == 0: the launcher drops the pointer -- not written)
+    return [_t(a["dx"], M, N), _t(a["dgamma"], N), _t(a["dbeta"], N), _t(a["dbias_prev"], N), _whole(a["ws"]),
+            _t(a["dx_dropped"], M if dropped else 0, N)]
+
+
+def _o_visn_bwd(a):
+    M, N, P = a["M"], a["N"], a["P"]
+    return [_t(a["dxv"], M, N)] + [_t(a[k], N) for k in ("dgv", "dbv", "dgb", "dbb", "dbbox", "dbias_visn")] + [_t(a["dwbox"], N * P), _whole(a["ws"])]
+
+
+def _o_adamw(a):
+    n = a["n"]
+    pc = a["p_compute"] if (a["p_compute"] is not None and a["p_compute"].data_ptr() != a["p"].data_ptr()) else None
+    return [_t(a["p"], n), _t(a["m"], n), _t(a["v"], n), _t(a["g"], n if a["zero_grad"] else 0), _t(pc, n)]
+
+
+def _o_featloss(a):
+    n = a["B"] * a["V"] if a["rows"] is None else a["n_rows"]
+    return [_t(a["dpred"], n, a["F"]), _t(a["loss_out"], 1)]
+
+
+# name -> the logical views a call may write (everything else of the outputs' storages stays bit-identical: "outside view")
+ROW_OUTS = {
+    "layernorm_fwd": lambda a: [_t(a["y"], a["M"], a["N"]), _t(a["mean"], a["M"]), _t(a["rstd"], a["M"])],
+    "layernorm_bwd": _o_ln_bwd,
+    "visn_ln_fwd": lambda a: [_t(a["y"], a["M"], a["N"])] + [_t(a[k], a["M"]) for k in ("mean_v", "rstd_v", "mean_b", "rstd_b")],
+    "visn_ln_bwd": _o_visn_bwd,
+    "embed_ln_fwd": lambda a: [_t(a["y"], a["B"] * a["L"], a["N"]), _t(a["pre"], a["B"] * a["L"], a["N"]),
+                               _t(a["mean"], a["B"] * a["L"]), _t(a["rstd"], a["B"] * a["L"])],
+    "embed_bwd": lambda a: [_whole(a["dword"]), _whole(a["dpos"]), _whole(a["dtype_tab"])],
+    "codebook_gather": lambda a: [_t(a["feats"], a["M"], a["F"])],
+    "dropout": lambda a: [_t2(a["y"], a["M"], a["N"], a["ldy"])],
+    "gelu_bwd": lambda a: [_t(a["dx"], a["n"])], "tanh_bwd": lambda a: [_t(a["dx"], a["n"])],
+    "colsum": lambda a: [_t(a["out"], a["N"]), _whole(a["ws"])],
+    "masked_colsum": lambda a: [_t(a["out"], a["N"]), _whole(a["ws"])],
+    "cast_from_f32": lambda a: [_t(a["dst"], a["n"])], "cast_to_f32": lambda a: [_t(a["dst"], a["n"])],
+    "take_f32": lambda a: [_t(a["dst"], a["idx"].numel())], "put_f32": lambda a: [_whole(a["dst"])],
+    "gather_rows": lambda a: [_t2(a["dst"], a["n_rows"], a["N"], a["ld_dst"])],
+    "scatter_rows": lambda a: [_t2(a["dst"], int(a["rows"].reshape(-1)[:a["n_rows"]].max()) + 1, a["N"], a["ld_dst"])],
+    "gather_labels": lambda a: [_t(a["out"], a["n_rows"])],
+    "mask_counts": lambda a: [_t(a["counts"], 1), _t(a["nmask"], a["B"])],
+    "ce_fwd_bwd": _o_ce,
+    "featloss_fwd_bwd": _o_featloss,
+    "bce_logits_fwd_bwd": lambda a: [_t2(a["dlogits"], a["M"], a["ld_dlogits"], a["ld_dlogits"]), _t(a["loss"], 1)],
+    "sumsq": lambda a: [_t(a["out"], 1), _whole(a.get("scratch"))],
+    "schedule_step": lambda a: [_t(a["step"], 1), _t(a["lr_and_steps"], 4)],
+    "adamw": _o_adamw,
+    "rowmax_combine": lambda a: [_t(a["row_maxprob"], a["M"]), _t(a["row_argmax"], a["M"]), _t(a["row_lse"], a["M"])],
+    "remask_lowest": lambda a: [_t(a["vis_mask"], a["B"] * a["V"])],
+    "sampler_update": lambda a: [_t(a["code_ids"], a["n"])],
+    "sampler_ar_update": lambda a: [_t(a[k], a["B"] * a["V"]) for k in ("code_ids", "vis_mask", "visited")],
+}
+
+
 class Recorder:
     """stands in for the step's HipOps: forwards every attribute, checks the first call of each signature"""
 
@@ -252,10 +496,19 @@ class Recorder:
         object.__setattr__(self, "_tr_read", True)      # xl_set_lds_transpose_read (library default 1): part of the attention dispatch
         object.__setattr__(self, "_sw", gemm_switches())   # the xl_gemm switches forwarded so far: part of the GEMM dispatch
         object.__setattr__(self, "_ws_slabs", {})       # stream -> slabs of the workspace registered on it (gemm_workspace)
+        object.__setattr__(self, "_kern", None)         # rowop_kernel(...) of the call being checked (taken BEFORE the call runs)
         object.__setattr__(self, "lse_excluded", [])    # (method, shape, number of lse entries left out: queries without a valid key)
 
     def mark(self, tag):
         object.__setattr__(self, "_tag", tag)
+
+    @staticmethod
+    def _rowops():
+        return _ROWOP
+
+    @staticmethod
+    def _row_outs():
+        return ROW_OUTS
 
     def retry(self):
         """A destination may receive two contributions between flushes (the shared cross-attention's q / k / v bias: one sdpa_bwd
@@ -339,6 +592,9 @@ class Recorder:
                 key += (("kernel", self._gemm_kernel(a)),)
             elif name == "gemm_wgrad_group":
                 key += (("kernel", tuple(wgrad_group_kernel(a["problems"], a["overwrite_mask"], self._switches())[1])),)
+            elif name in self._rowops():            # (the same for the launchers of csrc/rowops.hip and csrc/optim.hip)
+                object.__setattr__(self, "_kern", rowop_kernel(name, a))
+                key += (("kernel", self._kern),)
             if name in STEP_KEYED or (name == "gemm" and a["epilogue"] == BD.EPI_ROWMAX):
                 key += (("step", self._tag),)
             dests = self._dests(name, a) if self._deferred else []
@@ -360,7 +616,11 @@ class Recorder:
                 _sync()
                 return r
             try:
+                outs = self._row_outs().get(name)
+                guard = self._guard([o for o in outs(a) if o is not None], "outside view") if outs is not None else None
                 res = chk(a, s, run)
+                if guard is not None:
+                    res.append(guard(res[0][2] if res else self._kern))
             except Exception as e:          # (a checker that fails still leaves the call done: the step goes on)
                 if not ran:
                     run()
@@ -518,7 +778,7 @@ class Recorder:
         it = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]
         return torch.tensor([], dtype=it, device=t.device).set_(st, 0, (st.nbytes() // t.element_size(),), (1,))
 
-    def _guard(self, outs):
+    def _guard(self, outs, what="C outside view"):
         """outs: [(tensor, shape, stride)] -- the logical views this call may write (strides in elements of the tensor's type, from
         its storage offset).  Snapshots the bit patterns of every storage involved; the returned function, called after the run,
         holds every element outside all the views to its earlier bits and returns the result row."""
@@ -533,7 +793,7 @@ class Recorder:
                 for t, shape, stride in views:          # inside the views: whatever the call wrote
                     torch.as_strided(was, shape, stride, t.storage_offset()).copy_(torch.as_strided(now, shape, stride, t.storage_offset()))
                 BD.check_exact(now, was, f"{self._cur[0]} stores outside the [M, N] views of its outputs (storage of {len(now)} elements)")
-            return ("C outside view", 0.0, kern)
+            return (what, 0.0, kern)
         return after
 
     def chk_gemm(self, a, s, run):
@@ -594,7 +854,7 @@ class Recorder:
         n_seg, M = a["n_seg"], a["M"]
         ws_in = a["ws"].reshape(-1)[:n_seg * M * 4].clone()          # the records the kernel reads (fp32: the argmax is a bit pattern)
         run()
-        kern = "rowmax_combine_kernel"
+        kern = self._kern
         res = [(w, r, kern) for w, r in BD.check_rowmax_combine(self._ref, ws_in, n_seg, M, a["row_maxprob"], a["row_argmax"],
                                                                  a["row_lse"])]
         if self._rowmax is not None and self._rowmax[0] == a["ws"].data_ptr():
@@ -616,20 +876,20 @@ class Recorder:
         self._ref.remask_lowest(s["prob"], s["vis_mask"], B, V, n_mask)
         got = a["vis_mask"].reshape(-1)[:B * V].view(B, V)
         cnt = torch.full((B,), n_mask, device=got.device)
-        return [("vis_mask", BD.check_exact(got.long(), s["vis_mask"].reshape(-1)[:B * V].view(B, V).long(), "remask_lowest"), "remask_lowest"),
-                ("per-row count", BD.check_exact((got != 0).sum(1), cnt, "remask_lowest count"), "remask_lowest")]
+        return [("vis_mask", BD.check_exact(got.long(), s["vis_mask"].reshape(-1)[:B * V].view(B, V).long(), "remask_lowest"), self._kern),
+                ("per-row count", BD.check_exact((got != 0).sum(1), cnt, "remask_lowest count"), self._kern)]
 
     def chk_sampler_update(self, a, s, run):
         n = a["n"]
         run()
         self._ref.sampler_update(s["pred_ids"], s["vis_mask"], s["code_ids"], n)
-        return [("code_ids", BD.check_exact(a["code_ids"].reshape(-1)[:n], s["code_ids"].reshape(-1)[:n], "sampler_update"), "sampler_update")]
+        return [("code_ids", BD.check_exact(a["code_ids"].reshape(-1)[:n], s["code_ids"].reshape(-1)[:n], "sampler_update"), self._kern)]
 
     def chk_sampler_ar_update(self, a, s, run):
         B, V = a["B"], a["V"]
         run()
         self._ref.sampler_ar_update(s["prob"], s["pred_ids"], s["visited"], s["vis_mask"], s["code_ids"], B, V, a["fixed_pos"])
-        kern = "sampler_ar_update (fixed position)" if a["fixed_pos"] >= 0 else "sampler_ar_update (most confident)"
+        kern = self._kern
         res = [(k, BD.check_exact(a[k].reshape(-1)[:B * V].long(), s[k].reshape(-1)[:B * V].long(), f"sampler_ar_update {k}"), kern)
                for k in ("code_ids", "vis_mask", "visited") if a[k] is not None]
         if a["fixed_pos"] < 0:
@@ -642,12 +902,12 @@ class Recorder:
         n = a["idx"].numel()
         run()
         self._ref.take_f32(s["src"], s["idx"], a["own_lo"], a["own_hi"], s["dst"])
-        return [("dst", BD.check_exact(a["dst"][:n].double(), s["dst"][:n], "take_f32"), "take_f32")]
+        return [("dst", BD.check_exact(a["dst"][:n].double(), s["dst"][:n], "take_f32"), self._kern)]
 
     def chk_put_f32(self, a, s, run):
         run()
         self._ref.put_f32(s["dst"], s["idx"], s["src"])
-        return [("dst", BD.check_exact(a["dst"].double(), s["dst"], "put_f32"), "put_f32")]
+        return [("dst", BD.check_exact(a["dst"].double(), s["dst"], "put_f32"), self._kern)]
 
     def chk_bce_logits_fwd_bwd(self, a, s, run):
         M, N, ld = a["M"], a["N"], a["ld_dlogits"]
@@ -655,7 +915,7 @@ class Recorder:
         prev = float(s["loss"][0])
         run()
         self._ref.bce_logits_fwd_bwd(**s)
-        kern = "bce_logits_kernel" + ("" if a["dlogits"] is not None else " (no gradient)")
+        kern = self._kern
         dl = _v2(s["dlogits"], M, ld, ld) if a["dlogits"] is not None else torch.zeros(M, N, dtype=torch.float64, device=x.device)
         b_dl, b_loss = BD.bce_bounds(x, t, M, N, dl[:, :N], float(s["loss"][0]), prev,
                                      a["dlogits"].dtype if a["dlogits"] is not None else torch.float32)
@@ -786,7 +1046,7 @@ class Recorder:
         self._ref.layernorm_fwd(**s)
         x, y = _v2(s["x"], M, N, N).clone(), _v2(s["y"], M, N, N)
         by, bm, br = BD.ln_fwd_bounds(x, s["gamma"].double(), y, s["mean"][:M], s["rstd"][:M], a["y"].dtype)
-        kern = "ln_fwd_kernel"
+        kern = self._kern
         return [("y", BD.check(_v2(a["y"], M, N, N), y, by, "layernorm_fwd y"), kern),
                 ("mean", BD.check(a["mean"][:M], s["mean"][:M], bm, "layernorm_fwd mean"), kern),
                 ("rstd", BD.check(a["rstd"][:M], s["rstd"][:M], br, "layernorm_fwd rstd"), kern)]
@@ -805,7 +1065,7 @@ class Recorder:
         self._ref.layernorm_bwd(**s)
         dx = _v2(s["dx"], M, N, N)
         bdx, t, bdg, bdb = BD.ln_bwd_bounds(dy, x, s["gamma"].double(), mean, rstd, dx, a["dx"].dtype)
-        kern = "ln_bwd_dma_kernel" if (M >= 16384 and N == 768) else "ln_bwd_kernel"
+        kern = self._kern
         res = [("dx", BD.check(_v2(a["dx"], M, N, N), dx, bdx, "layernorm_bwd dx"), kern)]
         self._sum_out(res, "dgamma", a["dgamma"], s["dgamma"], prev["dgamma"], bdg + BD.U32 * (s["dgamma"].abs() + prev["dgamma"].abs()), kern)
         self._sum_out(res, "dbeta", a["dbeta"], s["dbeta"], prev["dbeta"], bdb + BD.U32 * (s["dbeta"].abs() + prev["dbeta"].abs()), kern)
@@ -815,9 +1075,16 @@ class Recorder:
             res.append(("dx_dropped", BD.check(_v2(a["dx_dropped"], M, N, N), dd, bdd, "layernorm_bwd dx_dropped"), kern))
             if a["dbias_prev"] is not None:
                 ref = s["dbias_prev"]
-                bb = (BD.U16 * dd.abs() + BD.SLACK * keep * t).sum(0) + BD.SLACK * (M + 1) * BD.U32 * (
-                    dd.abs().sum(0) + prev["dbias_prev"].abs()) + BD.U32 * ref.abs() + BD.TINY
+                # (the kernel adds the fp32 dropped value BEFORE its store: a summand carries the fp32 term and the rounding of
+                #  the multiply by the keep scale, no output rounding)
+                bb = BD.ln_bwd_bias_bound(keep * t + BD.U32 * dd.abs(), dd, prev["dbias_prev"], ref)
                 self._sum_out(res, "dbias_prev", a["dbias_prev"], ref, prev["dbias_prev"], bb, kern)
+        elif a["dbias_prev"] is not None:
+            # without dropout (the eval-mode path, or no dropped copy asked for) the kernel still writes it: the column sums of
+            # the fp32 dx BEFORE its store (no rounding of the summands)
+            ref = s["dbias_prev"]
+            self._sum_out(res, "dbias_prev", a["dbias_prev"], ref, prev["dbias_prev"],
+                          BD.ln_bwd_bias_bound(t, dx, prev["dbias_prev"], ref), kern)
         return res
 
     def _box(self, s, M, N, P):
@@ -838,7 +1105,7 @@ class Recorder:
         b1, bmv, brv = BD.ln_fwd_bounds(xv, s["gv"].double(), ya, mv, rv, torch.float64)
         b2, bmb, brb = BD.ln_fwd_bounds(box, s["gb"].double(), yb, mb, rb, torch.float64, x_err=berr)
         by = BD.unit(a["y"].dtype) * y.abs() + 0.5 * (b1 + b2) + BD.SLACK * BD.U32 * y.abs()
-        kern = "visn_ln_fwd"
+        kern = self._kern
         return [("y", BD.check(_v2(a["y"], M, N, N), y, by, "visn_ln_fwd y"), kern),
                 ("mean_v", BD.check(a["mean_v"][:M], s["mean_v"][:M], bmv, "visn mean_v"), kern),
                 ("rstd_v", BD.check(a["rstd_v"][:M], s["rstd_v"][:M], brv, "visn rstd_v"), kern),
@@ -863,7 +1130,7 @@ class Recorder:
         b1, t1, bg1, bb1 = BD.ln_bwd_bounds(dh, xv, s["gv"].double(), mean_v, rstd_v, d1, a["dxv"].dtype)
         _, t2, bg2, bb2 = BD.ln_bwd_bounds(dh, box, s["gb"].double(), mean_b, rstd_b, d2, torch.float64, x_err=berr)
         t2 = BD.SLACK * t2
-        kern = "visn_ln_bwd"
+        kern = self._kern
 
         res = [("dxv", BD.check(_v2(a["dxv"], M, N, N), _v2(s["dxv"], M, N, N), b1, "visn_ln_bwd dxv"), kern)]
 
@@ -887,7 +1154,7 @@ class Recorder:
         wsum = (s["word"][s["ids"].reshape(-1).long()].abs() + s["pos"][torch.arange(L, device=pre.device).repeat(B)].abs()
                 + s["type_"][s["tt"].reshape(-1).long()].abs())
         bpre = BD.unit(a["pre"].dtype) * pre.abs() + BD.SLACK * 2 * BD.U32 * wsum + BD.TINY
-        kern = "embed_ln_fwd"
+        kern = self._kern
         res = [("pre", BD.check(_v2(a["pre"], M, N, N), pre, bpre, "embed pre"), kern)]
         gpre = _v2(a["pre"], M, N, N).double()              # the kernel normalises the STORED sum (csrc/rowops.hip)
         y, m, r = FakeOps._ln(gpre, s["gamma"].double(), s["beta"].double(), a["eps"])
@@ -903,11 +1170,16 @@ class Recorder:
         tabs = ("dword", "dpos", "dtype_tab")
         absd = {k: s[k].abs() for k in tabs}                 # |prev| + sum of |terms| (the same scatter on absolute values)
         sa = dict(s, dpre=_v2(s["dpre"], M, N, N).abs().contiguous(), **absd)
+        rows0 = torch.cat([s[k][0].reshape(-1).clone() for k in tabs])
         run()
         self._ref.embed_bwd(**sa)
         self._ref.embed_bwd(**s)
-        return [(k, BD.check(a[k], s[k], BD.U32 * s[k].abs() + BD.SLACK * (M + 1) * BD.U32 * sa[k] + BD.TINY, f"embed_bwd {k}"),
-                 "embed_bwd (sorted rows)" if a["order"] is not None else "embed_bwd (scan)") for k in tabs]
+        res = [(k, BD.check(a[k], s[k], BD.U32 * s[k].abs() + BD.SLACK * (M + 1) * BD.U32 * sa[k] + BD.TINY, f"embed_bwd {k}"),
+                self._kern) for k in tabs]
+        # padding_idx = 0: row 0 of the word, the position and the token-type table is frozen
+        res.append(("rows 0 frozen", BD.check_exact(torch.cat([a[k][0].reshape(-1).double() for k in tabs]), rows0,
+                                                    "embed_bwd rows 0 of the three tables"), self._kern))
+        return res
 
     # ------------------------------------------------------------------------------------------------ elementwise / copies
     def chk_codebook_gather(self, a, s, run):
@@ -916,14 +1188,14 @@ class Recorder:
         self._ref.codebook_gather(**s)
         ref = _v2(s["feats"], M, F, F)
         return [("feats", BD.check(_v2(a["feats"], M, F, F), ref, BD.unit(a["feats"].dtype) * ref.abs() + BD.TINY, "codebook"),
-                 "codebook_gather")]
+                 self._kern)]
 
     def chk_dropout(self, a, s, run):
         M, N = a["M"], a["N"]
         run()
         self._ref.dropout(**s)
         ref = _v2(s["y"], M, N, a["ldy"])
-        return [("y", BD.check(_v2(a["y"], M, N, a["ldy"]), ref, BD.scaled_copy_bound(ref, a["y"].dtype), "dropout"), "dropout")]
+        return [("y", BD.check(_v2(a["y"], M, N, a["ldy"]), ref, BD.scaled_copy_bound(ref, a["y"].dtype), "dropout"), self._kern)]
 
     def chk_gelu_bwd(self, a, s, run):
         n = a["n"]
@@ -932,7 +1204,7 @@ class Recorder:
         self._ref.gelu_bwd(**s)
         ref = s["dx"].reshape(-1)[:n]
         return [("dx", BD.check(a["dx"].reshape(-1)[:n], ref, BD.gelu_bwd_bound(dy, pre, ref, a["dx"].dtype), "gelu_bwd"),
-                 "gelu_bwd (A-S erf)")]
+                 self._kern)]
 
     def chk_tanh_bwd(self, a, s, run):
         n = a["n"]
@@ -940,7 +1212,7 @@ class Recorder:
         run()
         self._ref.tanh_bwd(**s)
         ref = s["dx"].reshape(-1)[:n]
-        return [("dx", BD.check(a["dx"].reshape(-1)[:n], ref, BD.tanh_bwd_bound(dy, y, ref, a["dx"].dtype), "tanh_bwd"), "tanh_bwd")]
+        return [("dx", BD.check(a["dx"].reshape(-1)[:n], ref, BD.tanh_bwd_bound(dy, y, ref, a["dx"].dtype), "tanh_bwd"), self._kern)]
 
     def _colsum_like(self, name, a, s, run):
         M, N = a["M"], a["N"]
@@ -952,7 +1224,7 @@ class Recorder:
         ref = s["out"][:N]
         bnd = BD.U32 * ref.abs() + BD.SLACK * (M + 1) * BD.U32 * sa["out"][:N] + BD.TINY
         res = []
-        self._sum_out(res, "out", a["out"][:N], ref, prev, bnd, name + " (two-stage)")
+        self._sum_out(res, "out", a["out"][:N], ref, prev, bnd, self._kern)
         return res
 
     def chk_colsum(self, a, s, run):
@@ -966,7 +1238,7 @@ class Recorder:
         run()
         getattr(self._ref, name)(**s)
         ref = s["dst"].reshape(-1)[:n]
-        return [("dst", BD.check(a["dst"].reshape(-1)[:n], ref, BD.unit(a["dst"].dtype) * ref.abs() + BD.TINY, name), name)]
+        return [("dst", BD.check(a["dst"].reshape(-1)[:n], ref, BD.unit(a["dst"].dtype) * ref.abs() + BD.TINY, name), self._kern)]
 
     def chk_cast_from_f32(self, a, s, run):
         return self._cast("cast_from_f32", a, s, run)
@@ -979,7 +1251,7 @@ class Recorder:
         run()
         self._ref.gather_rows(**s)
         return [("dst", BD.check_exact(_v2(a["dst"], n, N, a["ld_dst"]).double(), _v2(s["dst"], n, N, a["ld_dst"]), "gather_rows"),
-                 "gather_rows")]
+                 self._kern)]
 
     def chk_scatter_rows(self, a, s, run):
         n, N = a["n_rows"], a["N"]
@@ -987,20 +1259,20 @@ class Recorder:
         run()
         self._ref.scatter_rows(**s)
         return [("dst", BD.check_exact(_v2(a["dst"], rows, N, a["ld_dst"]).double(), _v2(s["dst"], rows, N, a["ld_dst"]),
-                                       "scatter_rows"), "scatter_rows")]
+                                       "scatter_rows"), self._kern)]
 
     def chk_gather_labels(self, a, s, run):
         n = a["n_rows"]
         run()
         self._ref.gather_labels(**s)
-        return [("out", BD.check_exact(a["out"].reshape(-1)[:n], s["out"].reshape(-1)[:n], "gather_labels"), "gather_labels")]
+        return [("out", BD.check_exact(a["out"].reshape(-1)[:n], s["out"].reshape(-1)[:n], "gather_labels"), self._kern)]
 
     def chk_mask_counts(self, a, s, run):
         B, V = a["B"], a["V"]
         run()
         self._ref.mask_counts(**s)
-        return [("counts", BD.check_exact(a["counts"][:1].double(), s["counts"][:1], "mask_counts"), "mask_counts"),
-                ("nmask", BD.check_exact(a["nmask"][:B].double(), s["nmask"][:B], "mask_counts nmask"), "mask_counts")]
+        return [("counts", BD.check_exact(a["counts"][:1].double(), s["counts"][:1], "mask_counts"), self._kern),
+                ("nmask", BD.check_exact(a["nmask"][:B].double(), s["nmask"][:B], "mask_counts nmask"), self._kern)]
 
     # ------------------------------------------------------------------------------------------------ losses
     def chk_ce_fwd_bwd(self, a, s, run):
@@ -1016,18 +1288,28 @@ class Recorder:
         dl = _v2(s["dlogits"], M, K, a["lddl"]) if a["dlogits"] is not None else torch.zeros_like(lg)
         blse, bdl = BD.ce_bounds(lg, valid, a["grad_scale"] / cnt, lse, dl, a["dlogits"].dtype if a["dlogits"] is not None
                                  else torch.float32)
-        kern = "ce_fwd_bwd"
+        kern = self._kern
         res = []
         if a["dlogits"] is not None:
-            res.append(("dlogits", BD.check(_v2(a["dlogits"], M, K, a["lddl"]), dl, bdl, "ce dlogits"), kern))
+            # the register kernels also write the slots K .. K8 of a row, with zeros: inside the view, exactly zero
+            Kw = (K + 7) // 8 * 8 if ce_in_regs(a["logits"], a["dlogits"], K, a["ldl"], a["lddl"]) else K
+            ref_w, b_w = torch.zeros(M, Kw, dtype=torch.float64, device=lg.device), torch.zeros(M, Kw, dtype=torch.float64, device=lg.device)
+            ref_w[:, :K], b_w[:, :K] = dl, bdl
+            res.append(("dlogits" + (" (slots K..K8 zero)" if Kw > K else ""),
+                        BD.check(_v2(a["dlogits"], M, Kw, a["lddl"]), ref_w, b_w, "ce dlogits"), kern))
         if a["row_lse"] is not None:
             res.append(("row_lse", BD.check(a["row_lse"][:M], s["row_lse"][:M], blse, "ce row_lse"), kern))
         if a["row_argmax"] is not None:
             got = a["row_argmax"][:M].long()
+            BD.check_exact((got >= 0) & (got < K), torch.ones(M, dtype=torch.bool, device=got.device), "ce row_argmax (an index of the row)")
             mx = lg.amax(1)
             res.append(("row_argmax", BD.check_exact(lg.gather(1, got[:, None])[:, 0], mx, "ce row_argmax (value at the index)"), kern))
             unique = (lg == mx[:, None]).sum(1) == 1
             res.append(("row_argmax idx", BD.check_exact(got[unique], s["row_argmax"][:M].long()[unique], "ce row_argmax"), kern))
+            # the admissibility rule (bounds.argmax_admissible) on exact inputs, E = 0: the LOWEST index of the maximum, ties included
+            n_adm = BD.check_admissible(lg, got, torch.zeros(M, dtype=torch.float64, device=lg.device), "ce row_argmax (lowest index of the maximum)")
+            res.append(("row_argmax admissible", 0.0, kern))
+            self.sharp.append((self._tag,) + BD.sharpness(n_adm))
         if a["row_maxprob"] is not None:
             ref = s["row_maxprob"][:M]
             res.append(("row_maxprob", BD.check(a["row_maxprob"][:M], ref, BD.SLACK * ref.abs() * (blse + 2 * BD.U32) + BD.U32 * ref.abs()
@@ -1036,6 +1318,8 @@ class Recorder:
             ref = s["loss_out"][0]
             bl = BD.ce_loss_bound(lg, lab, valid, cnt, blse, float(ref)) + BD.U32 * float(loss_prev[0].abs())
             res.append(("loss", BD.check(a["loss_out"][:1], s["loss_out"][:1], bl, "ce loss"), kern))
+        elif a["loss_out"] is not None:         # no labels: no loss term
+            res.append(("loss untouched", BD.check_exact(a["loss_out"][:1].double(), loss_prev[:1], "ce loss without labels"), kern))
         return res
 
     def chk_featloss_fwd_bwd(self, a, s, run):
@@ -1055,9 +1339,9 @@ class Recorder:
                                     a["dpred"].dtype if a["dpred"] is not None else torch.float32)
         res = []
         if a["dpred"] is not None:
-            res.append(("dpred", BD.check(_v2(a["dpred"], n, F, F), dref, bd, "featloss dpred"), "featloss_fwd_bwd"))
+            res.append(("dpred", BD.check(_v2(a["dpred"], n, F, F), dref, bd, "featloss dpred"), self._kern))
         if a["loss_out"] is not None:
-            res.append(("loss", BD.check(a["loss_out"][:1], s["loss_out"][:1], lb, "featloss loss"), "featloss_fwd_bwd"))
+            res.append(("loss", BD.check(a["loss_out"][:1], s["loss_out"][:1], lb, "featloss loss"), self._kern))
         return res
 
     # ------------------------------------------------------------------------------------------------ optimizer
@@ -1068,7 +1352,7 @@ class Recorder:
         self._ref.sumsq(**s)
         ref = s["out"][:1]
         bnd = BD.sumsq_bound(s["g"][:n], float(ref)) + BD.U32 * abs(prev)
-        return [("out", BD.check(a["out"][:1], ref, bnd, "sumsq"), f"sumsq_kernel ({n} elements)")]
+        return [("out", BD.check(a["out"][:1], ref, bnd, "sumsq"), self._kern)]
 
     def chk_schedule_step(self, a, s, run):
         run()
@@ -1077,35 +1361,53 @@ class Recorder:
         t = float(ref[3])
         scale = torch.tensor([abs(float(ref[0])), a["beta1"] ** t, a["beta2"] ** t, 0.0], dtype=torch.float64, device=ref.device)
         bnd = BD.SLACK * 4 * BD.U32 * scale + BD.U32 * ref.abs() + BD.TINY
-        return [("step", BD.check_exact(a["step"][:1], s["step"][:1], "schedule step"), "schedule_step"),
-                ("lr_and_steps", BD.check(a["lr_and_steps"][:4], ref, bnd, "schedule lr_and_steps"), "schedule_step")]
+        return [("step", BD.check_exact(a["step"][:1], s["step"][:1], "schedule step"), self._kern),
+                ("lr_and_steps", BD.check(a["lr_and_steps"][:4], ref, bnd, "schedule lr_and_steps"), self._kern)]
 
     def chk_adamw(self, a, s, run):
         n = a["n"]
-        g0, m0, v0 = (s[k][:n].clone() for k in ("g", "m", "v"))
+        dev = s["p"].device
+        before = {k: s[k][:n].clone() for k in ("p", "g", "m", "v")}
+        g0, m0, v0 = before["g"], before["m"], before["v"]
+        separate = a["p_compute"] is not None and a["p_compute"].data_ptr() != a["p"].data_ptr()
+        if separate:
+            before["p_compute"] = s["p_compute"][:n].clone()
         lrs = [float(x) for x in s["lr_and_steps"][:3]]
         clip = a["grad_scale"]
         if a["max_norm"] > 0 and a["sumsq"] is not None:
             norm = float(s["sumsq"][0]) ** 0.5 * a["grad_scale"]
             clip *= min(1.0, a["max_norm"] / (norm + 1e-6))
-        assert a["chunk_steps"] is None
-        step = lrs[0] * lrs[2] ** 0.5 / lrs[1]
+        fl = (s["decay_flags"].repeat_interleave(256)[:n] if a["decay_flags"] is not None
+              else torch.zeros(n, dtype=torch.uint8, device=dev))
+        skip, keep_g = (fl & 2) != 0, (fl & 4) != 0
+        if a["chunk_steps"] is not None:        # per-chunk update counts: the kernel derives the step size in fp32 (bounds.adamw_chunk_step)
+            t = s["chunk_steps"].repeat_interleave(256)[:n].double().clamp(min=1)
+            step, step_rel = BD.adamw_chunk_step(lrs[0], a["beta1"], a["beta2"], t)
+        else:
+            step, step_rel = lrs[0] * lrs[2] ** 0.5 / lrs[1], 0.0
+        kern = self._kern
         run()
         self._ref.adamw(**s)
         bp, bm, bv = BD.adamw_bounds(s["p"][:n], s["m"][:n], s["v"][:n], g0, m0, v0, step, clip, a["beta1"], a["beta2"], a["eps"],
-                                     lrs[0], a["weight_decay"])
-        del g0, m0, v0
-        res = [("p", BD.check(a["p"][:n], s["p"][:n], bp, "adamw p"), "adamw"),
-               ("m", BD.check(a["m"][:n], s["m"][:n], bm, "adamw m"), "adamw"),
-               ("v", BD.check(a["v"][:n], s["v"][:n], bv, "adamw v"), "adamw")]
-        if a["p_compute"] is not None and a["p_compute"].data_ptr() != a["p"].data_ptr():
+                                     lrs[0], a["weight_decay"], step_rel=step_rel)
+        res = [("p", BD.check(a["p"][:n], s["p"][:n], bp, "adamw p"), kern),
+               ("m", BD.check(a["m"][:n], s["m"][:n], bm, "adamw m"), kern),
+               ("v", BD.check(a["v"][:n], s["v"][:n], bv, "adamw v"), kern)]
+        if separate:
             ref = s["p_compute"][:n]
             res.append(("p_compute", BD.check(a["p_compute"][:n], ref, BD.unit(a["p_compute"].dtype) * ref.abs() + bp, "adamw p_compute"),
-                        "adamw"))
+                        kern))
         if a["zero_grad"]:
             ref = s["g"][:n]
             kept = torch.isnan(ref)                  # the restatement poisons the chunks the kernel leaves alone
-            res.append(("g cleared", BD.check_exact(a["g"][:n][~kept].double(), ref[~kept], "adamw zero_grad"), "adamw"))
+            res.append(("g cleared", BD.check_exact(a["g"][:n][~kept].double(), ref[~kept], "adamw zero_grad"), kern))
+            if bool((keep_g & ~skip).any()):         # bit 2: the next backward overwrites this chunk -- the gradient stays as it is
+                res.append(("g kept (bit 2)", BD.check_exact(a["g"][:n][keep_g & ~skip].double(), g0[keep_g & ~skip],
+                                                              "adamw gradient of a chunk flagged keep"), kern))
+        if bool(skip.any()):                         # bit 1: a tensor without a gradient this step is not touched at all
+            for k, was in before.items():
+                res.append((f"{k} skipped (bit 1)", BD.check_exact(a[k][:n][skip].double(), was[skip].double(),
+                                                                    f"adamw {k} of a chunk flagged skip"), kern))
         return res
 
 
