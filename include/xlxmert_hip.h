@@ -72,6 +72,16 @@ extern "C" {
                              * a real column's y + g >= -|x| / T - 2.82, so for 1e-3 <= T <= 1e3 (the range the host layers accept)
                              * and |x| < 1e26 a pad column is never drawn and adds exp() = 0 to the sum                          */
 
+#define XL_EPI_ROWSCORE 10   /* no C: XL_EPI_ROWMAX's sibling for forward-only losses (same preconditions, dispatch and padding contract: bf16
+                             * K-major operands, M and N multiples of 256, a 16-byte aligned aux, whole 256x256 tiles, pad columns = zero
+                             * rows of B with bias -1e30; p_drop 0).  `residual` carries `const int64_t* labels`, one label per row of A
+                             * (length M, 8-byte aligned); `ldr` is ignored.  x = alpha * acc + bias[n]:
+                             * aux[(n/64)*M + m] = float4{max_n x, sum_n exp(x - max), argmax_n x (int bits), x_label} over the 64-column
+                             * segment; slots 0-2 are XL_EPI_ROWMAX's, bit for bit (lowest column on a tie); x_label = x[m, labels[m]]
+                             * when labels[m] lies in this segment and -INFINITY otherwise (so also for every label outside [0, N): -100,
+                             * the ignore label).  The forward half of a fused logits + online log-sum-exp cross-entropy: the loss needs
+                             * nothing else of the logits; finish with xl_rowscore_combine.                                              */
+
 const char* xl_last_error(void);
 int  xl_version(void);
 /* Contexts: xl_ctx_create() -> handle (>= 1); xl_ctx_bind(handle) makes it the calling thread's current context (0 = the
@@ -433,6 +443,26 @@ int xl_rowsample_combine(const float* ws, int n_seg, int M, uint64_t seed, float
 int xl_sample_rows(const float* logits, int M, int K, int ldl, float inv_T, uint64_t seed, float* row_prob, int32_t* row_id,
                    float* row_lse, void* stream);
 int xl_gumbel_from_bits(const uint32_t* h, float* g, int n, void* stream);
+
+/* Validation scores: the label's negative log-likelihood, the prediction and the totals of a meter, without gradients.
+ * xl_rowscore_combine: second half of XL_EPI_ROWSCORE over ws[seg*M + m] (labels = the GEMM's; n_cols = the number of REAL columns,
+ *   n_cols <= 64 n_seg: the pad columns' -1e30 never wins and adds exp() = 0).
+ * xl_score_rows: the same outputs from fp32 logits in memory [M, K] (ldl >= K; only columns < K of a row are read), one wave per row:
+ *   fp32 engines, shapes off the 256 grid, the small heads (K = 2 with ldl = 8, 3129 answers).  n_cols = K; labels may be NULL (no
+ *   valid row: predictions and maxima only).
+ * Per row m:  row_pred[m] = argmax_n x (lowest index on ties, as torch.max), row_max[m] = max_n x,
+ *   row_nll[m] = lse - x[m, labels[m]], lse = max + log sum_n exp(x_n - max), for a VALID label 0 <= labels[m] < n_cols; any other
+ *   label (-100, the label xl_gather_labels gives a pad row, anything else) is ignored: row_nll[m] = 0 and the row is not counted.
+ * totals (fp32[4], ACCUMULATED: a meter adds a whole validation epoch on the device and reads it once):
+ *   totals[0] += sum_m row_nll[m], totals[1] += #valid rows, totals[2] += #(valid rows with row_pred[m] == labels[m]); totals[3] is
+ *   not touched.  The sums run in a fixed order -- rows per block, block partials in block order by the last block to arrive (an
+ *   integer ticket) -- with no floating-point atomics: one launch geometry, one bit pattern, run to run.  The partials live in
+ *   library memory, 8 sets handed out round-robin: launches on one stream serialise, at most 8 may overlap on different streams.
+ * Any per-row output may be NULL; totals may be NULL. */
+int xl_rowscore_combine(const float* ws, int n_seg, int M, const int64_t* labels, int n_cols, float* row_nll, int32_t* row_pred,
+                        float* row_max, float* totals, void* stream);
+int xl_score_rows(const float* logits, int M, int K, int ldl, const int64_t* labels, float* row_nll, int32_t* row_pred,
+                  float* row_max, float* totals, void* stream);
 
 /* Truncated sampling: xl_sample_rows with top-k, top-p (nucleus) and min-p cuts; one workgroup per row, K <= 65536, only columns
  * < K of a row are read (ldl >= K), finite logits.  For row m:  y_n = logits[m, n] * inv_T (ONE fp32 multiply; -0 counts as +0),

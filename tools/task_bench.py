@@ -1,6 +1,9 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint|eval] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+--rows eval: the validation pass alone (bs 256): ms per Engine.evaluate_task for vis_mask (`--vis_mask_predict` masks, n ~ U{1..64}) and
+word_mask (labelled rows from the loader), on the fused path (XL_EPI_ROWSCORE records) and on the logits path (XL_FUSED_PREDICT=0),
+alternating in this process with their yardstick, Engine.task_forward(task, want_grad=False): all rows, fp32 logits.
 --rows caption: the Mask-Predict caption sampler alone (bs 256, L = 20, T = 10, ragged lengths): ms per batch and captions/s, greedy on
 the fused and on the logits predict path and with the visual stack recomputed every step, in one alternation with the arms below.
 --rows inpaint: Engine.inpaint_codes alone (bs 256, Mask-Predict T = 4, half of every grid free): ms per batch, greedy (and drawn, with
@@ -18,7 +21,7 @@ from xlxmert_amd.config import XLxmertConfig
 from xlxmert_amd.trainer import PretrainStep, word_rows_of
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint"), default="all")
+ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint", "eval"), default="all")
 ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
 ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
 ap.add_argument("--top-k", type=int, default=None, help="truncated arm: at most K candidates (1..256)")
@@ -175,6 +178,51 @@ def inpaint_row(B=256, T=4):
         print(f"  {k:16s}: median {med * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}  {B / med:9.0f} images/s")
 
 
+def eval_row(B=256, L=20):
+    from xlxmert_amd.trainer import synthetic_batch
+    for task in ("vis_mask", "word_mask"):
+        store = ParamStore(cfg, dev, torch.bfloat16, task=task)
+        init_reference_weights(store, 1)
+        g = torch.Generator().manual_seed(0)
+        store.set_centroids(torch.randn(cfg.num_clusters, cfg.visual_feat_dim, generator=g).relu())
+        eng = Engine(cfg, store, HipOps(torch.bfloat16), B, L, 64, need_lang=task != "vis_mask", train_dropout=False)
+        eng.sync_compute_weights()
+        b = cuda(synthetic_batch(cfg, B, L, 8, seed=5))
+        common = dict(lang_rows=b["lang_rows"], lang_off=b["lang_off"], word_order=b["word_order"])
+        if task == "vis_mask":
+            eng.set_inputs(b["input_ids"], b["attention_mask"], None, b["visual_pos"], cluster_ids=b["cluster_ids"], vis_mask=b["vis_mask"],
+                           obj_labels=b["obj_labels"], masked_rows=b["masked_rows"], **common)
+            kw, rows, of = {"feat_loss": False}, eng.n_mrows, eng.MV
+        else:
+            wl, _ = O.make_lang_task_labels(oc, b["input_ids"].cpu(), 3)
+            eng.set_inputs(b["input_ids"], b["attention_mask"], None, b["visual_pos"], cluster_ids=b["cluster_ids"], **common)
+            kw = {"word_labels": wl.cuda(), "word_rows": word_rows_of(wl)}
+            eng.lang_heads.set_rows(kw["word_rows"])
+            rows, of = eng.lang_heads.n_rows, eng.MLd
+
+        def ev(fused):
+            os.environ["XL_FUSED_PREDICT"] = "1" if fused else "0"
+            try:
+                eng.evaluate_task(task, **kw)
+            finally:
+                os.environ["XL_FUSED_PREDICT"] = "1"
+        fkw = {k: v for k, v in kw.items() if k != "word_rows"}
+        arms = {"evaluate fused": lambda: ev(True), "evaluate logits path": lambda: ev(False),
+                "task_forward(want_grad=False)": lambda: eng.task_forward(task, want_grad=False, **fkw)}
+        runs = {k: [] for k in arms}
+        for _ in range(args.rounds):
+            for k, fn in arms.items():
+                runs[k].append(timed(fn, warm=1))
+        print(f"evaluate {task:9s} bs {B:4d}: head on {rows} of {of} rows")
+        for k, v in runs.items():
+            v = sorted(v)
+            med = v[len(v) // 2]
+            print(f"  {k:30s}: median {med * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}  {B / med:9.0f} examples/s")
+        del eng, store
+
+
+if args.rows == "eval":
+    eval_row()
 if args.rows in ("all", "caption"):
     caption_row()
 if args.rows == "inpaint":

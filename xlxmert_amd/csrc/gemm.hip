@@ -340,10 +340,10 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     XL_CHECK_ARG(M > 0 && N > 0 && K > 0, XL_ERR_BAD_SHAPE, "xl_gemm: bad shape M=%d N=%d K=%d", M, N, K);
     XL_CHECK_ARG(in_dtype == XL_F32 || in_dtype == XL_BF16, XL_ERR_BAD_DTYPE, "xl_gemm: bad in_dtype %d", in_dtype);
     XL_CHECK_ARG(out_dtype == in_dtype || out_dtype == XL_F32, XL_ERR_BAD_DTYPE, "xl_gemm: bad out_dtype %d", out_dtype);
-    XL_CHECK_ARG(A && B && (C || epilogue == XL_EPI_ROWMAX || epilogue == XL_EPI_ROWSAMPLE), XL_ERR_BAD_ARG, "xl_gemm: null operand");
+    XL_CHECK_ARG(A && B && (C || epilogue == XL_EPI_ROWMAX || epilogue == XL_EPI_ROWSAMPLE || epilogue == XL_EPI_ROWSCORE), XL_ERR_BAD_ARG, "xl_gemm: null operand");
     XL_CHECK_ARG(lda >= (a_kmajor ? K : M) && ldb >= (b_kmajor ? K : N) && ldc >= N, XL_ERR_BAD_SHAPE,
                  "xl_gemm: leading dimension too small (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
-    XL_CHECK_ARG(epilogue >= XL_EPI_NONE && epilogue <= XL_EPI_ROWSAMPLE, XL_ERR_BAD_ARG, "xl_gemm: bad epilogue %d", epilogue);
+    XL_CHECK_ARG(epilogue >= XL_EPI_NONE && epilogue <= XL_EPI_ROWSCORE, XL_ERR_BAD_ARG, "xl_gemm: bad epilogue %d", epilogue);
     const bool res32 = epilogue == XL_EPI_RESIDUAL_F32;       // fp32 residual stream: fp32 operand and output, A / B as in_dtype says
     if (res32) XL_CHECK_ARG(residual && ldr >= N && out_dtype == XL_F32 && !colsum_out, XL_ERR_BAD_ARG,
                             "xl_gemm: XL_EPI_RESIDUAL_F32 needs an fp32 residual, out_dtype XL_F32 and no colsum_out");
@@ -358,6 +358,14 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
                      ldb % 8 == 0 && aux && aligned16(aux) && aligned16(A) && aligned16(B) && (!bias || aligned16(bias)) &&
                      !accumulate && !colsum_out && cx.use_tr_read && p_drop == 0.f, XL_ERR_BAD_SHAPE,
                      "xl_gemm: XL_EPI_ROWSAMPLE takes bf16 K-major operands with M, N multiples of 256 (M=%d N=%d), a 16-byte aligned aux and p_drop 0", M, N);
+    const bool rowscore = epilogue == XL_EPI_ROWSCORE;        // validation losses: XL_EPI_ROWMAX's preconditions and dispatch, labels in `residual`
+    if (rowscore)
+        XL_CHECK_ARG(in_dtype == XL_BF16 && a_kmajor && b_kmajor && M % 256 == 0 && N % 256 == 0 && K % 8 == 0 && lda % 8 == 0 &&
+                     ldb % 8 == 0 && aux && aligned16(aux) && aligned16(A) && aligned16(B) && (!bias || aligned16(bias)) &&
+                     !accumulate && !colsum_out && cx.use_tr_read && p_drop == 0.f && residual &&
+                     (reinterpret_cast<uintptr_t>(residual) & 7) == 0, XL_ERR_BAD_SHAPE,
+                     "xl_gemm: XL_EPI_ROWSCORE takes bf16 K-major operands with M, N multiples of 256 (M=%d N=%d), a 16-byte aligned aux, "
+                     "int64 labels[M] in `residual` and p_drop 0", M, N);
     if (epilogue == XL_EPI_RESIDUAL) XL_CHECK_ARG(residual && ldr >= N, XL_ERR_BAD_ARG, "xl_gemm: residual missing");
     if (epilogue == XL_EPI_GELU || epilogue == XL_EPI_DGELU || epilogue == XL_EPI_GELU_DG || epilogue == XL_EPI_MULAUX)
         XL_CHECK_ARG(aux && ldx >= N, XL_ERR_BAD_ARG, "xl_gemm: aux missing");
@@ -394,7 +402,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     // workgroups they drop into the 64 idle CUs instead of competing for all of them (-0.5 ms per step)
     long pp_blocks = t256n;
     if (may_split && t256n < 256 && K >= 1024) pp_blocks = t256n * std::max<long>(1, std::min<long>(256 / t256n, K / 512));
-    const bool use_pp = pp_ok && (pp_mode == 2 || (pp_mode == 1 && pp_blocks >= pp_min_tiles) || epilogue == XL_EPI_ROWMAX || rowsample);
+    const bool use_pp = pp_ok && (pp_mode == 2 || (pp_mode == 1 && pp_blocks >= pp_min_tiles) || epilogue == XL_EPI_ROWMAX || rowsample || rowscore);
     const int tile = use_pp ? 256 : mfma_ok ? 128 : 64;
     p.tiles_m = (M + tile - 1) / tile;
     // 256x192 tiles (forward / dX layouts with a fast epilogue, every tile interior): taken when they shorten the launch,
@@ -413,7 +421,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     const int bn192_mode = cx.gemm_bn192;
     int bn = 256;
     if (use_pp && bn192_mode && a_kmajor && M % 256 == 0 && N % 192 == 0 && out_dtype == in_dtype && !accumulate &&
-        colsum_out == nullptr && epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && !rowsample) {
+        colsum_out == nullptr && epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && !rowsample && !rowscore) {
         const long t256 = (long)p.tiles_m * ((N + 255) / 256), t192 = (long)p.tiles_m * (N / 192);
         const double c256 = (double)((t256 + 255) / 256), c192 = 0.8 * (double)((t192 + 255) / 256);
         if (bn192_mode == 2 || c192 < c256) bn = 192;
@@ -454,6 +462,10 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
         XL_CHECK_ARG(use_pp, XL_ERR_BAD_SHAPE, "xl_gemm: XL_EPI_ROWSAMPLE needs the ping-pong kernel's operand ranges");
         p.vec_epi = 1;
     }
+    if (rowscore) {
+        XL_CHECK_ARG(use_pp, XL_ERR_BAD_SHAPE, "xl_gemm: XL_EPI_ROWSCORE needs the ping-pong kernel's operand ranges");
+        p.vec_epi = 1;
+    }
     if (epilogue == XL_EPI_RESIDUAL) p.vec_epi = p.vec_epi && aligned16(residual) && ldr % 8 == 0;
     if (res32) p.vec_epi = p.vec_epi && aligned16(residual) && ldr % 4 == 0;
     if (epilogue == XL_EPI_GELU || epilogue == XL_EPI_DGELU || epilogue == XL_EPI_GELU_DG || epilogue == XL_EPI_MULAUX)
@@ -483,7 +495,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     static const int split_epi_min_k = env_int("XL_GEMM_SPLIT_EPI_MIN_K", 1536);
     static const int split_epi_max_tiles = env_int("XL_GEMM_SPLIT_EPI_MAX_TILES", 80);
     bool epi_split = false;
-    if (split_epi && pp_ok && pp_mode && a_kmajor && epik >= 0 && epik != XL_EPI_ROWMAX && !rowsample && out_dtype == in_dtype && !accumulate &&
+    if (split_epi && pp_ok && pp_mode && a_kmajor && epik >= 0 && epik != XL_EPI_ROWMAX && !rowsample && !rowscore && out_dtype == in_dtype && !accumulate &&
         colsum_out == nullptr && splitk == 1 && !p.atomic_out && K >= split_epi_min_k && K % 64 == 0 && M % 256 == 0 &&
         (double)M * lda < 1e9) {
         const int e_bn = (N % 192 == 0 && (N % 256 != 0 || (M / 256) * (N / 192) <= 256)) ? 192 : (N % 256 == 0 ? 256 : 0);
@@ -514,7 +526,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     if (cx.gemm_relay_wgs < 0) cx.gemm_relay_wgs = env_int("XL_GEMM_RELAY_WGS", 256);
     const int relay_wgs = cx.gemm_relay_wgs;
     if (!epi_split && pp_ok && pp_mode && cx.gemm_relay && a_kmajor && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && K >= 768 &&
-        out_dtype == in_dtype && !accumulate && epik >= 0 && !rowsample && colsum_out == nullptr && splitk == 1 && !p.atomic_out &&
+        out_dtype == in_dtype && !accumulate && epik >= 0 && !rowsample && !rowscore && colsum_out == nullptr && splitk == 1 && !p.atomic_out &&
         relay_has_instance(b_kmajor, epik) &&
         (cx.gemm_relay == 2 || (t256n >= relay_min_tiles && K <= relay_max_k))) {
         p.tiles_m = M / 256; p.tiles_n = N / 256;
@@ -537,7 +549,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     static const int q_max_n = env_int("XL_GEMM_Q_MAX_N", 2304);
     static const int q_max_tiles = env_int("XL_GEMM_Q_MAX_TILES", 1 << 30);
     if (!epi_split && pp_ok && pp_mode && cx.gemm_q && a_kmajor && M % 128 == 0 && N % 192 == 0 && K % 64 == 0 && out_dtype == in_dtype &&
-        !accumulate && epik >= 0 && !rowsample && colsum_out == nullptr && splitk == 1 && !p.atomic_out && q_has_instance(b_kmajor, epik) &&
+        !accumulate && epik >= 0 && !rowsample && !rowscore && colsum_out == nullptr && splitk == 1 && !p.atomic_out && q_has_instance(b_kmajor, epik) &&
         (double)M * lda < 1e9 && (cx.gemm_q == 2 || (K <= q_max_k && N <= q_max_n && (long)(M / 128) * (N / 192) >= q_min_tiles && (long)(M / 128) * (N / 192) <= q_max_tiles))) {
         p.tiles_m = M / 128; p.tiles_n = N / 192;
         p.splitk = 1; p.kper = K; p.tail_tiles = 0;
@@ -555,7 +567,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     static const int duo_max_tiles = env_int("XL_GEMM_DUO_MAX_TILES", 64);
     int bm = 256;
     if (!epi_split && pp_ok && pp_mode && cx.gemm_duo && a_kmajor && M % 128 == 0 && N % 192 == 0 && (out_dtype == in_dtype || res32) && !accumulate && epik >= 0 &&
-        colsum_out == nullptr && epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && !rowsample && splitk == 1 && !p.atomic_out &&
+        colsum_out == nullptr && epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && !rowsample && !rowscore && splitk == 1 && !p.atomic_out &&
         (double)M * lda < 1e9 && (cx.gemm_duo == 2 || t256n <= duo_max_tiles)) {
         bm = 128; bn = 192;
         p.tiles_m = M / 128; p.tiles_n = N / 192;
@@ -572,7 +584,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     // contraction, K = 2048, 1320 tiles, does not gain -- 338 -> 368 us -- hence the depth threshold)
     if (cx.tail_max < 0) { cx.tail_max = env_int("XL_GEMM_TAIL_MAX", 64); cx.tail_min_k = env_int("XL_GEMM_TAIL_MIN_K", 4096); }
     const int tail_max = cx.tail_max, tail_min_k = cx.tail_min_k;
-    if (use_pp && !epi_split && !rowsample && bm == 256 && splitk == 1 && !p.atomic_out && tiles > 256 && tiles % 256 <= tail_max && tiles % 256 > 0 && K >= tail_min_k) {
+    if (use_pp && !epi_split && !rowsample && !rowscore && bm == 256 && splitk == 1 && !p.atomic_out && tiles > 256 && tiles % 256 <= tail_max && tiles % 256 > 0 && K >= tail_min_k) {
         const int rem = tiles % 256;
         int S = std::min(std::min(256 / rem, K / 512), 8);          // >= 8 K tiles per slice, <= 7 slabs for the last arriver to add
         if (S >= 2) {
@@ -591,7 +603,7 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
     // the epilogue, no workgroup hand-over between tiles) -- OPT-IN: faster alone, slower inside the four-stream step
     if (cx.gemm_persist < 0) cx.gemm_persist = env_int("XL_GEMM_PERSIST", 0);      // opt-in: see gemm_pp_persist.hip
     static const int persist_max_k = env_int("XL_GEMM_PERSIST_MAX_K", 1536);
-    if (use_pp && cx.gemm_persist && bn == 256 && bm == 256 && a_kmajor && epik >= 0 && epik != XL_EPI_TANH && epik != XL_EPI_ROWMAX && !rowsample &&
+    if (use_pp && cx.gemm_persist && bn == 256 && bm == 256 && a_kmajor && epik >= 0 && epik != XL_EPI_TANH && epik != XL_EPI_ROWMAX && !rowsample && !rowscore &&
         epik != XL_EPI_RESIDUAL && out_dtype == XL_BF16 && !p.atomic_out && p.splitk == 1 && p.tail_tiles == 0 && M % 256 == 0 &&
         N % 256 == 0 && K % 64 == 0 && K >= 128 && K <= persist_max_k && tiles > n_cu && (colsum_out == nullptr || colsum_fused) &&
         (double)M * lda < 1e9 && cx.gemm_trace == nullptr) {
@@ -608,6 +620,11 @@ extern "C" int xl_gemm(const void* A, const void* B, void* C, const float* bias,
         XL_CHECK_ARG(epik == XL_EPI_ROWSAMPLE && bm == 256 && bn == 256 && splitk == 1 && p.tail_tiles == 0, XL_ERR_BAD_SHAPE,
                      "xl_gemm: XL_EPI_ROWSAMPLE has the fast epilogue on whole 256x256 tiles only");
         hipError_t e = launch_pp_sample(p, nblk, st);
+        XL_CHECK_ARG(e == hipSuccess, XL_ERR_HIP, "xl_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    } else if (rowscore) {
+        XL_CHECK_ARG(epik == XL_EPI_ROWSCORE && bm == 256 && bn == 256 && splitk == 1 && p.tail_tiles == 0, XL_ERR_BAD_SHAPE,
+                     "xl_gemm: XL_EPI_ROWSCORE has the fast epilogue on whole 256x256 tiles only");
+        hipError_t e = launch_pp_score(p, nblk, st);
         XL_CHECK_ARG(e == hipSuccess, XL_ERR_HIP, "xl_gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     } else if ((use_pp || bm == 128) && epik == XL_EPI_RESIDUAL_F32 && a_kmajor) {
         hipError_t e = launch_pp_res32(p, b_kmajor, bm, nblk, st);
@@ -656,7 +673,7 @@ extern "C" int xl_gemm_pair(const void* A0, const void* B0, void* C0, const floa
     bool one = cx.gemm_pair != 0 && cx.gemm_pp != 0 && cx.use_tr_read && in_dtype == XL_BF16 && out_dtype == XL_BF16 && a_kmajor &&
                M0 > 0 && M1 > 0 && N > 0 && K > 0 && N % 256 == 0 && K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 &&
                lda >= K && ldb >= (b_kmajor ? K : N) && ldc >= N && p_drop >= 0.f && p_drop < 1.f &&
-               epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && epilogue != XL_EPI_ROWSAMPLE && pp_pair_has_instance(b_kmajor, epilogue) &&
+               epilogue != XL_EPI_TANH && epilogue != XL_EPI_ROWMAX && epilogue != XL_EPI_ROWSAMPLE && epilogue != XL_EPI_ROWSCORE && pp_pair_has_instance(b_kmajor, epilogue) &&
                (double)(b_kmajor ? N : K) * ldb < 1e9;
     long tiles[2] = {0, 0};
     for (int i = 0; i < 2 && one; ++i) {

@@ -500,9 +500,25 @@ __device__ __forceinline__ uint64_t dropout_seed_of(const GemmParams& p) {
     else return 0;
 }
 
+// XL_EPI_ROWSCORE: the labels of a wave's 128 tile rows (`residual` = const int64_t* labels, one per row of A), lane l holding the
+// labels of rows mw + l and mw + 64 + l -- requested ahead of the K loop like the dropout seed, for the same reason -- and their
+// reduction to the column the epilogue looks for (-1: no column of this launch)
+struct ScoreLabels { int64_t lo, hi; };
+template <int EPI>
+__device__ __forceinline__ ScoreLabels score_labels_of(const GemmParams& p, int mw, int lane) {
+    ScoreLabels s = {0, 0};
+    if constexpr (EPI == XL_EPI_ROWSCORE) {
+        const int64_t* lab = reinterpret_cast<const int64_t*>(p.residual) + mw + lane;
+        s.lo = lab[0]; s.hi = lab[64];
+    }
+    return s;
+}
+__device__ __forceinline__ int score_label_col(const GemmParams& p, int64_t lab) { return (lab >= 0 && lab < (int64_t)p.N) ? (int)lab : -1; }
+
 template <int EPI, int NPS = 8>
 __device__ __forceinline__ void epilogue_rows_fast(const GemmParams& p, const float* wbuf, int lane, bool first, int mq, int nq,
-                                                   const QuadOperand& op, float (&cs)[8], const float (&bv)[8], uint64_t seed) {
+                                                   const QuadOperand& op, float (&cs)[8], const float (&bv)[8], uint64_t seed,
+                                                   [[maybe_unused]] int lab = -1) {      // lab (XL_EPI_ROWSCORE): label column of row mq + lane
     const int c8 = lane & 7, rr = lane >> 3;
     const int n = nq + c8 * 8;
     const bool drop = p.p_drop > 0.0f;      // (seed: dropout_seed_of(p), fetched by the caller BEFORE its K loop -- fetched here, the
@@ -561,6 +577,32 @@ __device__ __forceinline__ void epilogue_rows_fast(const GemmParams& p, const fl
             }
             if (c8 == 0)
                 reinterpret_cast<float4*>(p.aux)[(size_t)(nq >> 6) * p.M + m] = make_float4(mx, se, __int_as_float(idx), 0.f);
+        } else if constexpr (EPI == XL_EPI_ROWSCORE) {
+            // XL_EPI_ROWMAX's record (the same arithmetic and tie rule) with the label's logit in the fourth slot: the row's label
+            // column comes from the lane that holds it (ds_bpermute), the lane whose 8 columns contain it supplies x, -inf otherwise
+            const int lc = __shfl(lab, row, 64);
+            float mx = v[0];
+            int idx = n;
+#pragma unroll
+            for (int e = 1; e < 8; ++e) if (v[e] > mx) { mx = v[e]; idx = n + e; }
+            float se = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) se += __expf(v[e] - mx);
+            float xl = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xl = (n + e == lc) ? v[e] : xl;
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                const float omx = __shfl_xor(mx, o, 64), ose = __shfl_xor(se, o, 64);
+                const int oi = __shfl_xor(idx, o, 64);
+                const float nm = fmaxf(mx, omx);
+                se = se * __expf(mx - nm) + ose * __expf(omx - nm);
+                idx = (omx > mx || (omx == mx && oi < idx)) ? oi : idx;
+                mx = nm;
+                xl = fmaxf(xl, __shfl_xor(xl, o, 64));
+            }
+            if (c8 == 0)
+                reinterpret_cast<float4*>(p.aux)[(size_t)(nq >> 6) * p.M + m] = make_float4(mx, se, __int_as_float(idx), xl);
         } else if constexpr (EPI == XL_EPI_ROWSAMPLE) {
             // (max, sum exp(y - max)) of the segment as XL_EPI_ROWMAX has them, and the Gumbel-max draw s = argmax_n (y_n + g_n) with
             // its y_s: z = y + g lives in registers across the lane merge (the same fp32 expression that a merge of two stored
@@ -842,6 +884,8 @@ hipError_t launch_pp(const GemmParams& p, int a_kmajor, int b_kmajor, int epik, 
 hipError_t launch_pp_res32(const GemmParams& p, int b_kmajor, int bm, int nblk, hipStream_t st);
 // gemm_pp_sample.hip: the XL_EPI_ROWSAMPLE instance of the ping-pong kernel (both operands K-major, 256x256 tiles, every tile interior)
 hipError_t launch_pp_sample(const GemmParams& p, int nblk, hipStream_t st);
+// gemm_pp_score.hip: the XL_EPI_ROWSCORE instance of the ping-pong kernel (both operands K-major, 256x256 tiles, every tile interior)
+hipError_t launch_pp_score(const GemmParams& p, int nblk, hipStream_t st);
 // gemm_pp_pair.hip: two problems per launch (gemm_pp_kernel.h gemm_bf16_pp_pair_kernel), 256x256 tiles, A K-major, fast epilogue;
 // hipErrorInvalidValue: no instance for this (layout, epilogue kind) -- forward layout: NONE / RESIDUAL / GELU_DG, dX layout:
 // NONE / RESIDUAL / MULAUX.  tiles0: problem 0's tile count (linear tiles [0, tiles0) are its, the rest problem 1's)

@@ -275,6 +275,8 @@ __device__ __forceinline__ void pp_tile(const GemmParams& p, int tm, int tn, int
     // the epilogue's bias segment is requested before the first DMA: older than every counted load, so the K loop's vmcnt
     // arithmetic is unchanged, and its latency (a full miss after 15 us of streaming operands) is off the epilogue's front
     [[maybe_unused]] const uint64_t dseed = dropout_seed_of<EPIK>(p);
+    [[maybe_unused]] ScoreLabels slab = {0, 0};
+    if constexpr (EPIK == XL_EPI_ROWSCORE) slab = score_labels_of<EPIK>(p, m0 + wr * WTM, lane);      // (every tile interior)
     float bias8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     [[maybe_unused]] float bias8b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // BN = 192: third column fragment
     if constexpr (EPIK >= 0) {
@@ -411,6 +413,21 @@ __device__ __forceinline__ void pp_tile(const GemmParams& p, int tm, int tn, int
                     if (p.trace != nullptr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(3); }
                     return;
                 }
+            } else if constexpr (EPIK == XL_EPI_ROWSCORE) {
+                // no operand rows: the two quads' label columns (fetched ahead of the K loop) ride into the row passes
+                static_assert(BM == 256 && BN == 256, "XL_EPI_ROWSCORE: 256x256 tiles");
+                QuadOperand none;
+                float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                const int lab0 = score_label_col(p, slab.lo), lab1 = score_label_col(p, slab.hi);
+                quad_to_lds(wbuf, lane, acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
+                __builtin_amdgcn_sched_barrier(0);
+                epilogue_rows_fast<EPIK>(p, wbuf, lane, first, mw, nw, none, cs, bias8, dseed, lab0);
+                __builtin_amdgcn_sched_barrier(0);
+                quad_to_lds(wbuf, lane, acc[2][0], acc[2][1], acc[3][0], acc[3][1]);
+                __builtin_amdgcn_sched_barrier(0);
+                epilogue_rows_fast<EPIK>(p, wbuf, lane, first, mw + 64, nw, none, cs, bias8, dseed, lab1);
+                if (p.trace != nullptr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(3); }
+                return;
             } else
             if (mw + 128 <= p.M && nw + 64 <= p.N) {
                 // the first quad's operand rows are requested before its transpose, the second quad's as soon as the first

@@ -2354,6 +2354,152 @@ extern "C" int xl_rowmax_combine(const float* ws, int n_seg, int M, float* row_m
     return XL_OK;
 }
 
+// ---- validation scores (include/xlxmert_hip.h xl_rowscore_combine / xl_score_rows): per row the negative log-likelihood of its
+// label, the argmax and the maximum, and per launch totals += {sum of nll, valid rows, valid rows whose argmax is the label}.
+// The totals are bit-reproducible: no floating-point atomics.  Every block adds its rows in a fixed order and leaves one partial;
+// the block that arrives last (an INTEGER ticket, the agent-scope release / acquire pair of gemm_common.h slab_exchange) adds the
+// partials in block order and performs the one read-modify-write of `totals`.  Partials and tickets live in device memory of the
+// library, SCORE_SLOTS sets handed out round-robin per launch: launches on one stream serialise, and up to SCORE_SLOTS launches
+// may be in flight on different streams.
+constexpr int SCORE_SLOTS = 8;
+constexpr int SCORE_MAX_BLOCKS = 1024;
+__device__ __attribute__((aligned(16))) float g_score_part[SCORE_SLOTS][SCORE_MAX_BLOCKS][4];
+__device__ int g_score_ticket[SCORE_SLOTS];
+static int score_slot() {
+    static std::mutex mu;
+    static unsigned next = 0;
+    std::lock_guard<std::mutex> g(mu);
+    return (int)(next++ % SCORE_SLOTS);
+}
+
+// wave 0 of every block, all 64 lanes, (s, c, h) = the block's sums on lane 0: partial -> ticket -> the last block adds them all
+__device__ __forceinline__ void score_totals_commit(float s, float c, float h, int lane, int slot, float* totals) {
+    float* part = &g_score_part[slot][0][0];
+    if (lane == 0) *reinterpret_cast<float4*>(part + 4 * blockIdx.x) = make_float4(s, c, h, 0.f);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    int t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(&g_score_ticket[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = __shfl(t, 0, 64);
+    if (t != (int)gridDim.x - 1) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int b = lane; b < (int)gridDim.x; b += 64) {                    // lane-strided in block order, then the fixed butterfly
+        const float4 v = *reinterpret_cast<const float4*>(part + 4 * b);
+        a0 += v.x; a1 += v.y; a2 += v.z;
+    }
+    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
+    if (lane == 0) {
+        totals[0] += a0; totals[1] += a1; totals[2] += a2;
+        __hip_atomic_store(&g_score_ticket[slot], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the slot's next launch
+    }
+}
+
+// second half of the GEMM's XL_EPI_ROWSCORE epilogue over the [n_seg][M] records {max, sum exp, argmax, x_label}: the thread layout of
+// rowmax_combine_kernel (64 rows per block pass, four threads per row, merged through LDS); the label's logit is the one record
+// slot that is not -inf
+__global__ __launch_bounds__(256) void rowscore_combine_kernel(const float4* __restrict__ ws, int n_seg, int M,
+                                                               const int64_t* __restrict__ labels, int n_cols, float* row_nll,
+                                                               int* row_pred, float* row_max, float* totals, int slot) {
+    __shared__ float4 part[4][64];
+    const int r = threadIdx.x & 63, q = threadIdx.x >> 6;
+    float ts = 0.f, tc = 0.f, th = 0.f;                                  // wave 0: this lane's rows, in row order
+    for (int base = blockIdx.x * 64; base < M; base += gridDim.x * 64) {
+        const int m = base + r;
+        float mx = -INFINITY, se = 0.f, xl = -INFINITY;
+        int idx = 0x7fffffff;
+        if (m < M)
+            for (int s = q; s < n_seg; s += 4) {
+                const float4 rec = ws[(size_t)s * M + m];
+                rowmax_merge(mx, se, idx, rec.x, rec.y, __float_as_int(rec.z));
+                xl = fmaxf(xl, rec.w);
+            }
+        __syncthreads();                                                 // (the previous pass's reads of part)
+        part[q][r] = make_float4(mx, se, __int_as_float(idx), xl);
+        __syncthreads();
+        if (q != 0 || m >= M) continue;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+            const float4 o = part[k][r];
+            if (o.y > 0.f) { rowmax_merge(mx, se, idx, o.x, o.y, __float_as_int(o.z)); xl = fmaxf(xl, o.w); }
+        }
+        const int64_t lab = labels ? labels[m] : -100;
+        const bool valid = lab >= 0 && lab < n_cols;
+        const float nll = valid ? (mx + logf(se)) - xl : 0.f;
+        if (row_nll) row_nll[m] = nll;
+        if (row_pred) row_pred[m] = idx;
+        if (row_max) row_max[m] = mx;
+        ts += nll; tc += valid ? 1.f : 0.f; th += (valid && idx == (int)lab) ? 1.f : 0.f;
+    }
+    if (q != 0 || totals == nullptr) return;
+    score_totals_commit(wave_sum(ts), wave_sum(tc), wave_sum(th), r, slot, totals);
+}
+
+// The same outputs from fp32 logits in memory: one wave per row (sample_rows_kernel's layout), only columns < K are read; pass 1
+// the maximum and the argmax (ascending columns per lane and a strict >: the lower column on a tie), pass 2 the sum of exp(x - max)
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int M, int K, int ldl,
+                                                         const int64_t* __restrict__ labels, float* row_nll, int* row_pred,
+                                                         float* row_max, float* totals, int slot) {
+    __shared__ float red[WPB][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float ts = 0.f, tc = 0.f, th = 0.f;                                  // lane 0 of every wave: its rows, in row order
+    for (int m = blockIdx.x * WPB + wave; m < M; m += gridDim.x * WPB) {
+        const float* x = logits + (size_t)m * ldl;
+        float mx = -INFINITY;
+        int idx = 0x7fffffff;
+        for (int n = lane; n < K; n += 64) {
+            const float v = x[n];
+            if (v > mx) { mx = v; idx = n; }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float omx = __shfl_xor(mx, o, 64);
+            const int oi = __shfl_xor(idx, o, 64);
+            const bool take = omx > mx || (omx == mx && oi < idx);
+            mx = take ? omx : mx; idx = take ? oi : idx;
+        }
+        float se = 0.f;
+        for (int n = lane; n < K; n += 64) se += __expf(x[n] - mx);
+        se = wave_sum(se);
+        if (lane != 0) continue;
+        const int64_t lab = labels ? labels[m] : -100;
+        const bool valid = lab >= 0 && lab < K;
+        const float nll = valid ? (mx + logf(se)) - x[lab] : 0.f;
+        if (row_nll) row_nll[m] = nll;
+        if (row_pred) row_pred[m] = idx;
+        if (row_max) row_max[m] = mx;
+        ts += nll; tc += valid ? 1.f : 0.f; th += (valid && idx == (int)lab) ? 1.f : 0.f;
+    }
+    if (totals == nullptr) return;
+    if (lane == 0) { red[wave][0] = ts; red[wave][1] = tc; red[wave][2] = th; }
+    __syncthreads();
+    if (wave != 0) return;
+    float s = red[0][0], c = red[0][1], h = red[0][2];
+#pragma unroll
+    for (int w = 1; w < WPB; ++w) { s += red[w][0]; c += red[w][1]; h += red[w][2]; }
+    score_totals_commit(s, c, h, lane, slot, totals);
+}
+
+extern "C" int xl_rowscore_combine(const float* ws, int n_seg, int M, const int64_t* labels, int n_cols, float* row_nll,
+                                   int32_t* row_pred, float* row_max, float* totals, void* stream) {
+    XL_CHECK_ARG(ws && n_seg > 0 && M > 0 && aligned16(ws) && n_cols > 0 && n_cols <= n_seg * 64, XL_ERR_BAD_ARG,
+                 "xl_rowscore_combine: bad args (n_seg=%d M=%d n_cols=%d)", n_seg, M, n_cols);
+    const int nblk = std::min((M + 63) / 64, SCORE_MAX_BLOCKS);
+    hipLaunchKernelGGL(rowscore_combine_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(ws),
+                       n_seg, M, labels, n_cols, row_nll, row_pred, row_max, totals, totals ? score_slot() : 0);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
+extern "C" int xl_score_rows(const float* logits, int M, int K, int ldl, const int64_t* labels, float* row_nll, int32_t* row_pred,
+                             float* row_max, float* totals, void* stream) {
+    XL_CHECK_ARG(logits && M > 0 && K > 0 && ldl >= K, XL_ERR_BAD_ARG, "xl_score_rows: M=%d K=%d ldl=%d", M, K, ldl);
+    const int nblk = std::min((M + WPB - 1) / WPB, SCORE_MAX_BLOCKS);
+    hipLaunchKernelGGL(score_rows_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, logits, M, K, ldl, labels, row_nll,
+                       row_pred, row_max, totals, totals ? score_slot() : 0);
+    XL_CHECK_LAUNCH();
+    return XL_OK;
+}
+
 // ---- temperature sampling (Gumbel-max; noise: common.h gumbel_noise)
 // Two candidates (s, y_s) of one row: the larger z = y_s + g(seed, m, s) wins, the lower column on a tie.  z is not stored in a
 // segment record: it is this fp32 expression, which is also what the GEMM epilogue compared.

@@ -19,7 +19,7 @@ import os
 
 import torch
 
-from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_ROWMAX, EPI_ROWSAMPLE, EPI_TANH, GemmCall
+from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_ROWMAX, EPI_ROWSAMPLE, EPI_ROWSCORE, EPI_TANH, GemmCall
 
 
 class _Res:
@@ -681,6 +681,53 @@ class LangHeads:
             ops.sample_rows(self.p_scores, M, Vn, Vp, inv_T, launch_seed, self.row_prob, self.row_id, self.row_lse)
         else:
             ops.ce_fwd_bwd(self.p_scores, None, None, None, None, self.row_lse, self.row_id, self.row_prob, M, Vn, Vp, Vp, 1.0)
+
+    # ---- validation (Engine.evaluate_task): the heads forward-only, losses and accuracies from xl_rowscore_combine / xl_score_rows
+    def fused_score_available(self, M):
+        e = self.e
+        return (e.cdtype == torch.bfloat16 and M % 256 == 0 and e.d % 8 == 0 and hasattr(e.ops, "rowscore_combine")
+                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
+
+    def _prepare_fused_score(self):
+        """the padded tied decoder of _prepare_fused_predict (30522 -> 30720 zero rows; shared with the caption sampler) and a padded
+        decoder bias of the validation pass's own: nothing is banned here, the pad columns sit at -1e30"""
+        e = self.e
+        Vq = (self.Vn + 255) // 256 * 256
+        if getattr(self, "_emb_pad", None) is None:
+            self._emb_pad = torch.zeros(Vq, e.d, dtype=e.cdtype, device=e.dev)
+            self._bias_pad = torch.full((Vq,), -1e30, dtype=torch.float32, device=e.dev)
+            self._bias_pad_T = torch.empty_like(self._bias_pad)
+            self._seg_ws = torch.zeros((Vq // 64) * e.MLc * 4, dtype=torch.float32, device=e.dev)
+        if getattr(self, "_score_bias", None) is None:
+            self._score_bias = torch.full((Vq,), -1e30, dtype=torch.float32, device=e.dev)
+        self._emb_pad[:self.Vn].copy_(e.store.cview("bert.embeddings.word_embeddings.weight"))
+        self._score_bias[:self.Vn].copy_(self.vb)
+
+    def mlm_evaluate(self, lang, totals, row_pred):
+        """MLM head on the labelled rows (set_rows) or on all rows: totals += {sum nll, labelled rows, rows predicted right}"""
+        e, d, Vn, Vp = self.e, self.e.d, self.Vn, self.Vp
+        ops, st = e.ops, e.store
+        ops.block = "head"
+        M = self.n_rows if self.n_rows else e.MLd
+        x, labels = lang, self.word_labels
+        if self.n_rows:
+            x = e.eval_buf("mlm_x", e.MLd, d)[:M]              # (not the backward scratch of mlm_fwd)
+            ops.gather_rows(lang, self.rows, x, M, d, d, d)
+            labels = self.labels_c[:M]
+            ops.gather_labels(self.word_labels, self.rows, labels, M)
+        hn = self.hn[:M]
+        ops.gemm(x, self.wt, self.h[:M], self.bt, None, self.pre[:M], M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
+        ops.layernorm_fwd(self.h[:M], self.g, self.b, hn, self.mean, self.rstd, M, d, 1e-12)
+        if self.fused_score_available(M):
+            self._prepare_fused_score()
+            Vq = self._emb_pad.shape[0]
+            ops.gemm(hn, self._emb_pad, None, self._score_bias, labels, self._seg_ws, M, Vq, d, d, d, Vq, epilogue=EPI_ROWSCORE)
+            ops.rowscore_combine(self._seg_ws, Vq // 64, M, labels, Vn, None, row_pred, None, totals)
+        else:
+            ops.gemm(hn, st.cview("bert.embeddings.word_embeddings.weight"), self.scores, self.vb, None, None,
+                     M, Vn, d, d, d, Vp, out_f32=True)
+            ops.score_rows(self.scores, M, Vn, Vp, labels, None, row_pred, None, totals)
+        return M
 
     # ---- matched
     def rel_fwd(self, pooled):
@@ -1967,6 +2014,154 @@ class Engine:
             out["qa_loss"] = self.answer.loss[0:1]
         self._qa_run = "qa_loss" in out
         return out
+
+    # ---- validation pass (ref pretrain/lxmert_pretrain.py:553-673 evaluate_epoch; tasks/vqa.py:259-311 predict / evaluate): one task
+    # per batch, forward only, model.eval() semantics.  The losses need of the logits only (max, sum exp, the label's logit) per row
+    # and the accuracy the argmax: on the bf16 path the big heads' contractions end in XL_EPI_ROWSCORE and the logits never reach
+    # memory; the small heads (and fp32 engines, rows off the 256 grid, XL_FUSED_PREDICT=0) go through xl_score_rows over fp32 logits.
+    def eval_buf(self, name, M, N, dtype=None):
+        """scratch of the validation pass: its own (the backward scratch generations -- tmp() -- are not touched)"""
+        dt = self.cdtype if dtype is None else dtype
+        key = (name, M, N, dt)
+        bufs = self.__dict__.setdefault("_eval_bufs", {})
+        if key not in bufs:
+            bufs[key] = torch.zeros(M, N, dtype=dt, device=self.dev)
+        return bufs[key]
+
+    def _eval_totals(self, key):
+        """fp32[4] of xl_rowscore_combine / xl_score_rows {sum nll, valid rows, rows predicted right, -}, zeroed for this call"""
+        t = self.eval_buf("tot_" + key, 1, 4, torch.float32).view(4)
+        self.ops.zero(t)
+        return t
+
+    @staticmethod
+    def _eval_out(out, key, tot):
+        """the mean loss (what task_forward(want_grad=False) calls `key`: sum / max(count, 1)) and the additive totals"""
+        out[key] = tot[0:1] / tot[1:2].clamp(min=1.0)
+        out[key + "_sum"], out[key + "_count"], out[key + "_correct"] = tot[0:1].clone(), tot[1:2].clone(), tot[2:3].clone()
+
+    def fused_score_available(self, M):
+        return (self.cdtype == torch.bfloat16 and M % 256 == 0 and self.F % 8 == 0 and hasattr(self.ops, "rowscore_combine")
+                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
+
+    def evaluate_task(self, task, word_labels=None, word_rows=None, matched_labels=None, qa_labels=None, targets=None, labels=None,
+                      feat_loss=True):
+        """Forward-only losses and accuracies of one task on the batch set_inputs staged: `vis_mask`, `word_mask`, `matched`, `qa`
+        (arguments as task_forward) and the fine-tune tasks `vqa` (targets [B, A] soft scores) and `nlvr2` (labels [P]).
+        Dropout is off for the call whatever the engine was built with; the step seed, store.grad, the parameters, the optimizer
+        state, the accumulation flags and the backward scratch are not touched.  Returns {name: device tensor}, no host
+        synchronisation: the reference's loss keys (obj_loss, feat_loss, lm_loss, matched_loss, qa_loss; `loss` for vqa / nlvr2) --
+        each mean is what task_forward(want_grad=False) returns for the same inputs -- and per classification loss <key>_sum,
+        <key>_count, <key>_correct (additive over batches: EvalMeter), qa_pred (ref lxrt/modeling.py:300), and for vqa / nlvr2
+        `score`, `pred` = logit.max(1).  The tensors are valid until the next evaluate_task."""
+        assert task in ("vis_mask", "word_mask", "matched", "qa", "vqa", "nlvr2"), task
+        p_saved = (self.p_hid, self.p_attn)
+        self.p_hid = self.p_attn = 0.0
+        try:
+            return self._evaluate_task(task, word_labels, word_rows, matched_labels, qa_labels, targets, labels, feat_loss)
+        finally:
+            self.p_hid, self.p_attn = p_saved
+
+    def _eval_pred(self, key, n):
+        return self.eval_buf("pred_" + key, 1, n, torch.int32).view(n)
+
+    def _evaluate_task(self, task, word_labels, word_rows, matched_labels, qa_labels, targets, labels, feat_loss):
+        ops, lh, ans = self.ops, self.lang_heads, self.answer
+        out = {}
+        if task in ("vqa", "nlvr2"):
+            assert ans is not None and not self.task_qa, "vqa / nlvr2 need a fine-tune model (ParamStore task='vqa' / 'nlvr2')"
+            B, A = ans.Bh, ans.A
+            pred, score = self._eval_pred("ans", B), self.eval_buf("score_ans", 1, B, torch.float32).view(B)
+            if task == "vqa":
+                ans.targets.copy_(targets, non_blocking=True)
+                self.vqa_forward()
+                out["loss"] = ans.loss_fwd_bwd(False)                                   # BCEWithLogitsLoss, no d(logit)
+                ops.score_rows(ans.logit, B, A, A, None, None, pred, score, None)
+                out["loss_sum"], out["loss_count"] = out["loss"] * float(B), torch.full_like(out["loss"], float(B))
+                # the reference's VQA accuracy (tasks/vqa.py:288-297 evaluate): the soft score of the predicted answer
+                out["loss_correct"] = ans.targets.gather(1, pred.long()[:, None]).sum().reshape(1)
+            else:
+                assert ans.pair, "build the store with task='nlvr2'"
+                ans.labels.copy_(labels.reshape(-1), non_blocking=True)
+                self.vqa_forward()
+                tot = self._eval_totals("ans")
+                ops.score_rows(ans.logit, B, A, A, ans.labels, None, pred, score, tot)
+                self._eval_out(out, "loss", tot)
+            out["pred"], out["score"] = pred, score
+            return out
+        if task == "vis_mask":
+            assert self.task in ("vis_mask", "all"), "the codebook head belongs to a model built for task 'vis_mask' / 'all'"
+            use_rows = self.compact_head and self.has_vmask and 0 < self.n_mrows < self.MV
+            rows = (self.mrows, self.n_mrows) if use_rows else None
+            self.encoder_forward(want_pooled=self.task_qa, ffn_rows=rows)
+            self._eval_vis_head(out, rows, feat_loss)
+        elif task == "word_mask":
+            wl = word_labels.clone()
+            wl[wl < 0] = -100
+            lh.word_labels.copy_(wl, non_blocking=True)
+            lh.set_rows(word_rows)
+            self.encoder_forward(want_pooled=self.task_qa)
+            tot = self._eval_totals("lm")
+            lh.mlm_evaluate(self.lang_final, tot, self._eval_pred("lm", self.MLd))
+            self._eval_out(out, "lm_loss", tot)
+        elif task == "matched":
+            lh.matched_labels.copy_(matched_labels, non_blocking=True)
+            self.encoder_forward(want_pooled=True)
+            lh.rel_fwd(self.pooled)
+            tot = self._eval_totals("matched")
+            ops.score_rows(lh.rel, self.B, 2, 8, lh.matched_labels, None, None, None, tot)
+            self._eval_out(out, "matched_loss", tot)
+        else:
+            assert self.task_qa, "task 'qa' needs a model built with the QA head (num_answers > 0)"
+            self.encoder_forward(want_pooled=True)
+        if self.task_qa:
+            assert qa_labels is not None, "a task_qa model adds qa_loss in every branch: label_dict['qa_labels'] is required"
+            ans.labels.copy_(qa_labels.reshape(-1), non_blocking=True)
+            ans.fwd(self.pooled)
+            tot, pred = self._eval_totals("qa"), self._eval_pred("qa", ans.Bh)
+            ops.score_rows(ans.logit, ans.Bh, ans.A, ans.A, ans.labels, None, pred, None, tot)
+            self._eval_out(out, "qa_loss", tot)
+            out["qa_pred"] = pred
+        else:
+            assert qa_labels is None, "qa_labels given but the model has no QA head (build the store with num_answers > 0)"
+        return out
+
+    def _eval_vis_head(self, out, rows, feat_loss):
+        """LxmertVisualObjHead (ref lxrt/modeling.py:38-53) and both of its losses on the masked rows only (exact: the losses read
+        nothing else; pad entries of the row list are zero rows with label -100) or, without a row list, on all rows"""
+        ops, d, F, K, hd = self.ops, self.d, self.F, self.K, self.hd
+        ops.block = "head"
+        M = rows[1] if rows is not None else self.MV
+        vis, labels = self.vis_final, self.labels
+        if rows is not None:
+            if self._ffn_rows_run is not None:                 # the last visual feed-forward block ran on these rows only
+                assert self._ffn_rows_run[1] == M
+                vis = _h(self._vis_c)[:M]
+            else:
+                vis = self.eval_buf("vis_c", self.MV, d)[:M]
+                ops.gather_rows(self.vis_final, rows[0], vis, M, d, d, d)
+            labels = self.labels_c[:M]
+            ops.gather_labels(self.labels, rows[0], labels, M)
+        ops.gemm(vis, hd["wt"][0], self.t_h, hd["bt"][0], None, self.t_pre, M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
+        ops.layernorm_fwd(self.t_h, hd["gt"][0], hd["bbt"][0], self.t_y, self.t_mean, self.t_rstd, M, d, self.eps)
+        ops.gemm(self.t_y, hd["wf"][0], self.feat, hd["bf"][0], None, None, M, F, d, d, d, F)
+        tot, pred = self._eval_totals("obj"), self._eval_pred("obj", self.MV)[:M]        # (pred: the head's rows, in row-list order)
+        if self.fused_score_available(M):
+            self._prepare_fused_predict()
+            Kq = self._cent_pad.shape[0]
+            ops.gemm(self.feat, self._cent_pad, None, self._bias_pad, labels, self._rowmax_ws, M, Kq, F, F, F, Kq, epilogue=EPI_ROWSCORE)
+            ops.rowscore_combine(self._rowmax_ws, Kq // 64, M, labels, K, None, pred, None, tot)
+        else:
+            ops.gemm(self.feat, self.store.centroids_c, self.logits, hd["bc"][0], None, None, M, K, F, F, F, K, out_f32=True)
+            ops.score_rows(self.logits, M, K, K, labels, None, pred, None, tot)
+        self._eval_out(out, "obj_loss", tot)
+        if feat_loss:
+            ops.zero(self.losses[1:2])
+            ops.mask_counts(self.labels, self.vmask, self.counts, self.nmask, self.B, self.V)
+            ops.featloss_fwd_bwd(self.feat, self.store.centroids_c, self.cid, self.vmask, self.nmask, None, self.losses[1:], self.B,
+                                 self.V, F, 1.0, rows=rows[0] if rows is not None else None, n_rows=M if rows is not None else 0,
+                                 targets=self.feat_tgt)
+            out["feat_loss"] = self.losses[1:2]
 
     def task_backward(self):
         """backward of the branch task_forward ran last; ACCUMULATES into store.grad."""

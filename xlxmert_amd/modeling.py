@@ -395,6 +395,52 @@ class XLxmertForPretraining(nn.Module):
         return out_dict
 
     @torch.no_grad()
+    def evaluate(self, input_ids=None, visual_feats=None, visual_pos=None, attention_mask=None,
+                 visual_attention_mask=None, cluster_ids=None, vis_mask=None, token_type_ids=None, inputs_embeds=None,
+                 output_attentions=None, output_hidden_states=None, return_dict=None, label_dict=None,
+                 task="vis_mask", **kwargs):
+        """One batch of the reference's validation pass (ref lxmert_pretrain.py:553-673 evaluate_epoch: model.eval(), no_grad, one
+        task per batch): forward's arguments, Engine.evaluate_task's dict -- the task's loss keys, <key>_sum / _count / _correct
+        (additive: trainer.EvalMeter) and qa_pred -- as device tensors without a host synchronisation.  eval() semantics for the
+        call (no dropout); the training flag is restored afterwards, as the samplers do."""
+        if task not in ("vis_mask", "word_mask", "matched", "qa"):
+            raise ValueError(f"task must be one of 'word_mask', 'vis_mask', 'matched', 'qa' (got {task!r})")
+        if self.vis_emb is None:
+            raise RuntimeError("call set_visual_embedding(centroids) first (ref lxrt/modeling.py:185-186)")
+        if inputs_embeds is not None or visual_attention_mask is not None or output_attentions or output_hidden_states:
+            raise NotImplementedError("inputs_embeds / visual_attention_mask / attention maps / hidden states: None in every "
+                                      "reference caller of this model (ref lxmert_pretrain.py:201-223)")
+        label_dict = label_dict or {}
+        was_training = self.training
+        self.eval()
+        try:
+            B, L = input_ids.shape
+            eng = self._step_engine(B, L, cluster_ids.shape[1])
+            kw = {}
+            if task == "vis_mask":
+                feat_labels = label_dict.get("feat_labels")
+                eng.set_inputs(input_ids, attention_mask, token_type_ids, visual_pos, cluster_ids=cluster_ids, vis_mask=vis_mask,
+                               obj_labels=label_dict["obj_labels"], feat_labels=feat_labels)
+                kw["feat_loss"] = feat_labels is not None
+            else:
+                if task == "word_mask":
+                    if not self.task_mask_lm:
+                        raise RuntimeError("task 'word_mask' on a model built without task_mask_lm (no `cls` head)")
+                    kw["word_labels"] = label_dict["word_labels"]
+                elif task == "matched":
+                    if not self.task_matched:
+                        raise RuntimeError("task 'matched' on a model built without task_matched (no `cls` head)")
+                    kw["matched_labels"] = label_dict["matched_labels"]
+                eng.set_inputs(input_ids, attention_mask, token_type_ids, visual_pos, cluster_ids=cluster_ids)
+            if self.task_qa:
+                kw["qa_labels"] = label_dict["qa_labels"]
+            elif task == "qa":
+                return {}                                                           # the reference adds nothing either
+            return {k: v.clone() for k, v in eng.evaluate_task(task, **kw).items()}
+        finally:
+            self.train(was_training)
+
+    @torch.no_grad()
     def sample_codes(self, input_ids, n_steps=4, grid_size=8, *, temperature=None, seed=None, top_k=None, top_p=None, min_p=None):
         """The device part of ImggenModel.sample_image_NAR (ref tasks/imggen_model.py:169-254): Mask-Predict sampling of
         the grid codes, returned as the generator's input `[B, feat_dim, grid, grid]` (fp32) plus the chosen code ids.
@@ -680,6 +726,42 @@ class VQAModel(nn.Module):
                        visual_attention_mask=visual_attention_mask, inputs_embeds=inputs_embeds)
         logit = _VqaFn.apply(self, self._anchor) if torch.is_grad_enabled() else eng.vqa_forward().clone()
         return {"logit": logit}
+
+
+    @torch.no_grad()
+    def predict(self, input_ids=None, visual_feats=None, visual_pos=None, attention_mask=None, visual_attention_mask=None,
+                token_type_ids=None, inputs_embeds=None):
+        """The fine-tune drivers' predict / evaluate step (ref tasks/vqa.py:259-311, tasks/gqa.py, tasks/nlvr2.py): forward's
+        arguments (NLVR2: the [P, 2, V, F] pairs), eval() semantics, returns (score, pred) = logit.max(1) as device tensors -- the
+        answer head's logits go through xl_score_rows, no host synchronisation.  The training flag is restored afterwards."""
+        if visual_feats.dim() == 4:                     # NLVR2 pairs (ref tasks/nlvr2_model.py:64-66)
+            visual_feats, visual_pos = visual_feats.reshape(-1, *visual_feats.shape[2:]), visual_pos.reshape(-1, *visual_pos.shape[2:])
+        was_training = self.training
+        self.eval()
+        try:
+            B, L = input_ids.shape if input_ids is not None else inputs_embeds.shape[:-1]
+            key = (B, L, visual_feats.shape[1], self.training, self._task)
+            if self.bert._geom != key:
+                self.bert._engine = Engine(self.config, self._store, self.bert._ops, B, L, visual_feats.shape[1], need_lang=True,
+                                           train_dropout=False, residual_dtype=self.bert._residual_dtype)
+                self.bert._geom = key
+            eng = self.bert._engine
+            eng.sync_compute_weights()
+            eng.set_inputs(input_ids, attention_mask, token_type_ids, visual_pos, visual_feats=visual_feats,
+                           visual_attention_mask=visual_attention_mask, inputs_embeds=inputs_embeds)
+            ans = eng.answer
+            p_saved = (eng.p_hid, eng.p_attn)
+            eng.p_hid = eng.p_attn = 0.0
+            try:
+                eng.vqa_forward()
+            finally:
+                eng.p_hid, eng.p_attn = p_saved
+            pred = torch.zeros(ans.Bh, dtype=torch.int32, device=ans.logit.device)
+            score = torch.zeros(ans.Bh, dtype=torch.float32, device=ans.logit.device)
+            self.bert._ops.score_rows(ans.logit, ans.Bh, ans.A, ans.A, None, None, pred, score, None)
+            return score, pred.long()
+        finally:
+            self.train(was_training)
 
 
 class GQAModel(VQAModel):

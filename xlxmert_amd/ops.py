@@ -15,6 +15,7 @@ XL_F32, XL_BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_TANH, EPI_ROWMAX, EPI_GELU_DG, EPI_MULAUX = 0, 1, 2, 3, 4, 5, 6, 7
 EPI_RESIDUAL_F32 = 8            # XL_EPI_RESIDUAL with an fp32 residual and output (the fp32 residual stream); chosen by HipOps.gemm
 EPI_ROWSAMPLE = 9               # XL_EPI_ROWMAX's sibling for temperature sampling: alpha = 1/T, bias / T, seed = the launch's noise seed
+EPI_ROWSCORE = 10               # XL_EPI_ROWMAX's sibling for validation losses: residual = int64 labels [M], the record's fourth slot = x_label
 
 TORCH_DTYPE = {XL_F32: torch.float32, XL_BF16: torch.bfloat16}
 _SLAB_WS = {}
@@ -445,6 +446,17 @@ class HipOps:
         the log-sum-exp of the tempered logits."""
         self._call("xl_rowsample_combine", self._p(ws), n_seg, M, int(seed), self._p(row_prob), self._p(row_id), self._p(row_lse),
                    self._stream())
+
+    def rowscore_combine(self, ws, n_seg, M, labels, n_cols, row_nll=None, row_pred=None, row_max=None, totals=None):
+        """second half of gemm(epilogue=EPI_ROWSCORE, residual=labels, aux=ws): per row the label's negative log-likelihood (0 for a
+        label outside [0, n_cols)), the argmax and the maximum; totals[0:3] += {sum nll, valid rows, valid rows predicted right}."""
+        self._call("xl_rowscore_combine", self._p(ws), n_seg, M, self._p(labels), int(n_cols), self._p(row_nll), self._p(row_pred),
+                   self._p(row_max), self._p(totals), self._stream())
+
+    def score_rows(self, logits, M, K, ldl, labels, row_nll=None, row_pred=None, row_max=None, totals=None):
+        """the same outputs from fp32 logits in memory (xl_score_rows): one wave per row, columns < K only; labels may be None."""
+        self._call("xl_score_rows", self._p(logits), M, K, ldl, self._p(labels), self._p(row_nll), self._p(row_pred),
+                   self._p(row_max), self._p(totals), self._stream())
 
     def sample_rows(self, logits, M, K, ldl, inv_T, seed, row_prob, row_id, row_lse=None):
         """the same draw over fp32 logits in memory (xl_sample_rows): y = logits * inv_T, one wave per row."""

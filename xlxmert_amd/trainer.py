@@ -602,6 +602,49 @@ class PretrainStep:
             self._mark_consumed(batch)
         return losses
 
+    def evaluate(self, batch, task=None):
+        """One batch of a validation pass (ref lxmert_pretrain.py:553-673 evaluate_epoch; tasks/vqa.py:259-311 evaluate): the batch
+        dict of step(), forward only, no dropout.  Nothing of the training state moves: no gradient, no exchange, no optimizer
+        pass; t, micro (the dropout seeds of the steps to come), a pending accumulation window and every recorded launch plan stay
+        as they are -- step, evaluate, step leaves the parameters step, step leaves.  Returns Engine.evaluate_task's dict of
+        device tensors (feed it to an EvalMeter; no host synchronisation here).  The totals are this rank's: they are additive, a
+        data-parallel caller all-reduces EvalMeter.totals."""
+        eng = self.engine
+        if batch.get("_ready") is not None:
+            torch.cuda.current_stream().wait_event(batch["_ready"])
+        run = self.task if self.task != "all" else task
+        assert run in ("vis_mask", "word_mask", "matched", "qa", "vqa", "nlvr2"), "PretrainStep(task='all').evaluate(batch, task=...)"
+        ids = batch["input_ids"]
+        am = batch.get("attention_mask")
+        if am is None:
+            am = ids > 0
+        common = dict(lang_rows=batch.get("lang_rows"), lang_off=batch.get("lang_off"), word_order=batch.get("word_order"))
+        kw = {"qa_labels": batch.get("qa_labels")} if eng.task_qa else {}
+        if run in ("vqa", "nlvr2"):
+            feats, pos = batch["visual_feats"], batch["visual_pos"]
+            if run == "nlvr2":
+                feats, pos = feats.reshape(-1, *feats.shape[2:]), pos.reshape(-1, *pos.shape[2:])
+            eng.set_inputs(ids, am, batch.get("token_type_ids"), pos, visual_feats=feats, **common)
+            kw = {"targets": batch["targets"]} if run == "vqa" else {"labels": batch["labels"]}
+        elif run == "vis_mask":
+            labels = batch.get("obj_labels")
+            if labels is None:
+                labels = batch["cluster_ids"].clone()
+                labels[~batch["vis_mask"].bool()] = -100           # ref lxmert_pretrain.py:163-166
+            eng.set_inputs(ids, am, batch.get("token_type_ids"), batch["visual_pos"], cluster_ids=batch["cluster_ids"],
+                           vis_mask=batch["vis_mask"], obj_labels=labels, masked_rows=batch.get("masked_rows"),
+                           feat_labels=batch.get("feat_labels") if self.feat_loss else None, **common)
+            kw["feat_loss"] = self.feat_loss
+        else:
+            eng.set_inputs(ids, am, batch.get("token_type_ids"), batch["visual_pos"], cluster_ids=batch["cluster_ids"], **common)
+            if run == "word_mask":
+                kw.update(word_labels=batch["word_labels"], word_rows=batch.get("word_rows"))
+            elif run == "matched":
+                kw["matched_labels"] = batch["matched_labels"]
+        out = eng.evaluate_task(run, **kw)
+        self._mark_consumed(batch)              # (the label tensors are copied inside evaluate_task)
+        return out
+
     def _next_seed(self):
         """step part of the dropout seeds of the forward about to run: one value per (forward pass, rank)"""
         s = self.micro * self.world + self.rank
@@ -851,6 +894,43 @@ class PretrainStep:
 
     def grad_norm(self):
         return math.sqrt(float(self.sumsq.item())) / self.world
+
+
+class EvalMeter:
+    """Running totals of a validation pass, kept on the DEVICE: add() every PretrainStep.evaluate / Engine.evaluate_task result,
+    result() once at the end -- the reference's epoch_results (lxmert_pretrain.py:621-673) without an .item() per step.  Per loss key
+    it adds <key>_sum, <key>_count and <key>_correct; keys without totals (feat_loss: a per-batch mean) are averaged over the calls.
+    `totals` ({key: fp32[3] = sum, count, correct}) is additive across ranks: all-reduce it before result()."""
+
+    def __init__(self):
+        self.totals, self.means = {}, {}
+
+    def add(self, out):
+        for k, v in out.items():
+            if k.endswith("_sum") and k[:-4] + "_count" in out:
+                key = k[:-4]
+                t = torch.cat([out[key + "_sum"].reshape(1), out[key + "_count"].reshape(1), out[key + "_correct"].reshape(1)]).float()
+                if key in self.totals:
+                    self.totals[key] += t
+                else:
+                    self.totals[key] = t.clone()
+        for k, v in out.items():
+            if k.endswith("_loss") and k + "_sum" not in out:
+                m = self.means.setdefault(k, [torch.zeros(1, dtype=torch.float32, device=v.device), 0])
+                m[0] += v.reshape(1).float()
+                m[1] += 1
+
+    def result(self):
+        """{key: mean loss, key[:-5] + '_accuracy' (or 'accuracy' for `loss`): correct / count}: the only host read of the pass"""
+        res = {}
+        for key, t in self.totals.items():
+            s, c, h = (float(x) for x in t.tolist())
+            res[key] = s / max(c, 1.0)
+            res[(key[:-5] + "_accuracy") if key.endswith("_loss") else "accuracy"] = h / max(c, 1.0)
+            res[key + "_count"] = c
+        for key, (s, n) in self.means.items():
+            res[key] = float(s.item()) / max(n, 1)
+        return res
 
 
 class PackedBatch(dict):
