@@ -394,7 +394,10 @@ int xl_attn_probs(const void* q, const void* k, const uint8_t* key_mask, const f
                   const int* q_rowoff, const int* k_rowoff, int dtype, void* stream);
 /* bias_grad (optional, fp32 [3*H*dh]): bias_grad[q | k | v] += column sums of dq / dk / dv over all B*n rows - the bias
  * gradients of the query/key/value projections (HF:232-239 nn.Linear) - from per-token scalars inside the kernel, without
- * re-reading dq/dk/dv; `workspace` as for xl_colsum (the second stage obeys xl_set_deferred_reduce). */
+ * re-reading dq/dk/dv; `workspace` as for xl_colsum (the second stage obeys xl_set_deferred_reduce).  Where the kernel has no
+ * fused partials (no workspace, more than xl_workspace_floats(H*dh) / (3*H*dh) examples, the generic and the long kernels) the
+ * sums are three xl_colsum calls over the stored gradients: H*dh, lddq, lddk and lddv must then be multiples of 8 (fp32: 4), or
+ * the call is refused with XL_ERR_BAD_SHAPE before anything is launched. */
 
 /* ---------------------------------------------------------------- head losses (ref lxrt/modeling.py:237-290)
  * counts[0] = #labels != -100 ; nmask[b] = sum_v vis_mask[b,v]            (device-side, no host sync) */

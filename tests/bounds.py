@@ -160,7 +160,7 @@ def blocked_rescale_error(n_blk, rng):
     return (n_blk - 1) * (EXP_ULP + 1) * U32 + 2 * U32 * rng
 
 
-def sdpa_fwd_bounds(Q, K, V, valid, keep, scale, O_ref, lse_ref, n_kblk=1):
+def sdpa_fwd_bounds(Q, K, V, valid, keep, scale, O_ref, lse_ref, n_kblk=1, out_dtype=torch.bfloat16, arith="mfma"):
     """xl_sdpa_fwd (sdpa_fwd_mfma).  P' = softmax(s) keep is rounded to bf16 before the PV MFMA (design: U16 |P'||V|).  A score
     error e_S moves every p_j by at most p_j (|ds_j| + sum_k p_k |ds_k|) <= 2 e_S p_j; exp (v_exp_f32, 2 ulp), 1/sum (1 ulp) and
     the nk-deep fp32 sum add (nk + 4) U32 relative to the row.  So
@@ -177,11 +177,21 @@ def sdpa_fwd_bounds(Q, K, V, valid, keep, scale, O_ref, lse_ref, n_kblk=1):
       * O^T += V^T P^T is an fp32 MFMA chain over all nk keys carried across the blocks, and the division by the sum is one
         multiply of the accumulator at the end:  (nk + 1) U32 |P'||V|;
       * lse = m + __logf(sum) with the sum accumulated (and rescaled) across the blocks:  + r.
-    With n_kblk = 1 none of these terms exists and the result is the on-chip bound, bit for bit."""
+    With n_kblk = 1 none of these terms exists and the result is the on-chip bound, bit for bit.
+
+    out_dtype, arith: the storage type of O and the arithmetic of the kernel.  The defaults (bf16, "mfma") are the bound above, bit
+    for bit.  arith = "fp32" is sdpa_fwd_generic<T> (one lane per query, T = bf16 or fp32): a score is a serial dh-deep fmaf chain
+    (one rounding per step: the dh U32 |q||k| of e_S, also for fp32 operands, whose products an fma does not round), expf (2 ulp
+    like v_exp_f32 or better), a serial nk-deep sum and ONE division -- the (nk + 4) U32 of the row; P is NOT rounded to bf16: the
+    designed U16 |P'||V| is replaced by the serial nk-deep fmaf chain of O = P' V, nk U32 |P'||V| (the multiply by 1 / sum and by
+    the keep scale are inside the + 4); the store rounds once to the output format, u_out |O| (fp32: 2^-24).  lse has no bf16
+    term: unchanged (logf instead of __logf is the more accurate one)."""
     nk = K.shape[-2]
+    assert arith in ("mfma", "fp32"), arith
+    u_out, u_p = unit(out_dtype), (U16 if arith == "mfma" else nk * U32)
     s, P, Pk, eS = attention_parts(Q, K, V, valid, keep, scale)
     pv = Pk.abs() @ V.abs()
-    bO = U16 * O_ref.abs() + SLACK * (U16 + 2 * eS + (nk + 4) * U32) * pv + TINY
+    bO = u_out * O_ref.abs() + SLACK * (u_p + 2 * eS + (nk + 4) * U32) * pv + TINY
     lse_f = lse_ref.nan_to_num(0.0, neginf=0.0)
     bl = SLACK * (eS[..., 0] + (nk + 4) * U32 + 2 * U32 * lse_f.abs() + 2.0 ** -21)
     if n_kblk > 1:
@@ -192,7 +202,8 @@ def sdpa_fwd_bounds(Q, K, V, valid, keep, scale, O_ref, lse_ref, n_kblk=1):
     return bO, bl
 
 
-def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref, n_kblk=1, n_qblk=1):
+def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref, n_kblk=1, n_qblk=1, out_dtype=torch.bfloat16,
+                    arith="mfma"):
     """xl_sdpa_bwd (sdpa_bwd_mfma).  P = exp(s - lse) from the saved lse (the reference uses the same lse): e_P = e_S + 2 U32 +
     U32 |s - lse| relative.  dP = dO V^T (dh-deep: dh U32 |dO||V|^T), times keep.  delta = sum_k P dP': nk-deep.
     dS = P (dP' - delta) scale, |err| <= scale (e_P P |dP' - delta| + P (|ddP| + |ddelta|)) + 3 U32 |dS|, then rounded to bf16
@@ -215,9 +226,18 @@ def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref
         in fp32 across the blocks, depth nk resp. nq -- the terms above already have these depths (rows of a partial block
         beyond the length are exact zeros); n_qblk adds nothing and is accepted so that a caller states the geometry;
       * dS and P~ are rounded to bf16 per block exactly as on chip: U16 |dS|, U16 |P'|.
-    With both counts 1 the result is the on-chip bound, bit for bit."""
+    With both counts 1 the result is the on-chip bound, bit for bit.
+
+    out_dtype, arith: as in sdpa_fwd_bounds; the defaults give the bound above, bit for bit.  arith = "fp32" is sdpa_bwd_generic<T>:
+    s and dP are serial dh-deep fmaf chains (dh U32, as above), P = expf(s scale - lse) (e_P as above), delta a serial nk-deep sum
+    (K_eff = nk), dS = P (dP' - delta) scale in fp32 (the 3 U32 |dS|) and NOT rounded to bf16, P' = P keep likewise: both designed
+    U16 terms drop out.  dQ is a serial nk-deep fmaf chain (nk U32 |dS||K|); dK and dV are sums of nq products each, gathered by
+    atomic adds in LDS in whatever order the lanes arrive -- any order is inside nq U32 |dS|^T|Q| resp. (nq + 2) U32 |P'|^T|dO|,
+    a product rounds once before it is added (inside the + 2 and SLACK).  The store rounds once: u_out |ref|."""
     nq, nk, dh = Q.shape[-2], K.shape[-2], Q.shape[-1]
     assert n_kblk >= 1 and n_qblk >= 1
+    assert arith in ("mfma", "fp32"), arith
+    u_out, u_mid = unit(out_dtype), (U16 if arith == "mfma" else 0.0)
     if n_kblk > 1 or n_qblk > 1:
         assert n_kblk == (nk + 63) // 64 and n_qblk == (nq + 63) // 64, (n_kblk, nk, n_qblk, nq)
     k_delta = nk if n_kblk == 1 else nk + n_kblk + 1
@@ -230,12 +250,12 @@ def sdpa_bwd_bounds(Q, K, V, dO, valid, keep, scale, lse, dQ_ref, dK_ref, dV_ref
     delta = (P * dP).sum(-1, keepdim=True)
     edelta = (eP * P * dP.abs() + P * edP).sum(-1, keepdim=True) + k_delta * U32 * (P * dP.abs()).sum(-1, keepdim=True)
     dS = P * (dP - delta) * scale
-    edS = abs(scale) * (eP * P * (dP - delta).abs() + P * (edP + edelta)) + 3 * U32 * dS.abs() + U16 * dS.abs()
+    edS = abs(scale) * (eP * P * (dP - delta).abs() + P * (edP + edelta)) + 3 * U32 * dS.abs() + u_mid * dS.abs()
     Pk = (P * keep).abs()
-    tV = (U16 + eP.amax(-2, keepdim=True).transpose(-1, -2) + (nq + 2) * U32) * (Pk.transpose(-1, -2) @ dO.abs())
+    tV = (u_mid + eP.amax(-2, keepdim=True).transpose(-1, -2) + (nq + 2) * U32) * (Pk.transpose(-1, -2) @ dO.abs())
     tQ = edS @ K.abs() + nk * U32 * (dS.abs() @ K.abs())
     tK = edS.transpose(-1, -2) @ Q.abs() + nq * U32 * (dS.abs().transpose(-1, -2) @ Q.abs())
-    return ((U16 * dQ_ref.abs() + SLACK * tQ + TINY, U16 * dK_ref.abs() + SLACK * tK + TINY, U16 * dV_ref.abs() + SLACK * tV + TINY),
+    return ((u_out * dQ_ref.abs() + SLACK * tQ + TINY, u_out * dK_ref.abs() + SLACK * tK + TINY, u_out * dV_ref.abs() + SLACK * tV + TINY),
             (tQ, tK, tV))
 
 

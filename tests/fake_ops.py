@@ -387,7 +387,10 @@ class FakeOps:
             s = s.masked_fill(key_mask.view(B, 1, 1, nk) == 0, float("-inf"))
         if kv is not None:
             s = s.masked_fill(~kv.view(B, 1, 1, nk), float("-inf"))
-        lse.view(B, H, nq).copy_(torch.logsumexp(s, -1))
+        l = torch.logsumexp(s, -1)
+        if qv is not None:                                   # queries beyond an example's length do not exist: their lse is not written
+            l = torch.where(qv.view(B, 1, nq), l.to(lse.dtype), lse.view(B, H, nq))
+        lse.view(B, H, nq).copy_(l)
         out = (torch.softmax(s, -1) * self._pmask(B, H, nq, nk, p_drop, self._seed(seed), s.device)) @ V_
         self._store(o, out, B, nq, H, dh, ldo, q_off, q_pad)
 

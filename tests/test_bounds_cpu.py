@@ -881,9 +881,15 @@ def test_attention_bounds_without_block_counts_are_the_on_chip_bounds_bit_for_bi
     pv = Pk.abs() @ V.abs()
     want_O = U16 * O_.abs() + SL * (U16 + 2 * eS + (n + 4) * U32) * pv + TINY
     want_l = SL * (eS[..., 0] + (n + 4) * U32 + 2 * U32 * L.abs() + 2.0 ** -21)
-    for kw in ({}, {"n_kblk": 1}):
+    dflt = {"out_dtype": torch.bfloat16, "arith": "mfma"}            # the defaults of the output-type / arithmetic arguments
+    for kw in ({}, {"n_kblk": 1}, dflt):
         bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, 0.125, O_, L, **kw)
         assert torch.equal(bO, want_O) and torch.equal(bl, want_l)
+    # the fp32 arithmetic of the generic kernels: no designed bf16 term -- strictly tighter for a bf16 store, 2^-16 of it for an fp32 one
+    g16, gl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, 0.125, O_, L, arith="fp32")
+    g32, _ = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, 0.125, O_, L, out_dtype=torch.float32, arith="fp32")
+    assert torch.equal(gl, want_l) and bool((g16 <= want_O).all()) and bool((g32 <= g16).all())
+    assert torch.equal(g32, U32 * O_.abs() + SL * (n * U32 + 2 * eS + (n + 4) * U32) * pv + TINY)
     # attn_probs
     ref = torch.exp(s - L[..., None]).masked_fill(~valid.expand_as(s), 0.0) * keep
     arg = (s - L[..., None]).abs().masked_fill(~valid.expand_as(s), 0.0).nan_to_num(0.0, posinf=0.0)
@@ -912,10 +918,13 @@ def test_attention_bounds_without_block_counts_are_the_on_chip_bounds_bit_for_bi
     tQ = edS @ K.abs() + n * U32 * (dS.abs() @ K.abs())
     tK = edS.transpose(-1, -2) @ Q.abs() + n * U32 * (dS.abs().transpose(-1, -2) @ Q.abs())
     want = [U16 * g.abs() + SL * t + TINY for g, t in zip(dense, (tQ, tK, tV))]
-    for kw in ({}, {"n_kblk": 1, "n_qblk": 1}):
+    for kw in ({}, {"n_kblk": 1, "n_qblk": 1}, dflt):
         bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, 0.125, L, *dense, **kw)
         assert all(torch.equal(b, w) for b, w in zip(bounds, want))
         assert all(torch.equal(t, w) for t, w in zip(terms, (tQ, tK, tV)))
+    b32, t32 = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, 0.125, L, *dense, out_dtype=torch.float32, arith="fp32")
+    assert all(bool((t <= w).all()) for t, w in zip(t32, (tQ, tK, tV)))
+    assert all(torch.equal(b, U32 * g.abs() + SL * t + TINY) for b, g, t in zip(b32, dense, t32))
 
 
 # ------------------------------------------------------------------------------------------------------------------ GEMM dispatch edges
@@ -1323,3 +1332,67 @@ class RejectingRowOps(HonestRowOps):
 def test_rowop_rejected_calls_raise_and_write_nothing_over_the_restated_argument_checks(dt):
     import test_rowop_edges_bounds_gpu as R
     R.run_rejected(R.DTYPES[dt], ops=RejectingRowOps(R.DTYPES[dt]), dev="cpu", error=Refused)
+
+
+# ------------------------------------------------------------------------------------------------------------------ on-chip attention edges
+# tests/test_sdpa_edges_bounds_gpu.py over the host restatement of the attention entry points as a kernel stand-in
+# (tests/fake_ops_sdpa.SdpaOps): the same calls (tests/sdpa_edge_cases.py), the same recorder, the same label, count, keep_bits and
+# outside-view assertions.
+BF16, FP32 = torch.bfloat16, torch.float32
+SDPA_EDGE_RUNS = {
+    **{f"fragments-dh{dh}-{'tr' if tr else 'plain'}": ("run_fragments", (dh, tr), BF16) for dh in (16, 32, 64) for tr in (1, 0)},
+    "eligibility-bf16": ("run_eligibility", (BF16,), BF16), "eligibility-fp32": ("run_eligibility", (FP32,), FP32),
+    "packed-mfma": ("run_packed", (BF16, "mfma"), BF16), "packed-generic": ("run_packed", (BF16, "generic"), BF16),
+    "packed-fp32": ("run_packed", (FP32, "mfma"), FP32),
+    "bias_gradients": ("run_bias_gradients", (), BF16), "dropout": ("run_dropout", (), BF16), "extremes": ("run_extremes", (), BF16),
+    "attn_probs-bf16": ("run_attn_probs", (BF16,), BF16), "attn_probs-fp32": ("run_attn_probs", (FP32,), FP32)}
+
+
+@pytest.mark.parametrize("run", list(SDPA_EDGE_RUNS))
+def test_sdpa_edge_cases_pass_over_the_host_restatement(run):
+    """an honest implementation (fp32 arithmetic on bf16 / fp32 storage; keep_bits in the documented layout; lse of missing queries,
+    rows beyond the capacity and everything outside the logical views left alone) is inside every bound at the inputs of the edge
+    cases -- the scores of +-60 included -- and every sweep reaches the kernel labels the GPU tests expect"""
+    import test_sdpa_edges_bounds_gpu as S
+    from fake_ops_sdpa import SdpaOps
+    fn, args, dt = SDPA_EDGE_RUNS[run]
+    getattr(S, fn)(*args, ops=SdpaOps(dt), dev="cpu")
+
+
+SHAPES_33 = dict(shapes=((32, 32), (33, 33), (31, 64), (64, 1)))
+SDPA_FAULT_RUNS = {
+    "key32_dropped": ("run_fragments", (32, 1), BF16, SHAPES_33), "mask_by_length": ("run_packed", (BF16, "mfma"), BF16, {}),
+    "mask_255_off": ("run_fragments", (16, 1), BF16, dict(shapes=((32, 32), (33, 33), (31, 64)))), "pad_not_zeroed": ("run_packed", (BF16, "mfma"), BF16, {}),
+    "pad_one_row_too_far": ("run_packed", (BF16, "generic"), BF16, {}), "store_next_head": ("run_fragments", (64, 0), BF16, SHAPES_33),
+    "lse_missing_query": ("run_packed", (BF16, "mfma"), BF16, {}), "dropout_row_by_length": ("run_packed", (BF16, "mfma"), BF16, {}),
+    "step_seed_ignored_bwd": ("run_dropout", (), BF16, {}), "keep_bit_halves_swapped": ("run_dropout", (), BF16, {}),
+    "bias_overwritten": ("run_bias_gradients", (), BF16, {}), "bias_stale_pad_row": ("run_bias_gradients", (), BF16, {}),
+    "dv_without_dropout_scale": ("run_fragments", (64, 1), BF16, SHAPES_33),
+    "delta_second_fragment_lost": ("run_fragments", (32, 0), BF16, SHAPES_33),
+    "generic_tail_features_dropped": ("run_eligibility", (BF16,), BF16, {}), "fp32_through_bf16": ("run_eligibility", (FP32,), FP32, {}),
+    "round_toward_zero": ("run_eligibility", (BF16,), BF16, {})}
+
+
+@pytest.mark.parametrize("fault", list(SDPA_FAULT_RUNS))
+def test_sdpa_edge_cases_reject_plausible_kernel_faults(fault):
+    """the same recorder run as the honest pass, over an implementation with one fault: it must fail at EVERY call the fault
+    changed (each such call shows the fault on its own), and only there"""
+    import test_sdpa_edges_bounds_gpu as S
+    from fake_ops_sdpa import FAULTS, SdpaOps
+    assert set(SDPA_FAULT_RUNS) == set(FAULTS)
+    fn, args, dt, subset = SDPA_FAULT_RUNS[fault]
+    ops = SdpaOps(dt, fault=fault)
+    rec, n = getattr(S, fn)(*args, ops=ops, dev="cpu", **subset)
+    assert len(rec.checked) + len(rec.failures) == n and ops.applied > 0, (len(rec.checked), len(rec.failures), n, ops.applied)
+    print(f"{fault}: applied at {ops.applied} of {n} calls, {len(rec.failures)} failed")
+    assert len(rec.failures) == ops.applied, (fault, ops.applied, len(rec.failures), rec.failures[:3])
+    import re
+    word = "outside" if fault in ("pad_one_row_too_far", "store_next_head", "lse_missing_query") else "beyond their bound|differ|outside"
+    assert all(re.search(word, f) for f in rec.failures), rec.failures[:3]
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp32"])
+def test_sdpa_rejected_calls_raise_and_write_nothing_over_the_restated_argument_checks(dt):
+    import test_sdpa_edges_bounds_gpu as S
+    from fake_ops_sdpa import Refused, SdpaOps
+    S.run_rejected(S.DTYPES[dt], ops=SdpaOps(S.DTYPES[dt], checks=True), dev="cpu", error=Refused)

@@ -437,6 +437,64 @@ def _o_featloss(a):
     return [_t(a["dpred"], n, a["F"]), _t(a["loss_out"], 1)]
 
 
+def _at(t, k):
+    """a one-element view of t's storage k elements behind its base: the anchor of a logical view that starts there"""
+    return torch.as_strided(t, (1,), (1,), t.storage_offset() + k)
+
+
+def _held(*ts):
+    """tensors a call only reads: an empty view each, so that their whole storage is held to its earlier bits"""
+    return [(t, (0,), (1,)) for t in ts if t is not None]
+
+
+def _o_rows(t, B, n, HD, ld, off, pad):
+    """what an attention call writes of a q- or k-side buffer: all H heads of the [len_b, dh] row blocks (dense: B n rows; packed:
+    min(n, off[b+1] - off[b]) rows from row off[b] -- rows of an example beyond the capacity stay), and the pad rows [off[B], pad)"""
+    if t is None:
+        return []
+    if off is None:
+        return [(t, (B * n, HD), (ld, 1))]
+    o = [int(x) for x in off.reshape(-1)[:B + 1]]
+    v = [(_at(t, o[b] * ld), (min(n, o[b + 1] - o[b]), HD), (ld, 1)) for b in range(B) if o[b + 1] > o[b]]
+    if pad > o[B]:
+        v.append((_at(t, o[B] * ld), (pad - o[B], HD), (ld, 1)))
+    return v
+
+
+def _o_lse(lse, B, H, nq, off):
+    """the lse entries of the queries that exist ([B, H, nq capacity] indexing)"""
+    if off is None:
+        return [(lse, (B * H * nq,), (1,))]
+    o = [int(x) for x in off.reshape(-1)[:B + 1]]
+    return [(_at(lse, b * H * nq), (H, min(nq, o[b + 1] - o[b])), (nq, 1)) for b in range(B) if o[b + 1] > o[b]]
+
+
+def keep_bits_words(B, H, nq, nk):
+    """dwords of the keep_bits buffer (KeepBits::word0 of csrc/sdpa.hip): per problem and 32-query fragment, 32 per key fragment"""
+    return B * H * ((nq + 31) // 32) * ((nk + 31) // 32) * 32
+
+
+def _o_sdpa_fwd(a):
+    B, H, nq, nk = a["B"], a["H"], a["nq"], a["nk"]
+    written = a["keep_bits"] is not None and a["p_drop"] > 0             # (DROP && keep_bits != nullptr: no store without dropout)
+    return (_o_rows(a["o"], B, nq, H * a["dh"], a["ldo"], a["q_off"], a["q_pad"]) + _o_lse(a["lse"], B, H, nq, a["q_off"])
+            + ([(a["keep_bits"], (keep_bits_words(B, H, nq, nk),), (1,))] if written else _held(a["keep_bits"]))
+            + _held(a["q"], a["k"], a["v"], a["key_mask"]))
+
+
+def _o_sdpa_bwd(a):
+    B, H, nq, nk, HD = a["B"], a["H"], a["nq"], a["nk"], a["H"] * a["dh"]
+    return (_o_rows(a["dq"], B, nq, HD, a["lddq"], a["q_off"], a["q_pad"]) + _o_rows(a["dk"], B, nk, HD, a["lddk"], a["k_off"], a["k_pad"])
+            + _o_rows(a["dv"], B, nk, HD, a["lddv"], a["k_off"], a["k_pad"])
+            + [x for x in (_whole(a["ws"]), _t(a["bias_grad"], 3 * HD)) if x is not None]
+            + _held(a["q"], a["k"], a["v"], a["key_mask"], a["dout"], a["lse"], a["keep_bits"]))
+
+
+def _o_attn_probs(a):
+    """attn_probs_kernel writes the whole dense [B, H, nq, nk] block: zeros for missing queries, missing and masked keys"""
+    return [_t(a["probs"], a["B"] * a["H"] * a["nq"] * a["nk"])] + _held(a["q"], a["k"], a["key_mask"], a["lse"])
+
+
 # name -> the logical views a call may write (everything else of the outputs' storages stays bit-identical: "outside view")
 ROW_OUTS = {
     "layernorm_fwd": lambda a: [_t(a["y"], a["M"], a["N"]), _t(a["mean"], a["M"]), _t(a["rstd"], a["M"])],
@@ -467,6 +525,7 @@ ROW_OUTS = {
     "remask_lowest": lambda a: [_t(a["vis_mask"], a["B"] * a["V"])],
     "sampler_update": lambda a: [_t(a["code_ids"], a["n"])],
     "sampler_ar_update": lambda a: [_t(a[k], a["B"] * a["V"]) for k in ("code_ids", "vis_mask", "visited")],
+    "sdpa_fwd": _o_sdpa_fwd, "sdpa_bwd": _o_sdpa_bwd, "attn_probs": _o_attn_probs,
 }
 
 
@@ -979,7 +1038,38 @@ class Recorder:
                                            a["q"].dtype)
         name += f"{' + dropout' if a['p_drop'] > 0 else ''}{' keep_bits' if a.get('keep_bits') is not None else ''}" \
                 f"{' packed' if a['q_off'] is not None or a['k_off'] is not None else ''}"
+        if direction == "bwd" and a["bias_grad"] is not None:
+            # xl_sdpa_bwd: per-example partials in the workspace and one reduce (the on-chip MFMA kernel, a workspace, and B slabs
+            # of 3 H dh floats inside xl_workspace_floats(H dh)), otherwise three xl_colsum calls over the STORED dq / dk / dv
+            HD = a["H"] * a["dh"]
+            fused = (name.startswith("sdpa_bwd_mfma") and a["ws"] is not None
+                     and a["B"] * 3 * HD <= self._ops.workspace_floats(HD))
+            name += " fused bias" if fused else " separate colsum" if a["ws"] is not None else " separate colsum no workspace"
         return name, n_kblk, n_qblk
+
+    @staticmethod
+    def _arith(kern, t):
+        """(storage type of the outputs, arithmetic) for the attention bounds: the on-chip generic kernels compute in fp32
+        throughout and are held to the storage type they write; every other kernel keeps the bounds it has always been held to
+        (bf16 outputs, P and dS rounded to bf16 between the MFMA contractions)"""
+        return (t.dtype, "fp32") if "_generic" in kern else (torch.bfloat16, "mfma")
+
+    def _keep_bits_ref(self, a, dev):
+        """the keep_bits buffer as the comment at struct KeepBits (csrc/sdpa.hip) lays it out: for problem bh and query fragment j,
+        dword (i*16 + r)*2 + h holds at bit t the keep decision of query j*32 + t and key i*32 + (r&3) + 8*(r>>2) + 4*h, hashed
+        with row counter bh * nq + query (capacity indexing; also for the queries and keys a fragment carries beyond nq / nk)"""
+        B, H, nq, nk = a["B"], a["H"], a["nq"], a["nk"]
+        nqf, nkf = (nq + 31) // 32, (nk + 31) // 32
+        ar = lambda n: torch.arange(n, device=dev)                                   # noqa: E731
+        bh, j, i, r, h, t = (x.view(*sh) for x, sh in zip((ar(B * H), ar(nqf), ar(nkf), ar(16), ar(2), ar(32)),
+                                                           ((-1, 1, 1, 1, 1, 1), (1, -1, 1, 1, 1, 1), (1, 1, -1, 1, 1, 1),
+                                                            (1, 1, 1, -1, 1, 1), (1, 1, 1, 1, -1, 1), (1, 1, 1, 1, 1, -1))))
+        row = bh * nq + j * 32 + t
+        col = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h
+        row, col = torch.broadcast_tensors(row, col)
+        keep = (keep_scale(self._ref._seed(a["seed"]), row, col, a["p_drop"]) > 0).to(torch.int64)
+        words = (keep << t.to(torch.int64)).sum(-1)                                  # [BH, nqf, nkf, 16, 2] -> dword order
+        return words.reshape(-1)
 
     def chk_sdpa_fwd(self, a, s, run):
         B, H, nq, nk, dh = a["B"], a["H"], a["nq"], a["nk"], a["dh"]
@@ -992,15 +1082,29 @@ class Recorder:
         O_, _ = self._ref._load(s["o"], B, nq, H, dh, a["ldo"], s["q_off"])
         lse = s["lse"].reshape(-1)[:B * H * nq].view(B, H, nq)
         kern, n_kblk, _ = self._sdpa_kernel("fwd", a)
-        bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, a["scale"], O_, lse, n_kblk=n_kblk)
+        out_dt, arith = self._arith(kern, a["o"])
+        bO, bl = BD.sdpa_fwd_bounds(Q, K, V, valid, keep, a["scale"], O_, lse, n_kblk=n_kblk, out_dtype=out_dt, arith=arith)
         rows = lambda t: BD.attention_rows(self._ref, t, B, nq, H, dh, a["ldo"], a["q_off"], a["q_pad"])   # noqa: E731
         ref_rows = BD.attention_rows(self._ref, s["o"], B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"])
         bO = BD.attention_scatter(self._ref, bO, B, nq, H, dh, a["ldo"], s["q_off"], a["q_pad"])[:ref_rows.shape[0]]
         exist = valid.any(-1).expand(B, H, nq)       # (the only elements left out of a comparison: the lse of a query without a key)
         self.lse_excluded.append(("sdpa_fwd", self._short(a), int((~exist).sum())))
+        # ... and their number follows from the inputs: per head, the queries an example does not have (packed q side) and the
+        # queries of an example none of whose keys attends (key mask, packed k side)
+        lens = lambda off, n: ([n] * B if off is None else                            # noqa: E731
+                               [min(n, int(off.reshape(-1)[b + 1]) - int(off.reshape(-1)[b])) for b in range(B)])
+        lq, lk = lens(s["q_off"], nq), lens(s["k_off"], nk)
+        on = [lk[b] if s["key_mask"] is None else int((s["key_mask"].reshape(-1)[b * nk:b * nk + lk[b]] != 0).sum()) for b in range(B)]
+        want = H * sum((nq - lq[b]) + (lq[b] if on[b] == 0 else 0) for b in range(B))
+        assert int((~exist).sum()) == want, f"sdpa_fwd: {int((~exist).sum())} lse entries left out of the comparison, the inputs give {want}"
         got_l = a["lse"].reshape(-1)[:B * H * nq].view(B, H, nq)
-        return [("O", BD.check(rows(a["o"]), ref_rows, bO, "sdpa_fwd O"), kern),
-                ("lse", BD.check(got_l[exist], lse[exist], bl[exist], "sdpa_fwd lse"), kern)]
+        res = [("O", BD.check(rows(a["o"]), ref_rows, bO, "sdpa_fwd O"), kern),
+               ("lse", BD.check(got_l[exist], lse[exist], bl[exist], "sdpa_fwd lse"), kern)]
+        if a["keep_bits"] is not None and a["p_drop"] > 0:
+            n = keep_bits_words(B, H, nq, nk)
+            got_w = a["keep_bits"].reshape(-1)[:n].to(torch.int64) & 0xFFFFFFFF
+            res.append(("keep_bits", BD.check_exact(got_w, self._keep_bits_ref(a, got_w.device), "sdpa_fwd keep_bits"), kern))
+        return res
 
     def chk_sdpa_bwd(self, a, s, run):
         B, H, nq, nk, dh = a["B"], a["H"], a["nq"], a["nk"], a["dh"]
@@ -1013,11 +1117,14 @@ class Recorder:
         sides = (("dq", nq, "lddq", "q_off", "q_pad"), ("dk", nk, "lddk", "k_off", "k_pad"), ("dv", nk, "lddv", "k_off", "k_pad"))
         dense = [self._ref._load(s[nm], B, n, H, dh, a[ld], s[off])[0] for nm, n, ld, off, _ in sides]
         kern, n_kblk, n_qblk = self._sdpa_kernel("bwd", a)
-        bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, a["scale"], lse, *dense, n_kblk=n_kblk, n_qblk=n_qblk)
+        out_dt, arith = self._arith(kern, a["dq"])
+        bounds, terms = BD.sdpa_bwd_bounds(Q, K, V, dO, valid, keep, a["scale"], lse, *dense, n_kblk=n_kblk, n_qblk=n_qblk,
+                                           out_dtype=out_dt, arith=arith)
         # the long and the generic kernels have no fused partials: their bias gradients are xl_colsum of the STORED dq / dk / dv
         # (bf16-rounded), so each element enters the sum with its whole bound: bounds.colsum_bound.  The on-chip MFMA kernel keeps
         # the bound it has always been held to (fused fp32 partials: no rounding of the summands).
-        stored_sums = not kern.startswith("sdpa_bwd_mfma")
+        # So does the on-chip MFMA kernel when it has no workspace, or more examples than the workspace has slabs for.
+        stored_sums = "fused bias" not in kern
         res = []
         HD = H * dh
         for (nm, n, ld, off, pad), b, t in zip(sides, bounds, terms):

@@ -327,7 +327,8 @@ def attn_probs_long(dev="cuda", ops=None, B=8):
         c.probs(rec)
         cases.append(c)
     finish(rec, t0, cases, 3 * len(cases))
-    assert len([r for r in rec.rows if r[0] == "attn_probs"]) == len(cases)
+    assert len([r for r in rec.rows if r[0] == "attn_probs" and r[1] == "probs"]) == len(cases)
+    assert len([r for r in rec.rows if r[0] == "attn_probs" and r[1] == "outside view"]) == len(cases)
     return rec
 
 

@@ -1285,6 +1285,15 @@ extern "C" int xl_sdpa_bwd(const void* q, const void* k, const void* v, const ui
     const bool is_long = nq > MAXN || nk > MAXN;
     const bool fused_bias = !is_long && bias_grad != nullptr && workspace != nullptr && dtype == XL_BF16 && mfma_eligible(a, true) &&
                             (int64_t)B * 3 * HD <= xl_workspace_floats(HD);
+    // without fused partials the bias gradients are xl_colsum of the stored dq / dk / dv, which takes whole 16-byte vectors only:
+    // refused HERE, before the backward is launched -- refused by xl_colsum afterwards, the call had already written the three
+    // gradients (and, where dq passed and dk did not, a third of bias_grad) when it returned its error
+    if (bias_grad != nullptr && !fused_bias) {
+        const int vec = dtype == XL_F32 ? 4 : 8;
+        XL_CHECK_ARG(HD % vec == 0 && lddq % vec == 0 && lddk % vec == 0 && lddv % vec == 0, XL_ERR_BAD_SHAPE,
+                     "xl_sdpa_bwd: bias_grad from column sums of the stored gradients needs H * dh = %d and lddq, lddk, lddv = %d, %d, %d "
+                     "to be multiples of %d", HD, lddq, lddk, lddv, vec);
+    }
     if (is_long) {
         // delta [B, H, nq] goes through the caller's workspace (free again before the bias column sums below use it)
         XL_CHECK_ARG(workspace != nullptr && (int64_t)B * H * nq <= xl_workspace_floats(HD), XL_ERR_BAD_ARG,
