@@ -489,6 +489,55 @@ int xl_score_rows(const float* logits, int M, int K, int ldl, const int64_t* lab
 int xl_sample_rows_trunc(const float* logits, int M, int K, int ldl, float inv_T, uint64_t seed, int top_k, float top_p,
                          float log_min_p, float* row_prob, int32_t* row_id, float* row_lse, int32_t* row_kept, void* stream);
 
+/* ---------------------------------------------------------------- caption-image matching (the `matched` head over N x M pairs)
+ * N captions against M images.  The 9 language layers never see the picture and the feature encoder + 5 visual layers never see the
+ * text, so the two stacks run ONCE (batch N, batch M); only the cross layers, the pooler and the 2-way head run per pair, in chunks
+ * of B_c pair slots.  Pair order is caption-major: pair p = n*M + m.
+ *
+ * xl_pair_expand fills the first cross layer's input of one chunk on the device -- no index list from the host, no round trip:
+ *   vis, lang           the stacks' outputs: [M*V, d] visual rows (image m owns rows m*V ..) and the PACKED language rows
+ *                       [lang_src_rows, d], caption n owning rows [lang_off[n], lang_off[n+1]) (lang_off int32 [N+1], device; a dense
+ *                       [N*L, d] source is lang_off[n] = n*L).  len_n = lang_off[n+1] - lang_off[n], CLAMPED to [0, L] by the kernel
+ *                       (the host cannot check it without a round trip); a source row outside [0, lang_src_rows) is read as zeros.
+ *   lang_len            int32 [N] or NULL, dense chunk layout only: len_n of a source whose offsets are not the prefix sums of its
+ *                       lengths (the dense source: lang_off[n] = n*L and every caption owns L rows, len_n of them real).
+ *   vis2, lang2, x0_2   a second copy of the stream in another element type (the fp32 residual stream keeps the fp32 value and its
+ *                       bf16 rounding: the cross layers read both), all three or none; `dtype2` is its type.
+ *   slot j of the chunk (0 <= j < B_c) holds pair pair_start + min(j, pair_count - 1): the slots of a ragged last chunk repeat its
+ *                       last real pair, so nothing downstream reads uninitialised rows (xl_match_rank never writes their scores).
+ *   x0                  [B_c*V + lang_rows_pad, d]: rows j*V + v = image m's row v; then the language rows --
+ *     packed != 0       slot j's rows start at chunk_off[j] = F(p_j) + len * (j - min(j, pair_count-1)) - F(pair_start), with
+ *                       F(p) = M*lang_off[n] + m*len_n the first row of pair p in the list of ALL pairs (closed form, 64-bit on the
+ *                       device); chunk_off int32 [B_c+1], chunk_off[B_c] = the chunk's row count; chunk_rows int32 [lang_rows_pad]:
+ *                       j*L + l for the packed row of (slot j, position l), -1 in the tail; chunk_kmask uint8 [B_c, L] = (l < len);
+ *                       rows [chunk_off[B_c], lang_rows_pad) -- the tail that pads the packed rows to the GEMM row tile -- are zero
+ *                       rows.  lang_rows is the HOST's value of chunk_off[B_c] (it sizes the launch; the kernel never writes a row
+ *                       at or beyond lang_rows_pad whatever lang_off says), lang_rows <= lang_rows_pad <= B_c*L + 255.
+ *     packed == 0       row j*L + l = caption n's row l for l < len_n, a zero row beyond; chunk_kmask as above; chunk_off and
+ *                       chunk_rows are not touched (may be NULL); lang_rows = lang_rows_pad = B_c*L.
+ * Rows move as 16-byte vectors: d must be a multiple of 8 (XL_ERR_BAD_SHAPE) and the buffers 16-byte aligned.  Refused without a
+ * launch: NULL buffers, N or M outside 1..4096, L > 512, pair_count outside 1..B_c, pairs beyond N*M, inconsistent row counts.
+ *
+ * xl_match_rank, two stages in launch order (either may be left out):
+ *   scatter (rel != NULL)   rel fp32 [pairs of the chunk, 8] as the 2-way head writes it (columns 0, 1).  For i < pair_count, pair
+ *                       p = pair_start + i:  margin[p] = rel[i,1] - rel[i,0] (one fp32 subtraction),  prob[p] = 1 / (1 + expf(-margin)),
+ *                       the softmax's matched probability (prob may be NULL).  Slots at or beyond pair_count are never read or written.
+ *   rank (rank_stage != 0)  over the whole margin [N, M] (after the last chunk's scatter), one wave per query, both directions:
+ *                       topk_images int32 [N, k]: per caption its k best images; topk_captions int32 [M, k]: per image its k best
+ *                       captions (either may be NULL; 1 <= k <= min(32, candidates) for each one given);  with image_of_caption
+ *                       int32 [N] / caption_of_image int32 [M] (-1 = no target): rank_t2i[n] / rank_i2t[m] = the number of candidates
+ *                       that rank BEFORE the target, -1 without one (a target array and its rank output come together or not at all).
+ *   order               by MARGIN, descending, ties to the lower index (never by prob: fp32 saturates it at 1.0 beyond a margin of
+ *                       ~17 and would manufacture ties); a NaN margin ranks as -inf.  The stage only compares: exact, the position in
+ *                       a stable descending sort.  No floating-point atomics. */
+int xl_pair_expand(const void* vis, const void* lang, const void* vis2, const void* lang2, const int* lang_off, const int* lang_len,
+                   void* x0, void* x0_2, int* chunk_off, int* chunk_rows, void* chunk_kmask, int N, int M, int V, int L, int d,
+                   int pair_start, int pair_count, int B_c, int packed, int lang_src_rows, int lang_rows, int lang_rows_pad,
+                   int dtype, int dtype2, void* stream);
+int xl_match_rank(const float* rel, int pair_start, int pair_count, float* margin, float* prob, int N, int M, int rank_stage,
+                  int k, int* topk_images, int* topk_captions, const int* image_of_caption, const int* caption_of_image,
+                  int* rank_t2i, int* rank_i2t, void* stream);
+
 /* ---------------------------------------------------------------- optimizer side (ref lxmert_pretrain.py:343-364)
  * sumsq[0] += sum g^2 over n fp32 elements.  Deterministic: block partials are added in a fixed order by the last block to
  * arrive, so every rank of a data-parallel job derives the same clip factor from the same reduced gradients (an atomic per block

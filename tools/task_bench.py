@@ -1,6 +1,6 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint|eval] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint|eval|match] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
 --rows eval: the validation pass alone (bs 256): ms per Engine.evaluate_task for vis_mask (`--vis_mask_predict` masks, n ~ U{1..64}) and
 word_mask (labelled rows from the loader), on the fused path (XL_EPI_ROWSCORE records) and on the logits path (XL_FUSED_PREDICT=0),
 alternating in this process with their yardstick, Engine.task_forward(task, want_grad=False): all rows, fp32 logits.
@@ -8,6 +8,10 @@ alternating in this process with their yardstick, Engine.task_forward(task, want
 the fused and on the logits predict path and with the visual stack recomputed every step, in one alternation with the arms below.
 --rows inpaint: Engine.inpaint_codes alone (bs 256, Mask-Predict T = 4, half of every grid free): ms per batch, greedy (and drawn, with
 --temperature), alternating in this process with the `sampler` row's loop (sample_codes_nar(4) on the same engine), its yardstick.
+--rows match: caption-image matching alone (full model, L = 20, V = 64, ragged captions): ms per XLxmertForPretraining-style
+match.MatchRunner.run for N = M = 16 and N = M = 32 (stacks once, cross layers per pair, ranking on the device), alternating in this
+process with the path that existed before it: the same N*M pairs materialised as rows of an ordinary engine (batches of 256),
+encoder_forward + rel_fwd.  The lines also go to --out (default profiles/match/task_bench_match.txt).
 --temperature: the sampler rows are timed greedy AND with temperature sampling, alternating in this process (rounds of 8 loops
 each; the line gives the median and the min..max spread of both).
 --top-k / --top-p / --min-p (any of them): a third arm in the same alternation, the truncated sampler at that temperature (1 if
@@ -21,12 +25,13 @@ from xlxmert_amd.config import XLxmertConfig
 from xlxmert_amd.trainer import PretrainStep, word_rows_of
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint", "eval"), default="all")
+ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint", "eval", "match"), default="all")
 ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
 ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
 ap.add_argument("--top-k", type=int, default=None, help="truncated arm: at most K candidates (1..256)")
 ap.add_argument("--top-p", type=float, default=None, help="truncated arm: nucleus mass in (0, 1]")
 ap.add_argument("--min-p", type=float, default=None, help="truncated arm: probability floor relative to the mode, in (0, 1]")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match", "task_bench_match.txt"), help="--rows match: file the lines are written to")
 ap.add_argument("--rounds", type=int, default=5, help="greedy / sampled alternations (with --temperature)")
 args = ap.parse_args()
 trunc = {k: v for k, v in (("top_k", args.top_k), ("top_p", args.top_p), ("min_p", args.min_p)) if v is not None}
@@ -221,8 +226,71 @@ def eval_row(B=256, L=20):
         del eng, store
 
 
+def match_row(L=20, V=64):
+    from xlxmert_amd.match import MatchRunner
+    from xlxmert_amd.trainer import synthetic_batch
+    store = ParamStore(cfg, dev, torch.bfloat16, task="matched")
+    init_reference_weights(store, 1)
+    g = torch.Generator().manual_seed(0)
+    store.set_centroids(torch.randn(cfg.num_clusters, cfg.visual_feat_dim, generator=g).relu())
+    ops = HipOps(torch.bfloat16)
+    lines = [f"caption-image matching, full model (9/5/5, d = {cfg.hidden_size}), L = {L}, V = {V}, bf16, ragged captions; "
+             f"{args.rounds} rounds of 4 calls per arm, arms alternating in one process"]
+    for n in (16, 32):
+        b = synthetic_batch(cfg, n, L, 8, seed=5)
+        x = cuda({k: b[k] for k in ("input_ids", "attention_mask", "cluster_ids", "visual_pos")})
+        tgt = torch.arange(n, device=dev)
+        runner = MatchRunner(cfg, store, ops, n, n, L, V)
+        runner.sync_compute_weights()
+        # the path that existed before: the N*M rows, built once on the host (its best case), through an engine of 256 rows
+        Bm = min(n * n, 256)
+        eng = Engine(cfg, store, ops, Bm, L, V, need_lang=True)
+        rep, til = (lambda t: t.repeat_interleave(n, 0)), (lambda t: t.repeat(n, *([1] * (t.dim() - 1))))
+        big = cuda({"input_ids": rep(b["input_ids"]), "attention_mask": rep(b["attention_mask"]), "cluster_ids": til(b["cluster_ids"]),
+                    "visual_pos": til(b["visual_pos"])})
+        am = big["attention_mask"].cpu()
+        parts = []
+        for s in range(0, n * n, Bm):
+            a = am[s:s + Bm]
+            parts.append(dict(lang_rows=a.reshape(-1).nonzero().reshape(-1).cuda(),
+                              lang_off=torch.cat([torch.zeros(1, dtype=torch.int64), a.sum(1).cumsum(0)]).to(torch.int32).cuda()))
+        margin = torch.zeros(n * n, device=dev)
+
+        def materialised():
+            for i, s in enumerate(range(0, n * n, Bm)):
+                eng.set_inputs(big["input_ids"][s:s + Bm], big["attention_mask"][s:s + Bm], None, big["visual_pos"][s:s + Bm],
+                               cluster_ids=big["cluster_ids"][s:s + Bm], **parts[i])
+                eng.encoder_forward(want_pooled=True)
+                rel = eng.lang_heads.rel_fwd(eng.pooled)
+                margin[s:s + Bm] = rel[:, 1] - rel[:, 0]
+
+        def shared():
+            runner.run(x["input_ids"], x["attention_mask"], None, cluster_ids=x["cluster_ids"], visual_pos=x["visual_pos"], top_k=5,
+                       image_of_caption=tgt, caption_of_image=tgt)
+        arms = {"match_scores (shared stacks)": shared, "materialised N*M rows": materialised}
+        runs = {k: [] for k in arms}
+        for _ in range(args.rounds):
+            for k, fn in arms.items():
+                runs[k].append(timed(fn, n=4, warm=1))
+        lines.append(f"N = M = {n:3d}: {n * n} pairs, chunks of {runner.B_c}")
+        med = {}
+        for k, v in runs.items():
+            v = sorted(v)
+            med[k] = v[len(v) // 2]
+            lines.append(f"  {k:30s}: median {med[k] * 1e3:7.2f} ms  min {v[0] * 1e3:7.2f}  max {v[-1] * 1e3:7.2f}  {n * n / med[k]:9.0f} pairs/s")
+        a, m_ = med["match_scores (shared stacks)"], med["materialised N*M rows"]
+        lines.append(f"  ratio shared / materialised: {a / m_:5.3f}  ({m_ / a:4.2f}x)")
+        del runner, eng
+    print("\n".join(lines))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if args.rows == "eval":
     eval_row()
+if args.rows == "match":
+    match_row()
 if args.rows in ("all", "caption"):
     caption_row()
 if args.rows == "inpaint":

@@ -1792,7 +1792,13 @@ class Engine:
         # the feature encoder + r_layers visual stack (they never see the text) -- it still sits in the visual rows of X[0] from
         # the loop's first pass (no later layer writes there), so the later passes skip them.  Exact under the same condition.
         skip_vis = getattr(self, "_reuse_vis_stack", False) and self.p_hid == 0 and self.p_attn == 0
-        assert not (skip_lang and skip_vis)
+        # caption-image matching (match.MatchRunner): X[0] is GIVEN -- both stacks ran once on engines of their own batch sizes and
+        # xl_pair_expand laid their outputs out pair by pair -- so neither stack runs here.  Exact under the same condition, which
+        # the runner establishes for the call (with dropout the stacks would have to run here, over inputs nobody staged).
+        x0_given = getattr(self, "_x0_given", False)
+        assert not x0_given or (self.p_hid == 0 and self.p_attn == 0), "_x0_given needs dropout off"
+        skip_lang, skip_vis = skip_lang or x0_given, skip_vis or x0_given
+        assert x0_given or not (skip_lang and skip_vis)
         pairs = [] if skip_lang or skip_vis else self._stack_pairs()
         n_lang_alone = cfg.l_layers - len(pairs)
         n_vis_alone = cfg.r_layers - len(pairs)

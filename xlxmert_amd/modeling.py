@@ -441,6 +441,51 @@ class XLxmertForPretraining(nn.Module):
             self.train(was_training)
 
     @torch.no_grad()
+    def match_scores(self, input_ids, attention_mask=None, token_type_ids=None, visual_feats=None, cluster_ids=None, visual_pos=None, *,
+                     top_k=None, chunk_pairs=None, image_of_caption=None, caption_of_image=None):
+        """Score every one of N captions (`input_ids` [N, L]; `attention_mask` prefix masks, None = full length) against every one of
+        M images (`visual_feats` [M, V, F] or `cluster_ids` [M, V], un-masked; `visual_pos` [M, V, 4], default: the boxes of a square
+        grid) with the `matched` head -- image retrieval, caption retrieval, re-ranking of samples, recall@k -- match.MatchRunner:
+        the language stack runs once at batch N, the visual stack once at batch M, only the cross layers, the pooler and the 2-way
+        head run per pair, in chunks of `chunk_pairs` pairs (default min(N*M, 256)); N, M <= 4096.  eval() semantics for the call.
+        Returns a dict of device tensors: `margin` [N, M] = logit(matched) - logit(not matched) and `prob` [N, M] = its sigmoid, the
+        softmax's matched probability; with top_k (<= min(32, N, M)) `topk_images` [N, k] / `topk_captions` [M, k] int32, ordered by
+        margin, ties to the lower index; with targets `image_of_caption` [N] / `caption_of_image` [M] (ints, -1 = none) `rank_t2i` /
+        `rank_i2t` (the number of candidates that rank before the target, -1 without one) and `recall` = {"t2i" | "i2t": {1, 5, 10:
+        fraction of the queries with a target whose rank is < k}}, computed on the device and read by the host once (with it
+        `recall_hits` fp32 [2, 4], the additive counts {rank < 1, < 5, < 10, queries with a target} per direction)."""
+        from .match import RECALL_AT, MatchRunner
+        if not self.task_matched:
+            raise RuntimeError("match_scores on a model built without task_matched (no `cls` matched head)")
+        if (visual_feats is None) == (cluster_ids is None):
+            raise ValueError("give the pictures either as visual_feats or as cluster_ids")
+        if cluster_ids is not None and self.vis_emb is None:
+            raise RuntimeError("cluster_ids given but the model has no codebook: call set_visual_embedding(centroids) first")
+        vis = visual_feats if cluster_ids is None else cluster_ids
+        (N, L), M, V = input_ids.shape, vis.shape[0], vis.shape[1]
+        if visual_pos is None:
+            g = int(round(V ** 0.5))
+            if g * g != V:
+                raise ValueError(f"visual_pos is needed for {V} visual tokens (not a square grid)")
+            visual_pos = self._grid_pos(g, M, vis.device)
+        key = (N, M, L, V, chunk_pairs)
+        if getattr(self, "_match_key", None) != key:
+            self._match_runner = MatchRunner(self.config, self._store, self.bert._ops, N, M, L, V, chunk_pairs=chunk_pairs,
+                                             residual_dtype=self.bert._residual_dtype)
+            self._match_key = key
+        runner = self._match_runner
+        runner.sync_compute_weights()
+        out = runner.run(input_ids, attention_mask, token_type_ids, visual_feats=visual_feats, cluster_ids=cluster_ids,
+                         visual_pos=visual_pos, top_k=top_k, image_of_caption=image_of_caption, caption_of_image=caption_of_image)
+        out = {k: v.clone() for k, v in out.items()}
+        if "recall_hits" in out:
+            hits = out["recall_hits"].tolist()                                  # the one host read
+            names = [n for n, r in (("t2i", "rank_t2i"), ("i2t", "rank_i2t")) if r in out]
+            out["recall"] = {n: {k: hits[i][j] / max(hits[i][3], 1.0) for j, k in enumerate(RECALL_AT)}
+                             for i, n in enumerate(("t2i", "i2t")) if n in names}
+        return out
+
+    @torch.no_grad()
     def sample_codes(self, input_ids, n_steps=4, grid_size=8, *, temperature=None, seed=None, top_k=None, top_p=None, min_p=None):
         """The device part of ImggenModel.sample_image_NAR (ref tasks/imggen_model.py:169-254): Mask-Predict sampling of
         the grid codes, returned as the generator's input `[B, feat_dim, grid, grid]` (fp32) plus the chosen code ids.
@@ -853,6 +898,14 @@ class ImggenModel(XLxmertForPretraining):
         g = self.grid_size
         x = code.view(B, g * g, -1).permute(0, 2, 1).reshape(B, -1, g, g).float()
         return self.denorm(self.G(x)).cpu()
+
+    @torch.no_grad()
+    def rank_images(self, sentences, cluster_ids, max_text_length=20, *, top_k=None, chunk_pairs=None):
+        """Rank M images, given as grid codes `cluster_ids` [M, V] (e.g. what the samplers return), for every one of the N sentences by
+        the model's own matching score: XLxmertForPretraining.match_scores with the tokenisation of the samplers (attention mask =
+        input ids > 0).  Returns its dict (margin, prob, and with top_k the lists)."""
+        ids = self._input_ids(sentences, max_text_length)
+        return self.match_scores(ids, ids > 0, None, cluster_ids=cluster_ids, top_k=top_k, chunk_pairs=chunk_pairs)
 
     @torch.no_grad()
     def sample_image_NAR(self, sentences, max_text_length=20, n_steps=None, return_intermediate=False, *, temperature=None,

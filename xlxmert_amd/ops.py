@@ -386,6 +386,23 @@ class HipOps:
         self._call("xl_grid_step", self._p(row_prob), self._p(row_id), self._p(free_mask), self._p(order), self._p(code_ids),
                    self._p(vis_mask), self._p(conf), self._p(score), B, V, int(mode), int(step), int(n_steps), self._stream())
 
+    # -- caption-image matching
+    def pair_expand(self, vis, lang, lang_off, x0, chunk_off, chunk_rows, chunk_kmask, N, M, V, L, d, pair_start, pair_count, B_c, packed,
+                    lang_src_rows, lang_rows, lang_rows_pad, vis2=None, lang2=None, x0_2=None, lang_len=None):
+        """the first cross layer's input of one chunk of pairs from the two stacks' outputs (xl_pair_expand); vis2 / lang2 / x0_2: the
+        second copy of an fp32 residual stream; lang_len: int32 [N] lengths of a dense source (dense chunk layout only)."""
+        self._call("xl_pair_expand", self._p(vis), self._p(lang), self._p(vis2), self._p(lang2), self._p(lang_off), self._p(lang_len), self._p(x0),
+                   self._p(x0_2), self._p(chunk_off), self._p(chunk_rows), self._p(chunk_kmask), N, M, V, L, d, int(pair_start),
+                   int(pair_count), B_c, int(bool(packed)), int(lang_src_rows), int(lang_rows), int(lang_rows_pad), xl_dtype(vis.dtype),
+                   xl_dtype(vis2.dtype) if vis2 is not None else 0, self._stream())
+
+    def match_rank(self, rel, pair_start, pair_count, margin, prob, N, M, rank_stage=False, k=0, topk_images=None, topk_captions=None,
+                   image_of_caption=None, caption_of_image=None, rank_t2i=None, rank_i2t=None):
+        """scores of one chunk (rel given) and / or the ranking over the whole [N, M] margin (rank_stage) -- xl_match_rank."""
+        self._call("xl_match_rank", self._p(rel), int(pair_start), int(pair_count), self._p(margin), self._p(prob), N, M,
+                   int(bool(rank_stage)), int(k), self._p(topk_images), self._p(topk_captions), self._p(image_of_caption),
+                   self._p(caption_of_image), self._p(rank_t2i), self._p(rank_i2t), self._stream())
+
     # -- attention core
     def sdpa_keep_bits_bytes(self, B, H, nq, nk, dh):
         """bytes of the buffer in which sdpa_fwd leaves its dropout decisions for sdpa_bwd (0: this geometry / dtype runs on kernels
