@@ -538,6 +538,63 @@ int xl_match_rank(const float* rel, int pair_start, int pair_count, float* margi
                   int k, int* topk_images, int* topk_captions, const int* image_of_caption, const int* caption_of_image,
                   int* rank_t2i, int* rank_i2t, void* stream);
 
+/* ---------------------------------------------------------------- image generator (csrc/generator.hip; ref image_generator/src/layers.py)
+ * The frozen SPADE decoder that turns an 8x8 grid of codes into pixels.  Activations are NHWC: element (b, y, x, c) of a tensor
+ * lives at ((b*H + y)*W + x) * ld + c, ld >= C the PIXEL STRIDE in elements (a view into a wider buffer is ld > C).  `dtype`
+ * (XL_F32 / XL_BF16) is the element type of activations AND weights; bias, statistics, noise and the RGB accumulator are fp32.
+ *
+ * DEVICE WEIGHT LAYOUT of a convolution (the host repacks torch's [Cout, Cin/groups, kh, kw] once, xlxmert_amd/generator.py):
+ *     w[(kh*ks + kw) * Cout * Cg + co * Cg + ci],  Cg = Cin / groups          (tap-major, then output channel, input channel last)
+ * Output channel co belongs to group co / (Cout/groups) and reads the input channels [g*Cg, (g+1)*Cg).  For XL_CONV_SPADE the gamma
+ * and the beta convolution of a SPADE are ONE weight of Cout = 2C rows: gamma's C rows first, beta's C rows after (bias likewise).
+ *
+ * xl_conv2d_nhwc: ks = 3 (zero pad 1) or ks = 1, stride 1, fp32 accumulation, fp32 bias (may be NULL).  acc = conv(x, w) + bias, then
+ *   XL_CONV_NONE   y = acc
+ *   XL_CONV_RELU   y = max(acc, 0)
+ *   XL_CONV_ADD    y = acc + aux                                   (aux [B, H, W, Cout] with pixel stride ldaux: the residual branch)
+ *   XL_CONV_SPADE  Cout = 2C; y, aux [B, H, W, C]:  t = (aux[b,p,c] - mean[b*C+c]) * rstd[b*C+c] * (1 + acc[c]) + acc[C+c]
+ *                  + noise_w * noise[b*H*W + p];  y = t >= 0 ? t : slope * t          (modulate, then noise, then LeakyReLU: ref
+ *                  layers.py:46,60,99; noise may be NULL = no noise term; gamma and beta never reach memory)
+ * Kernels: bf16 with groups == 1, Cin % 16 == 0, Cout % 32 == 0, Cout <= 128, ldx % 8 == 0 and 16-byte aligned x / w runs the
+ * implicit-GEMM kernel on v_mfma_f32_32x32x16_bf16 (a workgroup owns 8 x 32 output pixels x all of Cout; the haloed input tile is
+ * staged in LDS once and the 9 taps read it at shifted addresses); everything else (fp32, groups, Cout = 3, other channel counts)
+ * runs a plain-FMA kernel with the same epilogues.  Refused without a launch (nothing written): NULL x / w / y, ks not 1 or 3,
+ * B, H, W, Cin, Cout < 1, groups that do not divide Cin and Cout, a pixel stride below the channel count, an unknown epilogue or
+ * dtype, XL_CONV_ADD without aux, XL_CONV_SPADE with an odd Cout or groups != 1 or without aux / mean / rstd, B*H*W*max(ld) >= 2^31.
+ *
+ * xl_instnorm_stats: mean[b*C+c] and rstd[b*C+c] = 1 / sqrt(biased variance + eps) over the H*W pixels of x [B, HW, C] (stride ld).
+ *   Two stages in a fixed order, no floating-point atomics: stage 1 reduces chunks of XL_INSTNORM_CHUNK pixels to (mean, M2) around a
+ *   per-chunk shift (the chunk's first pixel: no E[x^2] - E[x]^2 of large numbers), stage 2 combines the chunks in index order
+ *   (Chan's update).  ws: fp32 workspace of at least 2 * B * ceil(HW / XL_INSTNORM_CHUNK) * C floats.
+ *
+ * xl_resize_bilinear_nhwc: torch's bilinear, align_corners=False: src = max((dst + 0.5) * in/out - 0.5, 0), taps i0 = floor(src) and
+ *   min(i0 + 1, in - 1), weights (1 - f, f) in fp32; y = wy0 * (wx0*a + wx1*b) + wy1 * (wx0*c + wx1*d).  Any sizes.
+ *
+ * xl_torgb_accum: rgb [B, r, r, 3] (`dtype`, pixel stride ld) upsampled to T x T by the same rule and added into the fp32 NCHW
+ *   accumulator acc [B, 3, T, T] (first != 0: acc is overwritten, not read); out != NULL: out = tanhf(acc) (fp32 [B, 3, T, T]).
+ *
+ * xl_normal_planes: out[b*P + p] (fp32) = a standard normal, a pure function of (seed, site, b, p).  INTEGER PART (restated on the
+ *   host bit for bit), modulo 2^32 / 2^64:  s = seed + site * 0x9E3779B97F4A7C15;  mix = lo32(s) ^ hi32(s) * 0xC2B2AE3D;
+ *   h_i = lowbias32(b * 0x9E3779B1 ^ (2p + i) * 0x85EBCA77 ^ mix), i = 0, 1 (csrc/common.h gumbel_bits).  FLOAT PART (xl_normal_from_bits
+ *   evaluates it on the caller's words):  u1 = (2 (h_0 >> 9) + 1) * 2^-24 in (0, 1), u2 = (h_1 >> 8) * 2^-24 in [0, 1), both exact;
+ *   z = sqrtf(-2 logf(u1)) * cospif(2 u2)  (Box-Muller).  |z| <= 5.77; the absolute error bound lives with the tests
+ *   (tests/generator_cases.py NORMAL_ABS). */
+#define XL_CONV_NONE  0
+#define XL_CONV_RELU  1
+#define XL_CONV_ADD   2
+#define XL_CONV_SPADE 3
+#define XL_INSTNORM_CHUNK 1024
+int xl_conv2d_nhwc(const void* x, const void* w, const float* bias, void* y, const void* aux, const float* mean, const float* rstd,
+                   const float* noise, float noise_w, float slope, int B, int H, int W, int Cin, int Cout, int ks, int groups,
+                   int ldx, int ldy, int ldaux, int epilogue, int dtype, void* stream);
+int xl_instnorm_stats(const void* x, float* mean, float* rstd, float* ws, int64_t ws_floats, int B, int HW, int C, int ld, float eps,
+                      int dtype, void* stream);
+int xl_resize_bilinear_nhwc(const void* x, void* y, int B, int Hin, int Win, int Hout, int Wout, int C, int ldx, int ldy, int dtype,
+                            void* stream);
+int xl_torgb_accum(const void* rgb, float* acc, float* out, int B, int r, int T, int ld, int first, int dtype, void* stream);
+int xl_normal_planes(float* out, uint64_t seed, int site, int B, int P, void* stream);
+int xl_normal_from_bits(const uint32_t* h0, const uint32_t* h1, float* z, int n, void* stream);
+
 /* ---------------------------------------------------------------- optimizer side (ref lxmert_pretrain.py:343-364)
  * sumsq[0] += sum g^2 over n fp32 elements.  Deterministic: block partials are added in a fixed order by the last block to
  * arrive, so every rank of a data-parallel job derives the same clip factor from the same reduced gradients (an atomic per block

@@ -1,6 +1,6 @@
 """Throughput of the scope-table 'next' rows on one MI355X (synthetic data, bf16, random-init weights):
 VQA fine-tune step (BASELINE config 3), 4-step Mask-Predict sampling (config 4), word_mask / matched pretraining steps.
-Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint|eval|match] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
+Usage: python tools/task_bench.py [--rows all|sampler|caption|inpaint|eval|match|generator] [--temperature T [--seed S]] [--top-k K] [--top-p P] [--min-p Q]
 --rows eval: the validation pass alone (bs 256): ms per Engine.evaluate_task for vis_mask (`--vis_mask_predict` masks, n ~ U{1..64}) and
 word_mask (labelled rows from the loader), on the fused path (XL_EPI_ROWSCORE records) and on the logits path (XL_FUSED_PREDICT=0),
 alternating in this process with their yardstick, Engine.task_forward(task, want_grad=False): all rows, fp32 logits.
@@ -12,6 +12,9 @@ the fused and on the logits predict path and with the visual stack recomputed ev
 match.MatchRunner.run for N = M = 16 and N = M = 32 (stacks once, cross layers per pair, ranking on the device), alternating in this
 process with the path that existed before it: the same N*M pairs materialised as rows of an ordinary engine (batches of 256),
 encoder_forward + rel_fwd.  The lines also go to --out (default profiles/match/task_bench_match.txt).
+--rows generator: the native image generator (xlxmert_amd.generator.Generator, deployed geometry: base_dim 32, 2048 -> 256 codes, 8 -> 256
+pixels, bs 64, bf16, noise on) against what a user had before it, the plain-torch statement of the same network on the same GPU (fp32, and
+under bf16 autocast), arms alternating in this process; then ImggenModel.sample_image_NAR (T = 4, bs 64) end to end with either generator.
 --temperature: the sampler rows are timed greedy AND with temperature sampling, alternating in this process (rounds of 8 loops
 each; the line gives the median and the min..max spread of both).
 --top-k / --top-p / --min-p (any of them): a third arm in the same alternation, the truncated sampler at that temperature (1 if
@@ -25,13 +28,13 @@ from xlxmert_amd.config import XLxmertConfig
 from xlxmert_amd.trainer import PretrainStep, word_rows_of
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint", "eval", "match"), default="all")
+ap.add_argument("--rows", choices=("all", "sampler", "caption", "inpaint", "eval", "match", "generator"), default="all")
 ap.add_argument("--temperature", type=float, default=None, help="also time the sampler rows drawing from softmax(logits / T)")
 ap.add_argument("--seed", type=int, default=0, help="noise seed of the temperature sampler")
 ap.add_argument("--top-k", type=int, default=None, help="truncated arm: at most K candidates (1..256)")
 ap.add_argument("--top-p", type=float, default=None, help="truncated arm: nucleus mass in (0, 1]")
 ap.add_argument("--min-p", type=float, default=None, help="truncated arm: probability floor relative to the mode, in (0, 1]")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match", "task_bench_match.txt"), help="--rows match: file the lines are written to")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match", "task_bench_match.txt"), help="--rows match / generator: file the lines are written to (generator: profiles/generator/task_bench_generator.txt)")
 ap.add_argument("--rounds", type=int, default=5, help="greedy / sampled alternations (with --temperature)")
 args = ap.parse_args()
 trunc = {k: v for k, v in (("top_k", args.top_k), ("top_p", args.top_p), ("min_p", args.min_p)) if v is not None}
@@ -287,6 +290,112 @@ def match_row(L=20, V=64):
         f.write("\n".join(lines) + "\n")
 
 
+def torch_generator(sd, cfg_g):
+    """the same network in stock PyTorch, NCHW, spectral norms folded once (eval mode): what set_image_generator took before"""
+    import math
+    import torch.nn.functional as F
+    from xlxmert_amd.generator import fold_spectral_norm, resolution_channels
+    W = {}
+    for k in sd:
+        if k.endswith(".weight_orig"):
+            p = k[:-len(".weight_orig")]
+            W[p] = fold_spectral_norm(sd[k], sd[p + ".weight_u"], sd[p + ".weight_v"]).to(dev)
+        elif k.endswith(".weight") and not k.endswith(("noise1.weight", "noise2.weight")):
+            W[k[:-len(".weight")]] = sd[k].to(dev)
+    Bi = {k[:-len(".bias")]: v.to(dev) for k, v in sd.items() if k.endswith(".bias")}
+    nw = {k: float(v) for k, v in sd.items() if k.endswith(("noise1.weight", "noise2.weight"))}
+    T, r0 = cfg_g["target_size"], cfg_g["init_H"]
+    n_up = int(math.log2(T // r0))
+
+    def conv(t, p, pad, groups=1):
+        return F.conv2d(t, W[p], Bi[p], padding=pad, groups=groups)
+
+    def spade(t, y, p, weight):
+        y = F.interpolate(y, size=t.shape[2:], mode="bilinear", align_corners=False)
+        actv = F.relu(conv(y, p + ".shared.0", 1))
+        out = F.instance_norm(t) * (1 + conv(actv, p + ".gamma", 1)) + conv(actv, p + ".beta", 1)
+        return F.leaky_relu(out + weight * torch.randn(t.shape[0], 1, t.shape[2], t.shape[3], device=t.device, dtype=t.dtype), 0.2)
+
+    def G(x):
+        emb = torch.tanh(conv(x, "bottleneck_emb.0", 0))
+        h, y = conv(emb, "learned_init_conv.0", 1, 4), conv(emb, "style_init_conv.0", 1, 4)
+        out = torch.zeros(x.shape[0], 3, T, T, device=x.device)
+        for i in range(n_up):
+            p = f"resblocks.{i}"
+            t = spade(h, y, p + ".cbn1", nw[p + ".noise1.weight"])
+            t = conv(F.interpolate(t, scale_factor=2, mode="bilinear", align_corners=False), p + ".conv1", 1)
+            t = conv(spade(t, y, p + ".cbn2", nw[p + ".noise2.weight"]), p + ".conv2", 1)
+            h = t + conv(F.interpolate(h, scale_factor=2, mode="bilinear", align_corners=False), p + ".res_branch.1", 0)
+            rgb = conv(h, f"to_RGB_blocks.{i}.conv", 1)
+            out = out + (rgb if rgb.shape[-1] == T else F.interpolate(rgb, size=(T, T), mode="bilinear", align_corners=False)).float()
+        return torch.tanh(out)
+    return G
+
+
+def generator_row(B=64, T_steps=4):
+    from xlxmert_amd.generator import Generator
+    from xlxmert_amd.modeling import ImggenModel
+    cfg_g = dict(emb_dim=2048, codebook_dim=256, base_dim=32, init_H=8, init_W=8, target_size=256, extra_layers=0)
+    native = Generator(**cfg_g, device=dev, dtype=torch.bfloat16)
+    sd = native.state_dict()
+    g = torch.Generator().manual_seed(0)
+    for k in sd:
+        if k.startswith("to_RGB_blocks") and k.endswith("conv.weight"):
+            sd[k] = sd[k] * 0.05
+        if k.endswith(("noise1.weight", "noise2.weight")):
+            sd[k] = torch.full((1,), 0.3)
+        if k.endswith(".weight_orig"):          # u = the normalised image of v: sigma = |W v| is O(1)
+            p = k[:-len(".weight_orig")]
+            sd[p + ".weight_u"] = torch.nn.functional.normalize(torch.mv(sd[k].flatten(1), sd[p + ".weight_v"]), dim=0)
+    native.load_state_dict(sd)
+    stock = torch_generator(sd, cfg_g)
+    x = torch.randn(B, 2048, 8, 8, generator=g).to(dev)
+    rows = x.permute(0, 2, 3, 1).reshape(B * 64, 2048).to(torch.bfloat16).contiguous()
+
+    def stock_bf16(t):
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return stock(t)
+    with torch.no_grad():
+        a, b_ = native(x, noise_seed=1, train=False), stock(x[:4])
+        lines = [f"image generator, deployed geometry (base_dim 32, 2048 -> 256 codes, 8 x 8 -> 256 x 256), bs {B}, noise on; "
+                 f"{args.rounds} rounds of 4 calls per arm, arms alternating in one process",
+                 f"  (sanity: native image std {float(a.std()):.3f}, stock torch image std {float(b_.std()):.3f})"]
+        arms = {"native (bf16, code rows in)": lambda: native.render_codes(rows, B), "stock torch fp32": lambda: stock(x),
+                "stock torch bf16 autocast": lambda: stock_bf16(x)}
+        runs = {k: [] for k in arms}
+        for _ in range(args.rounds):
+            for k, fn in arms.items():
+                runs[k].append(timed(fn, n=4, warm=1))
+        med = {}
+        for k, v in runs.items():
+            v = sorted(v)
+            med[k] = v[len(v) // 2]
+            lines.append(f"  {k:30s}: median {med[k] * 1e3:8.2f} ms  min {v[0] * 1e3:8.2f}  max {v[-1] * 1e3:8.2f}  {B / med[k]:8.0f} images/s")
+        n_ = med["native (bf16, code rows in)"]
+        lines.append(f"  ratio native / stock fp32: {n_ / med['stock torch fp32']:5.3f}   native / stock bf16 autocast: {n_ / med['stock torch bf16 autocast']:5.3f}")
+        # end to end: the Mask-Predict sampler (T steps) and the generator behind it
+        m = ImggenModel(cfg, args=None, num_clusters=cfg.num_clusters, dtype=torch.bfloat16, grid_size=8)
+        m.set_visual_embedding(torch.randn(cfg.num_clusters, cfg.visual_feat_dim, generator=g).relu())
+        ids = torch.randint(1000, 20000, (B, 20), generator=g).to(dev)
+        e2e = {"native": native, "stock torch fp32": stock, "stock torch bf16 autocast": stock_bf16}
+        runs = {k: [] for k in e2e}
+        for _ in range(args.rounds):
+            for k, G in e2e.items():
+                m.set_image_generator(G)
+                runs[k].append(timed(lambda: m.sample_image_NAR(ids, n_steps=T_steps), n=2, warm=1))
+        lines.append(f"sample_image_NAR end to end (T = {T_steps}, bs {B}, image on the host at the end):")
+        for k, v in runs.items():
+            v = sorted(v)
+            lines.append(f"  {k:30s}: median {v[len(v) // 2] * 1e3:8.2f} ms  min {v[0] * 1e3:8.2f}  max {v[-1] * 1e3:8.2f}")
+    print("\n".join(lines))
+    out = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "generator", "task_bench_generator.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if args.rows == "generator":
+    generator_row()
 if args.rows == "eval":
     eval_row()
 if args.rows == "match":

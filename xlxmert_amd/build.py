@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 # launches, eight-wave q tiles, the role-trading relay kernel, K split with an epilogue) and their entry points (-DXL_EXPERIMENTAL).
 EXPERIMENTAL = os.environ.get("XL_EXPERIMENTAL", "0") not in ("", "0")
 LIB = os.path.join(HERE, "libxlxmert_hip_exp.so" if EXPERIMENTAL else "libxlxmert_hip.so")
-SOURCES = ["gemm_pp.hip", "gemm_pp_nn.hip", "gemm_pp_duo.hip", "gemm_pp_res32.hip", "gemm_pp_sample.hip", "gemm_pp_score.hip", "gemm.hip", "rowops.hip", "match.hip", "sdpa.hip", "optim.hip", "plan.hip", "comm.hip"]
+SOURCES = ["gemm_pp.hip", "gemm_pp_nn.hip", "gemm_pp_duo.hip", "gemm_pp_res32.hip", "gemm_pp_sample.hip", "gemm_pp_score.hip", "gemm.hip", "rowops.hip", "match.hip", "generator.hip", "sdpa.hip", "optim.hip", "plan.hip", "comm.hip"]
 SOURCES_EXPERIMENTAL = ["gemm_pp_192.hip", "gemm_pp_persist.hip", "gemm_pp_pair.hip", "gemm_q.hip", "gemm_relay.hip"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 if EXPERIMENTAL:

@@ -895,6 +895,9 @@ class ImggenModel(XLxmertForPretraining):
         """code [B*V, F] -> G(code as [B, F, g, g]) -> denorm -> host (ref :160-165, :250-256)"""
         if self.G is None:
             raise RuntimeError("call set_image_generator(G) first (ref tasks/imggen_model.py:41)")
+        from .generator import Generator
+        if isinstance(self.G, Generator):           # the native generator takes the code rows as they are (channels last, engine dtype)
+            return self.denorm(self.G.render_codes(code, B)).cpu()
         g = self.grid_size
         x = code.view(B, g * g, -1).permute(0, 2, 1).reshape(B, -1, g, g).float()
         return self.denorm(self.G(x)).cpu()

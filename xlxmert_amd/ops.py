@@ -16,8 +16,10 @@ EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_TANH, EPI_ROWMAX, EPI_GELU_DG, 
 EPI_RESIDUAL_F32 = 8            # XL_EPI_RESIDUAL with an fp32 residual and output (the fp32 residual stream); chosen by HipOps.gemm
 EPI_ROWSAMPLE = 9               # XL_EPI_ROWMAX's sibling for temperature sampling: alpha = 1/T, bias / T, seed = the launch's noise seed
 EPI_ROWSCORE = 10               # XL_EPI_ROWMAX's sibling for validation losses: residual = int64 labels [M], the record's fourth slot = x_label
+CONV_NONE, CONV_RELU, CONV_ADD, CONV_SPADE = 0, 1, 2, 3        # xl_conv2d_nhwc epilogues
+INSTNORM_CHUNK = 1024                                           # XL_INSTNORM_CHUNK
 
-TORCH_DTYPE = {XL_F32: torch.float32, XL_BF16: torch.bfloat16}
+TORCH_DTYPE ={XL_F32: torch.float32, XL_BF16: torch.bfloat16}
 _SLAB_WS = {}
 
 
@@ -402,6 +404,41 @@ class HipOps:
         self._call("xl_match_rank", self._p(rel), int(pair_start), int(pair_count), self._p(margin), self._p(prob), N, M,
                    int(bool(rank_stage)), int(k), self._p(topk_images), self._p(topk_captions), self._p(image_of_caption),
                    self._p(caption_of_image), self._p(rank_t2i), self._p(rank_i2t), self._stream())
+
+    # -- image generator (csrc/generator.hip): NHWC activations, ld = pixel stride in elements
+    def conv2d_nhwc(self, x, w, bias, y, B, H, W, Cin, Cout, ks, groups=1, ldx=None, ldy=None, epilogue=CONV_NONE, aux=None, ldaux=0,
+                    mean=None, rstd=None, noise=None, noise_w=0.0, slope=0.2):
+        """y = epilogue(conv(x, w) + bias) -- xl_conv2d_nhwc; w in the device layout [ks*ks, Cout, Cin/groups]; CONV_SPADE: Cout = 2C
+        (gamma rows, then beta rows), y and aux have C channels, mean / rstd fp32 [B, C], noise fp32 [B, H*W] or None."""
+        Cy = Cout // 2 if epilogue == CONV_SPADE else Cout
+        self._call("xl_conv2d_nhwc", self._p(x), self._p(w), self._p(bias), self._p(y), self._p(aux), self._p(mean), self._p(rstd),
+                   self._p(noise), float(noise_w), float(slope), B, H, W, Cin, Cout, ks, groups, Cin if ldx is None else ldx,
+                   Cy if ldy is None else ldy, int(ldaux), int(epilogue), xl_dtype(x.dtype), self._stream())
+
+    def instnorm_stats(self, x, mean, rstd, ws, B, HW, C, ld, eps=1e-5):
+        """mean, rstd fp32 [B, C] over the HW pixels of x [B, HW, C] (xl_instnorm_stats); ws: fp32 workspace, instnorm_ws_floats(B, HW, C)"""
+        self._call("xl_instnorm_stats", self._p(x), self._p(mean), self._p(rstd), self._p(ws), int(ws.numel()), B, HW, C, ld, float(eps),
+                   xl_dtype(x.dtype), self._stream())
+
+    @staticmethod
+    def instnorm_ws_floats(B, HW, C):
+        return 2 * B * ((HW + INSTNORM_CHUNK - 1) // INSTNORM_CHUNK) * C
+
+    def resize_bilinear_nhwc(self, x, y, B, Hin, Win, Hout, Wout, C, ldx=None, ldy=None):
+        self._call("xl_resize_bilinear_nhwc", self._p(x), self._p(y), B, Hin, Win, Hout, Wout, C, C if ldx is None else ldx,
+                   C if ldy is None else ldy, xl_dtype(x.dtype), self._stream())
+
+    def torgb_accum(self, rgb, acc, out, B, r, T, ld=3, first=False):
+        """acc fp32 [B, 3, T, T] (+)= bilinear(rgb [B, r, r, 3] -> T x T); out (may be None) = tanh(acc) -- xl_torgb_accum"""
+        self._call("xl_torgb_accum", self._p(rgb), self._p(acc), self._p(out), B, r, T, ld, int(bool(first)), xl_dtype(rgb.dtype), self._stream())
+
+    def normal_planes(self, out, seed, site, B, P):
+        """out fp32 [B, P] = standard normals, a pure function of (seed, site, b, p) -- xl_normal_planes"""
+        self._call("xl_normal_planes", self._p(out), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), B, P, self._stream())
+
+    def normal_from_bits(self, h0, h1, z, n):
+        """test export: z[i] = the float part of xl_normal_planes on the hash words h0[i], h1[i] (int32 storage of the uint32 bits)"""
+        self._call("xl_normal_from_bits", self._p(h0), self._p(h1), self._p(z), n, self._stream())
 
     # -- attention core
     def sdpa_keep_bits_bytes(self, B, H, nq, nk, dh):
