@@ -215,9 +215,9 @@ def _check_loop(eng, snaps, sd, oc, feats, pos, lengths, prefix, T, banned, spec
     for i, s in enumerate(snaps):
         M = s["ids"].numel()
         if s["fused"]:
-            Vq = lh._emb_pad.shape[0]
-            y, _, e = BS.tempered_reference(s["hn"], lh._emb_pad, lh._bias_pad, 1.0, 0)
-            e = torch.where(lh._bias_pad[None, :] < -1e29, torch.zeros_like(e), e)
+            Vq = lh.word_pred.w_pad.shape[0]
+            y, _, e = BS.tempered_reference(s["hn"], lh.word_pred.w_pad, lh.word_pred.bias_pad, 1.0, 0)
+            e = torch.where(lh.word_pred.bias_pad[None, :] < -1e29, torch.zeros_like(e), e)
             _, n_adm = Bd.check_rowmax_rows(y, e, Vq // 64, s["p"], s["ids"], s["lse"], f"step {i} fused predict")
         else:
             y = s["logits"][:, :lh.Vn].double()                      # the kernel's own fp32 logits: exact inputs, the exact rule
@@ -322,9 +322,9 @@ def test_fused_and_logits_paths_agree_where_a_single_column_is_admissible(monkey
         s = snaps[0]
         assert s["fused"] == (fused == "1")
         lh = eng.lang_heads
-        lh._prepare_fused_predict()
-        y, _, e = BS.tempered_reference(s["hn"], lh._emb_pad, lh._bias_pad, 1.0, 0)
-        e = torch.where(lh._bias_pad[None, :] < -1e29, torch.zeros_like(e), e)
+        lh.word_pred.prepare()
+        y, _, e = BS.tempered_reference(s["hn"], lh.word_pred.w_pad, lh.word_pred.bias_pad, 1.0, 0)
+        e = torch.where(lh.word_pred.bias_pad[None, :] < -1e29, torch.zeros_like(e), e)
         n_adm = Bd.check_admissible(y, s["ids"], e.amax(-1), f"fused={fused}")
         res[fused] = (s["ids"], n_adm, s["tokens"])
     single = (res["1"][1] == 1) & (res["0"][1] == 1)

@@ -169,8 +169,8 @@ def _check_loop(eng, snaps, sd, oc, ids, init, fm, order, mode, T, grid, margin_
     for i, s in enumerate(snaps):
         M = s["ids"].numel()
         if s["fused"]:
-            Kq = eng._cent_pad.shape[0]
-            y, _, e = BS.tempered_reference(s["feat"].view(M, eng.F), eng._cent_pad, eng._bias_pad, 1.0, 0)
+            Kq = eng.code_pred.w_pad.shape[0]
+            y, _, e = BS.tempered_reference(s["feat"].view(M, eng.F), eng.code_pred.w_pad, eng.code_pred.bias_pad, 1.0, 0)
             _, n_adm = Bd.check_rowmax_rows(y, e, Kq // 64, s["p"], s["ids"], s["lse"], f"step {i} fused predict")
             assert int(s["ids"].max()) < K
         else:

@@ -122,7 +122,7 @@ def test_engine_nar_reproducible_seeded_and_greedy_unchanged():
     eng.head_forward()
     out = []
     for step in (0, 1):
-        eng._sample_step(False, 1.0, Engine.sample_launch_seed(7, step))
+        eng._predict_step(False, 1.0, Engine.sample_launch_seed(7, step))
         out.append(eng.row_argmax.clone())
     assert not torch.equal(out[0], out[1])
     # a low temperature approaches the greedy choice: at T = 1e-3 the draw is the mode wherever the mode leads by a margin

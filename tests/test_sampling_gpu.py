@@ -239,8 +239,8 @@ def _grab(eng, snaps):
 def _check_step(eng, s, T, launch_seed, what):
     """one step's ids / probability / lse on the kernel's own inputs against float64; returns the admissible counts per row"""
     if s["fused"]:
-        Kq = eng._cent_pad.shape[0]
-        y, g, e = BS.tempered_reference(s["feat"][:eng.MV].view(eng.MV, eng.F), eng._cent_pad, eng._bias_pad_T, 1.0 / T, launch_seed)
+        Kq = eng.code_pred.w_pad.shape[0]
+        y, g, e = BS.tempered_reference(s["feat"][:eng.MV].view(eng.MV, eng.F), eng.code_pred.w_pad, eng.code_pred.bias_pad_T, 1.0 / T, launch_seed)
         rows, n_adm = BS.check_rows(y, g, e, Kq // 64, s["p"], s["ids"], s["lse"], what)
         assert int(s["ids"].max()) < eng.K
     else:
@@ -277,7 +277,7 @@ def test_engine_nar_sampling_properties_and_steps_admissible(dtype):
     eng.head_forward()
     out = []
     for step in (0, 1):
-        eng._sample_step(False, T, Engine.sample_launch_seed(7, step))
+        eng._predict_step(False, T, Engine.sample_launch_seed(7, step))
         out.append(eng.row_argmax.clone())
     assert not torch.equal(out[0], out[1])
 

@@ -19,7 +19,8 @@ import os
 
 import torch
 
-from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_ROWMAX, EPI_ROWSAMPLE, EPI_ROWSCORE, EPI_TANH, GemmCall
+from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_TANH, GemmCall
+from .sampling import RowPredictor, SamplerMixin
 
 
 class _Res:
@@ -518,6 +519,9 @@ class LangHeads:
             self.rows = torch.zeros(ML, dtype=torch.int32, device=eng.dev)
             self.labels_c = torch.zeros(ML, dtype=torch.int64, device=eng.dev)
             self.n_rows = 0
+            # the tied decoder's tail for the caption sampler and the validation pass (the padded word-embedding operand is one)
+            self.word_pred = RowPredictor(eng, self.Vn, d, eng.MLc, lambda: st.cview("bert.embeddings.word_embeddings.weight"),
+                                          lambda: self.vb_ban, self.Vp, self.Vp)
         if self.has_rel:
             self.wr, self.gwr = st.cview("cls.seq_relationship.weight"), st.gview("cls.seq_relationship.weight")
             self.br, self.gbr = st.view("cls.seq_relationship.bias"), st.gview("cls.seq_relationship.bias")
@@ -600,15 +604,12 @@ class LangHeads:
             ops.gemm(dpre, self.wt, d_lang, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **e.rkw)
         return self.loss
 
-    # ---- prediction over the vocabulary (caption sampler, Engine.sample_words_nar): the word-side twin of Engine._predict_step.
-    # The head runs on the rows of the last cross layer's language output AS THEY LIE -- packed rows lang_off[b] + l (rounded up to the
-    # row tile with zero rows) or dense rows b*L + l -- and leaves per row the predicted / drawn token id, its probability and the
-    # log-sum-exp.  Banned ids are -1e30 in the decoder bias, the mechanism of the codebook's pad columns: every path below (fused,
-    # logits, truncated) excludes them without a line of kernel code.
+    # ---- prediction over the vocabulary (caption sampler, SamplerMixin.sample_words_nar): the word-side twin of the codebook head's
+    # step.  The head runs on the rows of the last cross layer's language output AS THEY LIE -- packed rows lang_off[b] + l (rounded up
+    # to the row tile with zero rows) or dense rows b*L + l -- and leaves per row the predicted / drawn token id, its probability and
+    # the log-sum-exp.  Banned ids are -1e30 in the decoder bias, the mechanism of the codebook's pad columns (sampling.RowPredictor).
     def fused_predict_available(self):
-        e = self.e
-        return (e.cdtype == torch.bfloat16 and e.ML % 256 == 0 and e.d % 8 == 0 and hasattr(e.ops, "rowmax_combine")
-                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
+        return self.word_pred.available(self.e.ML)
 
     def _prepare_predict(self, banned_ids):
         """buffers of the predict paths (row capacity MLc: a packed row count is rounded up to the row tile, which may exceed B*L)
@@ -622,8 +623,8 @@ class LangHeads:
             self.p_scores = torch.zeros(Mc, self.Vp, dtype=torch.float32, device=e.dev) if own else self.scores
             self.row_prob, self.row_lse = e.f32(Mc), e.f32(Mc)
             self.row_id = torch.zeros(Mc, dtype=torch.int32, device=e.dev)
-            self.row_kept = torch.zeros(Mc, dtype=torch.int32, device=e.dev)
             self.vb_ban = torch.zeros(self.Vp, dtype=torch.float32, device=e.dev)
+            self.word_pred.logits, self.word_pred.out = self.p_scores, (self.row_prob, self.row_id, self.row_lse)
         self.vb_ban[:self.Vn].copy_(self.vb)
         if self.Vp > self.Vn:
             self.vb_ban[self.Vn:].fill_(-1e30)
@@ -634,79 +635,22 @@ class LangHeads:
             raise ValueError("banned_ids leaves no token to predict")
         self.vb_ban[ban.to(e.dev)] = -1e30
 
-    def _prepare_fused_predict(self):
-        """after _prepare_predict: the tied word-embedding matrix as a bf16 operand padded to a multiple of 256 rows (30522 -> 30720,
-        zero rows), the banned bias padded with -1e30, the segment workspace of the row-max / row-sample epilogues"""
-        e = self.e
-        Vq = (self.Vn + 255) // 256 * 256
-        if getattr(self, "_emb_pad", None) is None:
-            self._emb_pad = torch.zeros(Vq, e.d, dtype=e.cdtype, device=e.dev)
-            self._bias_pad = torch.full((Vq,), -1e30, dtype=torch.float32, device=e.dev)
-            self._bias_pad_T = torch.empty_like(self._bias_pad)
-            self._seg_ws = torch.zeros((Vq // 64) * e.MLc * 4, dtype=torch.float32, device=e.dev)
-        self._emb_pad[:self.Vn].copy_(e.store.cview("bert.embeddings.word_embeddings.weight"))
-        self._bias_pad[:self.Vn].copy_(self.vb_ban[:self.Vn])
-
-    def _prepare_fused_sample(self, temperature):
-        """the padded bias divided by T (once per loop); banned and pad columns keep -1e30, NOT divided (Engine._prepare_fused_sample)"""
-        self._bias_pad_T.copy_(torch.where(self._bias_pad > -1e29, self._bias_pad * (1.0 / temperature), self._bias_pad))
-
     def predict(self, lang, M, fused, temperature=None, launch_seed=0, trunc=None):
         """lang: the head's input rows [M, d].  Fills row_id / row_prob / row_lse[:M]: greedy (softmax-max / argmax), a draw from
         softmax(logits / temperature), or a truncated draw (always through the logits, as on the image side)."""
-        e, d, Vn, Vp = self.e, self.e.d, self.Vn, self.Vp
-        ops, st = e.ops, e.store
+        e, d = self.e, self.e.d
+        ops = e.ops
         ops.block = "head"
         hn = self.p_hn[:M]
         ops.gemm(lang, self.wt, self.p_h[:M], self.bt, None, self.p_pre[:M], M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
         ops.layernorm_fwd(self.p_h[:M], self.g, self.b, hn, self.p_mean, self.p_rstd, M, d, 1e-12)
-        if fused and trunc is None:
-            Vq = self._emb_pad.shape[0]
-            if temperature is None:
-                ops.gemm(hn, self._emb_pad, None, self._bias_pad, None, self._seg_ws, M, Vq, d, d, d, Vq, epilogue=EPI_ROWMAX)
-                ops.rowmax_combine(self._seg_ws, Vq // 64, M, self.row_prob, self.row_id, self.row_lse)
-            else:
-                ops.gemm(hn, self._emb_pad, None, self._bias_pad_T, None, self._seg_ws, M, Vq, d, d, d, Vq, epilogue=EPI_ROWSAMPLE,
-                         alpha=1.0 / temperature, seed=launch_seed)
-                ops.rowsample_combine(self._seg_ws, Vq // 64, M, launch_seed, self.row_prob, self.row_id, self.row_lse)
-            return
-        ops.gemm(hn, st.cview("bert.embeddings.word_embeddings.weight"), self.p_scores, self.vb_ban, None, None,
-                 M, Vn, d, d, d, Vp, out_f32=True)
-        inv_T = 1.0 / (1.0 if temperature is None else temperature)
-        if trunc is not None:
-            top_k, top_p, log_min_p = trunc
-            ops.sample_rows_trunc(self.p_scores, M, Vn, Vp, inv_T, launch_seed, top_k, top_p, log_min_p, self.row_prob, self.row_id,
-                                  self.row_lse, self.row_kept)
-        elif temperature is not None:
-            ops.sample_rows(self.p_scores, M, Vn, Vp, inv_T, launch_seed, self.row_prob, self.row_id, self.row_lse)
-        else:
-            ops.ce_fwd_bwd(self.p_scores, None, None, None, None, self.row_lse, self.row_id, self.row_prob, M, Vn, Vp, Vp, 1.0)
+        self.word_pred.run(hn, M, fused, temperature, launch_seed, trunc)
 
-    # ---- validation (Engine.evaluate_task): the heads forward-only, losses and accuracies from xl_rowscore_combine / xl_score_rows
-    def fused_score_available(self, M):
-        e = self.e
-        return (e.cdtype == torch.bfloat16 and M % 256 == 0 and e.d % 8 == 0 and hasattr(e.ops, "rowscore_combine")
-                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
-
-    def _prepare_fused_score(self):
-        """the padded tied decoder of _prepare_fused_predict (30522 -> 30720 zero rows; shared with the caption sampler) and a padded
-        decoder bias of the validation pass's own: nothing is banned here, the pad columns sit at -1e30"""
-        e = self.e
-        Vq = (self.Vn + 255) // 256 * 256
-        if getattr(self, "_emb_pad", None) is None:
-            self._emb_pad = torch.zeros(Vq, e.d, dtype=e.cdtype, device=e.dev)
-            self._bias_pad = torch.full((Vq,), -1e30, dtype=torch.float32, device=e.dev)
-            self._bias_pad_T = torch.empty_like(self._bias_pad)
-            self._seg_ws = torch.zeros((Vq // 64) * e.MLc * 4, dtype=torch.float32, device=e.dev)
-        if getattr(self, "_score_bias", None) is None:
-            self._score_bias = torch.full((Vq,), -1e30, dtype=torch.float32, device=e.dev)
-        self._emb_pad[:self.Vn].copy_(e.store.cview("bert.embeddings.word_embeddings.weight"))
-        self._score_bias[:self.Vn].copy_(self.vb)
-
+    # ---- validation (Engine.evaluate_task): the head forward-only, loss and accuracy from xl_rowscore_combine / xl_score_rows
     def mlm_evaluate(self, lang, totals, row_pred):
         """MLM head on the labelled rows (set_rows) or on all rows: totals += {sum nll, labelled rows, rows predicted right}"""
-        e, d, Vn, Vp = self.e, self.e.d, self.Vn, self.Vp
-        ops, st = e.ops, e.store
+        e, d = self.e, self.e.d
+        ops = e.ops
         ops.block = "head"
         M = self.n_rows if self.n_rows else e.MLd
         x, labels = lang, self.word_labels
@@ -718,15 +662,7 @@ class LangHeads:
         hn = self.hn[:M]
         ops.gemm(x, self.wt, self.h[:M], self.bt, None, self.pre[:M], M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
         ops.layernorm_fwd(self.h[:M], self.g, self.b, hn, self.mean, self.rstd, M, d, 1e-12)
-        if self.fused_score_available(M):
-            self._prepare_fused_score()
-            Vq = self._emb_pad.shape[0]
-            ops.gemm(hn, self._emb_pad, None, self._score_bias, labels, self._seg_ws, M, Vq, d, d, d, Vq, epilogue=EPI_ROWSCORE)
-            ops.rowscore_combine(self._seg_ws, Vq // 64, M, labels, Vn, None, row_pred, None, totals)
-        else:
-            ops.gemm(hn, st.cview("bert.embeddings.word_embeddings.weight"), self.scores, self.vb, None, None,
-                     M, Vn, d, d, d, Vp, out_f32=True)
-            ops.score_rows(self.scores, M, Vn, Vp, labels, None, row_pred, None, totals)
+        self.word_pred.score(hn, M, labels, row_pred, totals, bias=self.vb, logits=self.scores)    # (nothing is banned here)
         return M
 
     # ---- matched
@@ -771,7 +707,7 @@ class LangHeads:
         return self.loss
 
 
-class Engine:
+class Engine(SamplerMixin):
     """Static-shape forward/backward program.  `need_lang`: whether lang/pooled outputs of the last cross layer are
     consumed (False for the masked-visual-token step)."""
 
@@ -943,6 +879,8 @@ class Engine:
         self.losses = self.f32(4)             # [obj_loss, feat_loss, -, -]
         self.row_lse, self.row_maxprob = self.f32(self.MV), self.f32(self.MV)
         self.row_argmax = torch.zeros(self.MV, dtype=torch.int32, device=self.dev)
+        self.code_pred = RowPredictor(self, self.K, self.F, self.MV, lambda: st.centroids_c, lambda: self.hd["bc"][0], self.K, self.Kp,
+                                      self.logits, (self.row_maxprob, self.row_argmax, self.row_lse))
         self.mrows = torch.zeros(self.MV, dtype=torch.int32, device=self.dev)         # ids b*V+v of the masked positions
         self.labels_c = torch.zeros(self.MV, dtype=torch.int64, device=self.dev)
         self.n_mrows = 0
@@ -2046,10 +1984,6 @@ class Engine:
         out[key] = tot[0:1] / tot[1:2].clamp(min=1.0)
         out[key + "_sum"], out[key + "_count"], out[key + "_correct"] = tot[0:1].clone(), tot[1:2].clone(), tot[2:3].clone()
 
-    def fused_score_available(self, M):
-        return (self.cdtype == torch.bfloat16 and M % 256 == 0 and self.F % 8 == 0 and hasattr(self.ops, "rowscore_combine")
-                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
-
     def evaluate_task(self, task, word_labels=None, word_rows=None, matched_labels=None, qa_labels=None, targets=None, labels=None,
                       feat_loss=True):
         """Forward-only losses and accuracies of one task on the batch set_inputs staged: `vis_mask`, `word_mask`, `matched`, `qa`
@@ -2135,7 +2069,7 @@ class Engine:
     def _eval_vis_head(self, out, rows, feat_loss):
         """LxmertVisualObjHead (ref lxrt/modeling.py:38-53) and both of its losses on the masked rows only (exact: the losses read
         nothing else; pad entries of the row list are zero rows with label -100) or, without a row list, on all rows"""
-        ops, d, F, K, hd = self.ops, self.d, self.F, self.K, self.hd
+        ops, d, F, hd = self.ops, self.d, self.F, self.hd
         ops.block = "head"
         M = rows[1] if rows is not None else self.MV
         vis, labels = self.vis_final, self.labels
@@ -2152,14 +2086,7 @@ class Engine:
         ops.layernorm_fwd(self.t_h, hd["gt"][0], hd["bbt"][0], self.t_y, self.t_mean, self.t_rstd, M, d, self.eps)
         ops.gemm(self.t_y, hd["wf"][0], self.feat, hd["bf"][0], None, None, M, F, d, d, d, F)
         tot, pred = self._eval_totals("obj"), self._eval_pred("obj", self.MV)[:M]        # (pred: the head's rows, in row-list order)
-        if self.fused_score_available(M):
-            self._prepare_fused_predict()
-            Kq = self._cent_pad.shape[0]
-            ops.gemm(self.feat, self._cent_pad, None, self._bias_pad, labels, self._rowmax_ws, M, Kq, F, F, F, Kq, epilogue=EPI_ROWSCORE)
-            ops.rowscore_combine(self._rowmax_ws, Kq // 64, M, labels, K, None, pred, None, tot)
-        else:
-            ops.gemm(self.feat, self.store.centroids_c, self.logits, hd["bc"][0], None, None, M, K, F, F, F, K, out_f32=True)
-            ops.score_rows(self.logits, M, K, K, labels, None, pred, None, tot)
+        self.code_pred.score(self.feat, M, labels, pred, tot)
         self._eval_out(out, "obj_loss", tot)
         if feat_loss:
             ops.zero(self.losses[1:2])
@@ -2263,383 +2190,6 @@ class Engine:
         self._ready_heads()
         self.encoder_backward(True)
         return loss
-
-    def predict_codes(self):
-        """head -> softmax -> max over the codebook (ref tasks/imggen_model.py:229-235): (max prob, argmax) per row."""
-        self.ops.ce_fwd_bwd(self.logits, None, None, None, None, self.row_lse, self.row_argmax, self.row_maxprob,
-                            self.MV, self.K, self.K, self.Kp, 1.0)
-        return self.row_maxprob, self.row_argmax
-
-    # Sampling never needs the logits themselves, only softmax(-1).max(-1): on the bf16 path the codebook contraction ends in
-    # the XL_EPI_ROWMAX epilogue (per row and 64-column segment: max, sum exp, argmax) and xl_rowmax_combine finishes the rows --
-    # 42 MB of segment records instead of writing and re-reading the 655 MB fp32 [B*V, 10000] matrix.  The codebook is padded
-    # to a multiple of 256 rows for it (zero centroids with bias -1e30: never the maximum, exp() = 0).
-    def fused_predict_available(self):
-        return (self.cdtype == torch.bfloat16 and self.MV % 256 == 0 and self.F % 8 == 0 and hasattr(self.ops, "rowmax_combine")
-                and os.environ.get("XL_FUSED_PREDICT", "1") != "0")
-
-    def _prepare_fused_predict(self):
-        Kq = (self.K + 255) // 256 * 256
-        if getattr(self, "_cent_pad", None) is None or self._cent_pad.shape[0] != Kq:
-            self._cent_pad = torch.zeros(Kq, self.F, dtype=self.cdtype, device=self.dev)
-            self._bias_pad = torch.full((Kq,), -1e30, dtype=torch.float32, device=self.dev)
-            self._bias_pad_T = None                                    # its copy divided by T: made by _prepare_fused_sample
-            self._rowmax_ws = torch.zeros((Kq // 64) * self.MV * 4, dtype=torch.float32, device=self.dev)
-        self._cent_pad[:self.K].copy_(self.store.centroids_c)          # (frozen, but set_centroids may have replaced it)
-        self._bias_pad[:self.K].copy_(self.hd["bc"][0])
-
-    def predict_codes_fused(self):
-        """head_forward(want_logits=False) must have run: self.feat -> (max prob, argmax) per row, no logits in memory."""
-        Kq = self._cent_pad.shape[0]
-        self.ops.gemm(self.feat, self._cent_pad, None, self._bias_pad, None, self._rowmax_ws, self.MV, Kq, self.F, self.F, self.F, Kq,
-                      epilogue=EPI_ROWMAX)
-        self.ops.rowmax_combine(self._rowmax_ws, Kq // 64, self.MV, self.row_maxprob, self.row_argmax, self.row_lse)
-        return self.row_maxprob, self.row_argmax
-
-    def _predict_step(self, fused, temperature=None, seed=0, trunc=None):
-        if trunc is not None:
-            self._sample_step_trunc(temperature, seed, trunc)
-        elif temperature is not None:
-            self._sample_step(fused, temperature, seed)
-        elif fused:
-            self.head_forward(want_logits=False)
-            self.predict_codes_fused()
-        else:
-            self.head_forward()
-            self.predict_codes()
-
-    # Temperature sampling: each position DRAWS its code from softmax(logits / T) instead of taking the mode -- Gumbel-max, the
-    # noise a pure function of (launch seed, global row b*V+v, code), so the fused and the unfused path draw identically.  The
-    # draw fills the buffers of the greedy step (row_argmax = the drawn code, row_maxprob = its tempered probability: the
-    # confidence of the re-masking and of the `confidence` position policy), so everything behind _predict_step is unchanged.
-    TEMPERATURE_MIN, TEMPERATURE_MAX = 1e-3, 1e3     # the range of the pad-column guarantee (include/xlxmert_hip.h XL_EPI_ROWSAMPLE)
-
-    @classmethod
-    def check_temperature(cls, temperature):
-        if temperature is None:
-            return None
-        t = float(temperature)
-        if not math.isfinite(t) or not (cls.TEMPERATURE_MIN <= t <= cls.TEMPERATURE_MAX):
-            raise ValueError(f"temperature {temperature!r}: a finite value in [{cls.TEMPERATURE_MIN}, {cls.TEMPERATURE_MAX}] "
-                             "(None = greedy)")
-        return t
-
-    @staticmethod
-    def sample_launch_seed(seed, step):
-        """noise seed of sampler step `step`: seed * 0x9E3779B97F4A7C15 + step (mod 2^64) -- distinct per step, and for the seeds
-        a caller picks (small integers, 63-bit draws) distinct across (seed, step) pairs"""
-        return (int(seed) * 0x9E3779B97F4A7C15 + int(step)) & 0xFFFFFFFFFFFFFFFF
-
-    def _prepare_fused_sample(self, temperature):
-        """after _prepare_fused_predict: the codebook bias divided by T (once per loop); pad columns keep -1e30, NOT divided"""
-        if self._bias_pad_T is None:
-            self._bias_pad_T = torch.empty_like(self._bias_pad)
-        self._bias_pad_T.copy_(self._bias_pad)
-        self._bias_pad_T[:self.K].mul_(1.0 / temperature)
-
-    def _sample_step(self, fused, temperature, launch_seed):
-        inv_T = 1.0 / temperature
-        if fused:
-            self.head_forward(want_logits=False)
-            Kq = self._cent_pad.shape[0]
-            self.ops.gemm(self.feat, self._cent_pad, None, self._bias_pad_T, None, self._rowmax_ws, self.MV, Kq, self.F, self.F, self.F,
-                          Kq, epilogue=EPI_ROWSAMPLE, alpha=inv_T, seed=launch_seed)
-            self.ops.rowsample_combine(self._rowmax_ws, Kq // 64, self.MV, launch_seed, self.row_maxprob, self.row_argmax, self.row_lse)
-        else:
-            self.head_forward()
-            self.ops.sample_rows(self.logits, self.MV, self.K, self.K, inv_T, launch_seed, self.row_maxprob, self.row_argmax,
-                                 self.row_lse)
-
-    # Truncated sampling: top-k, top-p (nucleus) and min-p next to the temperature (include/xlxmert_hip.h xl_sample_rows_trunc states
-    # the semantics).  Any of the three given: the step materialises the fp32 logits (head_forward) and draws with
-    # xl_sample_rows_trunc, for fp32 and bf16 alike -- also where the fused predict path is available: truncation needs a row's
-    # logits ranked, which the fused epilogue never has in memory.  Same noise function and launch seed as the temperature path: a
-    # truncated draw equals the untruncated one whenever that lies in the kept set.  row_maxprob stays the probability under the
-    # FULL tempered softmax (a confidence for the re-masking and the `confidence` policy); row_kept holds the kept-set sizes.
-    # top-p and min-p act within at most TRUNC_MAX_CAND = 256 candidates (row_kept == 256 reveals the cap).
-    TRUNC_MAX_CAND = 256
-
-    @classmethod
-    def check_truncation(cls, top_k, top_p, min_p):
-        """None (no truncation argument given), or (top_k, top_p, log_min_p) as xl_sample_rows_trunc takes them"""
-        if top_k is None and top_p is None and min_p is None:
-            return None
-        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not (1 <= top_k <= cls.TRUNC_MAX_CAND)):
-            raise ValueError(f"top_k {top_k!r}: an int in [1, {cls.TRUNC_MAX_CAND}] (None = {cls.TRUNC_MAX_CAND} candidates)")
-        for name, v in (("top_p", top_p), ("min_p", min_p)):
-            if v is None:
-                continue
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not (0.0 < v <= 1.0):
-                raise ValueError(f"{name} {v!r}: a finite float in (0, 1] (None = off)")
-        return (cls.TRUNC_MAX_CAND if top_k is None else top_k, 1.0 if top_p is None else float(top_p),
-                -math.inf if min_p is None else math.log(float(min_p)))
-
-    def _sample_step_trunc(self, temperature, launch_seed, trunc):
-        if getattr(self, "row_kept", None) is None:
-            self.row_kept = torch.zeros(self.MV, dtype=torch.int32, device=self.dev)
-        top_k, top_p, log_min_p = trunc
-        self.head_forward()
-        self.ops.sample_rows_trunc(self.logits, self.MV, self.K, self.K, 1.0 / (1.0 if temperature is None else temperature), launch_seed,
-                                   top_k, top_p, log_min_p, self.row_maxprob, self.row_argmax, self.row_lse, self.row_kept)
-
-    def sample_codes_nar(self, n_steps=4, on_step=None, *, temperature=None, seed=0, top_k=None, top_p=None, min_p=None):
-        """Iterative Mask-Predict sampling (ref tasks/imggen_model.py:169-243) without a host round trip between steps:
-        re-mask the lowest-confidence positions -> encoder -> codebook head -> softmax-max / argmax -> keep the predictions
-        of the masked positions.  Text inputs come from set_inputs (cluster_ids / vis_mask there are placeholders).
-        Returns (code_ids [B,V] int64, code features [B*V, F] in the compute dtype, pred_prob [B*V] fp32); the caller
-        hands `code.view(B,V,F).permute(0,2,1).view(B,F,g,g)` to the frozen GAN generator (stock PyTorch, ref :254).
-        on_step(i): called after step i's update (return_intermediate of the reference, :245-248: materialise_codes() gives the
-        code tensor of that moment).
-        temperature (None = greedy, exactly the calls above): every position draws its code from softmax(logits / temperature),
-        reproducibly for one `seed`; the confidence of the re-masking is the tempered probability of the drawn code.
-        top_k / top_p / min_p (any given: truncated sampling, temperature None meaning 1): the draw is restricted to the kept set
-        of check_truncation's comment; self.row_kept holds its sizes."""
-        temperature = self.check_temperature(temperature)
-        trunc = self.check_truncation(top_k, top_p, min_p)
-        ops, B, V = self.ops, self.B, self.V
-        st = self.store
-        self.use_codebook, self.has_vmask = True, True
-        self.cid.zero_()
-        fused = trunc is None and self.fused_predict_available()
-        if fused:
-            self._prepare_fused_predict()
-            if temperature is not None:
-                self._prepare_fused_sample(temperature)
-        for i in range(n_steps):
-            n_mask = int((n_steps - i) / n_steps * V)                      # ref :201-202 (host arithmetic on the step index)
-            if i == 0:
-                self.vmask.fill_(1)                                        # ref :204-206
-            else:
-                ops.remask_lowest(self.row_maxprob, self.vmask, B, V, n_mask)
-            self._reuse_lang_stack = i > 0                                 # the text is the same in every refinement step
-            try:
-                self.encoder_forward(want_pooled=False)                    # codebook_gather == where(mask, mask_feat, vis_emb(ids))
-            finally:
-                self._reuse_lang_stack = False
-            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i), trunc)
-            ops.sampler_update(self.row_argmax, self.vmask, self.cid, B * V)
-            if on_step is not None:
-                on_step(i)
-        ops.codebook_gather(self.cid, None, st.centroids_c, st.view("mask_feat"), self.feats, self.MV, self.F)
-        return self.cid, self.feats, self.row_maxprob
-
-    def materialise_codes(self, masked=False):
-        """the sampler's code tensor [B*V, F] (compute dtype) of this moment: centroid rows of the current code ids; masked=True
-        (autoregressive loop): `mask_feat` rows where vis_mask is still set, as the reference's `code` holds them (ref :99-102)."""
-        st = self.store
-        self.ops.codebook_gather(self.cid, self.vmask if masked else None, st.centroids_c, st.view("mask_feat"), self.feats,
-                                 self.MV, self.F)
-        return self.feats
-
-    def sample_codes_ar(self, n_steps=None, mode="confidence", positions=None, trace=None, on_step=None, *, temperature=None, seed=0,
-                        top_k=None, top_p=None, min_p=None):
-        """Autoregressive sampling (ref tasks/imggen_model.py:49-153): one grid position per image is filled per step --
-        the most confident not-yet-visited one ("confidence", the reference's default), position i ("tlbr"), or the host's
-        shuffled order popped from the end ("random", positions = that list).  Same device-resident state as
-        sample_codes_nar; `trace` (a list) receives a copy of vis_mask after every step.  temperature / seed: as in sample_codes_nar
-        (the `confidence` policy ranks positions by the tempered probability of their drawn code); top_k / top_p / min_p likewise."""
-        temperature = self.check_temperature(temperature)
-        trunc = self.check_truncation(top_k, top_p, min_p)
-        ops, B, V = self.ops, self.B, self.V
-        st = self.store
-        n_steps = V if n_steps is None else n_steps
-        self.use_codebook, self.has_vmask = True, True
-        self.cid.zero_()
-        self.vmask.fill_(1)
-        if not hasattr(self, "visited"):
-            self.visited = torch.zeros(B, V, dtype=torch.uint8, device=self.dev)
-        self.visited.zero_()
-        positions = list(positions) if positions is not None else None
-        fused = trunc is None and self.fused_predict_available()
-        if fused:
-            self._prepare_fused_predict()
-            if temperature is not None:
-                self._prepare_fused_sample(temperature)
-        for i in range(n_steps):
-            cur = -1
-            if mode == "random":
-                cur = positions.pop() % V
-                self.vmask[:, cur] = 1                                     # ref :104-108 (re-visits beyond V steps)
-            elif mode == "tlbr":
-                cur = i
-            self._reuse_lang_stack = i > 0
-            try:
-                self.encoder_forward(want_pooled=False)
-            finally:
-                self._reuse_lang_stack = False
-            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i), trunc)
-            ops.sampler_ar_update(self.row_maxprob, self.row_argmax, self.visited, self.vmask, self.cid, B, V, cur)
-            if trace is not None:
-                trace.append(self.vmask.clone())
-            if on_step is not None:
-                on_step(i)
-        ops.codebook_gather(self.cid, self.vmask, st.centroids_c, st.view("mask_feat"), self.feats, self.MV, self.F)
-        return self.cid, self.feats, self.row_maxprob
-
-    # ------------------------------------------------------------ in-painting (the image loops with part of the grid given)
-    GRID_MODES = {"nar": 0, "confidence": 1, "tlbr": 2, "order": 2}     # XL_GRID_NAR / XL_GRID_AR_CONF / XL_GRID_AR_ORDER
-
-    def inpaint_codes(self, init_codes, free_mask, n_steps=4, mode="nar", order=None, on_step=None, *, temperature=None, seed=0,
-                      top_k=None, top_p=None, min_p=None):
-        """Sample the FREE cells of the grid around given codes (include/xlxmert_hip.h xl_grid_step states the rules; DESIGN.md "N2
-        notes"), without a host round trip between steps.  set_inputs has staged the text as for sample_codes_nar.
-        init_codes [B, V] int: the codes of the given cells (whatever the free cells hold is ignored); a host tensor / sequence is
-        range-checked against [0, K) at the given cells, a device tensor is clamped into it.  free_mask [B, V]: non-zero = sampled;
-        rows may have any number of free cells, none included (such a row comes back untouched, score 0).
-        mode "nar": Mask-Predict over the free cells, n_steps refinement steps with the per-row integer schedule.  "confidence" /
-        "tlbr" / "order": one free cell per image per step -- the most confident one, raster order, or ascending `order` [B, V] (int,
-        e.g. a permutation per image); n_steps=None = the largest free count of the batch (one host read before the loop), fewer
-        leave cells masked (mask_feat in the returned features, as in sample_codes_ar).
-        temperature / seed / top_k / top_p / min_p: as in sample_codes_nar -- the same predict paths, launch seeds and noise rows
-        b*V + v, so with every cell free the loop reproduces sample_codes_nar / sample_codes_ar bit for bit.
-        Returns (code_ids [B, V] int64, code features [B*V, F], score [B] fp32: mean log-probability of the sampled cells, conf [B, V]
-        fp32: the probability each sampled cell was last predicted / filled with); on_step(i) is called after step i's update."""
-        temperature = self.check_temperature(temperature)
-        trunc = self.check_truncation(top_k, top_p, min_p)
-        ops, B, V = self.ops, self.B, self.V
-        st = self.store
-        if mode not in self.GRID_MODES:
-            raise ValueError(f"mode {mode!r}: one of {sorted(self.GRID_MODES)}")
-        gmode = self.GRID_MODES[mode]
-        if V > 64:
-            raise ValueError(f"inpaint_codes: {V} grid cells > 64 (xl_grid_step: one lane per cell)")
-        host_codes = not (isinstance(init_codes, torch.Tensor) and init_codes.device.type != "cpu")
-        init_codes, free_mask = torch.as_tensor(init_codes), torch.as_tensor(free_mask)
-        if tuple(init_codes.shape) != (B, V) or init_codes.is_floating_point() or init_codes.dtype == torch.bool:
-            raise ValueError(f"init_codes: int codes of shape [B = {B}, V = {V}] (got {init_codes.dtype} {tuple(init_codes.shape)})")
-        if tuple(free_mask.shape) != (B, V):
-            raise ValueError(f"free_mask: shape [B = {B}, V = {V}] (got {tuple(free_mask.shape)})")
-        if (order is not None) != (mode == "order"):
-            raise ValueError(f"order: needed by mode 'order' and by no other (mode {mode!r})")
-        if order is not None:
-            order = torch.as_tensor(order)
-            if tuple(order.shape) != (B, V) or order.is_floating_point() or order.dtype == torch.bool:
-                raise ValueError(f"order: ints of shape [B = {B}, V = {V}] (got {order.dtype} {tuple(order.shape)})")
-        free = free_mask != 0
-        if host_codes and bool((~free.cpu() & ((init_codes < 0) | (init_codes >= self.K))).any()):
-            raise ValueError(f"init_codes: a given cell holds a code outside [0, {self.K})")
-        if n_steps is None:
-            n_steps = int(free.sum(1).max())                               # the one host read, before the loop
-        T = int(n_steps)
-        if T < (1 if gmode == 0 else 0):
-            raise ValueError(f"n_steps {n_steps!r}: at least 1")
-        if getattr(self, "grid_free", None) is None:
-            self.grid_free = torch.zeros(B, V, dtype=torch.uint8, device=self.dev)
-            self.grid_conf, self.grid_score = self.f32(B, V), self.f32(B)
-            self.grid_order = torch.zeros(B, V, dtype=torch.int32, device=self.dev)
-        self.use_codebook, self.has_vmask = True, True
-        self.grid_free.copy_(free)
-        self.cid.copy_(init_codes)
-        self.cid.clamp_(0, self.K - 1).masked_fill_(self.grid_free != 0, 0)   # free cells start from code 0, as sample_codes_nar's do
-        self.vmask.copy_(self.grid_free)                                    # step 0: every free cell masked
-        self.grid_conf.zero_()
-        self.grid_score.zero_()
-        if order is not None:
-            self.grid_order.copy_(order)
-        fused = trunc is None and self.fused_predict_available()
-        if fused:
-            self._prepare_fused_predict()
-            if temperature is not None:
-                self._prepare_fused_sample(temperature)
-        for i in range(T):
-            self._reuse_lang_stack = i > 0                                 # the text is the same in every step
-            try:
-                self.encoder_forward(want_pooled=False)
-            finally:
-                self._reuse_lang_stack = False
-            self._predict_step(fused, temperature, self.sample_launch_seed(seed, i), trunc)
-            ops.grid_step(self.row_maxprob, self.row_argmax, self.grid_free, self.grid_order if order is not None else None, self.cid,
-                          self.vmask, self.grid_conf, self.grid_score, B, V, gmode, i, T)
-            if on_step is not None:
-                on_step(i)
-        ops.codebook_gather(self.cid, None if gmode == 0 else self.vmask, st.centroids_c, st.view("mask_feat"), self.feats, self.MV,
-                            self.F)
-        return self.cid, self.feats, self.grid_score, self.grid_conf
-
-    # ------------------------------------------------------------ caption sampler (Mask-Predict over the MLM head)
-    CAPTION_MAX_L = 64              # xl_caption_step: one lane per token position
-    reuse_vis_stack = True          # False: every step recomputes the visual stack (A/B of the saving, tools/task_bench.py)
-
-    def sample_words_nar(self, lengths, n_steps=10, prefix_len=0, on_step=None, *, temperature=None, seed=0, top_k=None, top_p=None,
-                         min_p=None, suppress_repeats=False, mask_token_id=103, banned_ids=None):
-        """Mask-Predict caption decoding, the word-side twin of sample_codes_nar (include/xlxmert_hip.h xl_caption_step states the
-        rules; DESIGN.md "N2 notes"), without a host round trip between steps.  set_inputs has staged the visual side (real grid
-        features or un-masked cluster ids) and the token layout: row b = [CLS], prefix_len prefix ids, lengths[b] free positions
-        (whatever they hold: the loop feeds mask_token_id there), [SEP], [PAD]; attention_mask = l < prefix_len + lengths[b] + 2.
-        lengths: an int, or ints [B] (a host sequence / CPU tensor is range-checked here: 1 <= n <= L - 2 - prefix_len; a device
-        tensor cannot be without a round trip and is clamped by the kernel).  banned_ids: token ids that are never predicted
-        (default: every id below 999, the specials of bert-base-uncased).  temperature / seed / top_k / top_p / min_p: as in
-        sample_codes_nar; the noise row of position (b, l) is its row in the head's input matrix, b*L + l dense and loff[b] + l packed,
-        so one seed reproduces a run bit for bit for one batch and packing.  Steps after the first reuse the visual stack.
-        Returns (tokens [B, L] int64, score [B] fp32: mean log-probability of the free tokens under the last forward, conf [B, L] fp32:
-        the last forward's confidences); on_step(i) is called after step i's update."""
-        temperature = self.check_temperature(temperature)
-        trunc = self.check_truncation(top_k, top_p, min_p)
-        ops, B, L = self.ops, self.B, self.L
-        lh = self.lang_heads
-        if lh is None or not lh.has_mlm or not self.need_lang:
-            raise RuntimeError("sample_words_nar needs the MLM head: a store with task 'word_mask' or 'all' (cls.predictions.*) and an "
-                               "engine built with need_lang=True")
-        if getattr(self, "embeds_mode", False):
-            raise ValueError("sample_words_nar feeds token ids: set_inputs(input_ids=...), not inputs_embeds")
-        P, T = int(prefix_len), int(n_steps)
-        if L > self.CAPTION_MAX_L:
-            raise ValueError(f"caption sampler: text length {L} > {self.CAPTION_MAX_L}")
-        if P < 0 or L - 2 - P < 1:
-            raise ValueError(f"prefix_len {prefix_len!r}: need 0 <= prefix_len <= L - 3 = {L - 3}")
-        if T < 1:
-            raise ValueError(f"n_steps {n_steps!r}: at least 1")
-        if not (isinstance(lengths, torch.Tensor) and lengths.device.type != "cpu"):
-            lens = torch.as_tensor(lengths).reshape(-1)
-            if lens.is_floating_point() or lens.dtype == torch.bool:
-                raise ValueError(f"lengths {lengths!r}: an int or ints [B]")
-            lens = lens.to(torch.int64)
-            if lens.numel() == 1:
-                lens = lens.expand(B)
-            if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > L - 2 - P:
-                raise ValueError(f"lengths {lengths!r}: an int or ints [B = {B}] with 1 <= n <= L - 2 - prefix_len = {L - 2 - P}")
-        else:
-            lens = lengths.reshape(-1)
-            if lens.numel() != B:
-                raise ValueError(f"lengths: {lens.numel()} entries for a batch of {B}")
-        if getattr(self, "cap_len", None) is None:
-            self.cap_len = torch.zeros(B, dtype=torch.int32, device=self.dev)
-            self.cap_tokens = torch.zeros(B, L, dtype=torch.int64, device=self.dev)
-            self.word_mask = torch.zeros(B, L, dtype=torch.uint8, device=self.dev)
-            self.cap_conf, self.cap_score = self.f32(B, L), self.f32(B)
-            self._cap_pos = torch.arange(L, dtype=torch.int32, device=self.dev).view(1, L)
-        self.cap_len.copy_(lens, non_blocking=True)
-        if banned_ids is None:
-            banned_ids = torch.arange(min(999, self.cfg.vocab_size - 1))
-        lh._prepare_predict(banned_ids)
-        packed = self.packed
-        # step 0's state, by the host (sample_codes_nar: vmask.fill_(1)): every free position masked, tokens = the layout with [MASK] there
-        free = (self._cap_pos > P) & (self._cap_pos < P + 1 + self.cap_len.view(B, 1))
-        self.word_mask.copy_(free)
-        self.ids.masked_fill_(free, int(mask_token_id))
-        self.cap_tokens.copy_(self.ids)
-        self.cap_conf.zero_()
-        self._packed_head = packed
-        try:
-            fused = trunc is None and lh.fused_predict_available()
-            if fused:
-                lh._prepare_fused_predict()
-                if temperature is not None:
-                    lh._prepare_fused_sample(temperature)
-            for i in range(T):
-                self._reuse_vis_stack = i > 0 and self.reuse_vis_stack          # the picture is the same in every step
-                try:
-                    self.encoder_forward(want_pooled=False)
-                finally:
-                    self._reuse_vis_stack = False
-                lh.predict(self.lang_final, self.ML, fused, temperature, self.sample_launch_seed(seed, i), trunc)
-                ops.caption_step(lh.row_prob, lh.row_id, self.loff if packed else None, self.cap_len, self.cap_tokens, self.ids,
-                                 self.word_mask, self.cap_conf, self.cap_score, B, L, P, i, T, int(mask_token_id), suppress_repeats)
-                if on_step is not None:
-                    on_step(i)
-        finally:
-            self._packed_head = False
-        return self.cap_tokens, self.cap_score, self.cap_conf
 
     # ------------------------------------------------------------ backward
     def zero_accumulated_grads(self):
