@@ -711,7 +711,7 @@ def test_gradient_accumulation_update_freq():
         seeds.append(tr.engine._seed)
     # every micro-batch of the window draws its own dropout masks (the reference runs a fresh forward per minibatch): the step
     # part of the seeds follows the forward counter, not the update counter
-    assert seeds == [0, 1, 2] and tr.micro == 3 and tr.state() == {"t": 1, "micro": 3}
+    assert seeds == [0, 1, 2] and tr.micro == 3 and tr.state() == {"t": 1, "micro": 3, "step_dev": 1}
     gs = [oracle_grads(cfg, sd, b)[0] for b in batches[:3]]
     names = sorted(gs[0])
     total = [gs[0][k] + gs[1][k] + gs[2][k] for k in names]

@@ -383,6 +383,11 @@ class ParamStore:
                 if k in sd:
                     self.set_centroids(sd[k])
                     break
+        # the master copy is whole again (a sharded bf16-gather step leaves the matrices current on their owner only): parameters
+        # may be exported and sync_compute_weights() casts them.  A load that misses tensors leaves their old, possibly stale,
+        # values in place: the guard stays up then.
+        if not missing:
+            self.master_partial = False
         if strict and missing:
             raise KeyError(f"missing keys: {missing[:8]}...")
         return missing

@@ -308,6 +308,7 @@ class PretrainStep:
             st.centroids_c.copy_(st.centroids)
         self.t = int(self.step_dev.item())
         self.micro = max(self.micro, self.t)
+        st.master_partial = False                # (rank 0's whole master copy is on every rank now)
         self.engine.sync_compute_weights()
 
     def verify_replicas(self):
@@ -652,11 +653,27 @@ class PretrainStep:
         return s
 
     def state(self):
-        """host-side counters a resumed run needs next to the ParamStore buffers (parameters, Adam moments, step_dev)"""
-        return {"t": self.t, "micro": self.micro}
+        """the trainer's own part of what a resumed run needs: the host counters `t` and `micro` (the dropout seeds derive from
+        `micro`), the device-side update counter `step_dev` (the schedule and the bias corrections read it; an int) and, with
+        task="all", `chunk_steps` (the per-tensor update counts; a CPU int32 tensor).  Synchronises with the device.
+        The caller saves next to it: store.master, store.exp_avg, store.exp_avg_sq and the codebook (store.centroids, which is
+        not part of `master`).  To resume: copy the three buffers back in place, set_centroids(codebook), load_state(state),
+        then engine.sync_compute_weights()."""
+        self.sync()
+        out = {"t": self.t, "micro": self.micro, "step_dev": int(self.step_dev.item())}
+        if self.chunk_steps is not None:
+            out["chunk_steps"] = self.chunk_steps.detach().to("cpu", torch.int32).clone()
+        return out
 
     def load_state(self, st):
+        """counterpart of state().  The device buffers are written in place (recorded launch plans hold their addresses); keys
+        that are absent -- a dict of `t` and `micro` alone, as older checkpoints hold -- leave them as they are."""
         self.t, self.micro = int(st["t"]), int(st.get("micro", st["t"]))
+        if st.get("step_dev") is not None:
+            self.step_dev.fill_(int(st["step_dev"]))
+        if st.get("chunk_steps") is not None:
+            assert self.chunk_steps is not None, "chunk_steps belongs to a task='all' trainer"
+            self.chunk_steps.copy_(torch.as_tensor(st["chunk_steps"]).to(self.chunk_steps.device, torch.int32))
 
     @staticmethod
     def _mark_consumed(batch):
@@ -695,6 +712,7 @@ class PretrainStep:
             plan.run()
             HipOps.forget_binding()             # (the replay ends in whichever context its last recorded bind named)
             self.t += 1
+            self._arm_partial_master()          # (a replay runs no Python of the recorded body: the guard is armed here)
             return eng.losses
         if not self._plan_warm:
             self._plan_warm = True
@@ -719,7 +737,16 @@ class PretrainStep:
             for lo, hi in sorted(eng.overwritten - eng.written_now):
                 self.ops.zero(self.store.grad[lo:hi])
             eng.written_now = set()
+        self._arm_partial_master()
         self._optimizer_launches()
+
+    def _arm_partial_master(self):
+        """sharded exchange with gather="bf16": from this update on the fp32 master copy of the MATRICES is current on the owning
+        rank only -- the store refuses to export parameters (named_state) and the engine keeps its compute copy
+        (sync_compute_weights) until gather_state().  Armed on the host path EVERY update takes, eager or replayed: a launch plan
+        re-executes the recorded C-ABI calls only, never the Python of the body it was recorded from."""
+        if self.gather_bf16 and self.world > 1:
+            self.store.master_partial = True
 
     # ---- sharded optimizer (collective="rs+ag"): shard-local norm + one scalar all-reduce, AdamW over this rank's shards,
     # all-gather of the updated compute weights slice by slice in the order the next forward needs them
@@ -781,9 +808,7 @@ class PretrainStep:
         # the same bytes on the wire as the all-reduce's second half, and every rank's master weights stay whole.
         bf16_wire = self.gather_bf16
         if bf16_wire and W > 1:
-            # from here on the fp32 master copy of the MATRICES is current on the owning rank only: the store refuses to export
-            # parameters (named_state) and the engine keeps its compute copy (sync_compute_weights) until gather_state() -- ADVICE r5
-            st.master_partial = True
+            st.master_partial = True        # (_arm_partial_master has set it already: kept beside the launches it is about)
         for i in reversed(range(len(self._segments))):          # last-finished slice first: feature encoder, embeddings, layer 0 ...
             kind, lo, hi = self._segments[i]
             a, b = owned[i]
