@@ -28,14 +28,6 @@ def _hipcc():
     raise RuntimeError("hipcc not found: cannot build libxlxmert_hip.so")
 
 
-def needs_build():
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "xlxmert_hip.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
 def build_library(force=False, verbose=True):
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build", "exp" if EXPERIMENTAL else "default")

@@ -1,6 +1,6 @@
 """Model-side configuration of the path: the LxmertConfig fields the reference reads (HFcfg:72-101) plus the
 ad-hoc attributes its wrappers set (`num_clusters`, `clustering`; ref lxrt/modeling.py:64-65)."""
-from dataclasses import asdict, dataclass
+from dataclasses import dataclass
 
 
 @dataclass
@@ -42,9 +42,6 @@ class XLxmertConfig:
     @property
     def head_dim(self):
         return self.hidden_size // self.num_attention_heads
-
-    def to_dict(self):
-        return asdict(self)
 
     def __post_init__(self):
         if self.hidden_size % self.num_attention_heads != 0:

@@ -5,6 +5,9 @@ The engine owns a static activation plan for one (B, L, V) batch geometry and ru
 masked-visual-token losses (ref :237-290) as explicit kernel sequences -- forward and hand-derived backward --
 through an `ops` object (xlxmert_amd.ops.HipOps).  No autograd graph, no per-op allocation.
 
+This module: the activation plan, row layout, streams, scratch generations, weight-gradient schedule, inputs and the encoder's
+forward / backward.  Sub-blocks: blocks.py; heads: heads.py; task programs: tasks.TaskMixin; sampler loops: sampling.SamplerMixin.
+
 Layout decisions (MI355X-first):
   * language rows (B*L) and visual rows (B*V) of the cross-modality layers live in ONE [B*L + B*V, d] buffer:
     the bidirectional cross-attention uses one set of weights for both directions (HF:386-397), so its QKV
@@ -19,46 +22,11 @@ import os
 
 import torch
 
-from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_DG, EPI_MULAUX, EPI_NONE, EPI_RESIDUAL, EPI_TANH, GemmCall
+from .blocks import CrossAttBlock, FFNBlock, SelfAttBlock, _f, _h, _Res      # noqa: F401  (_f / _h: read from here by callers)
+from .heads import AnswerHead, HeadTransform, LangHeads, RowSubset          # noqa: F401  (LangHeads: likewise)
+from .ops import EPI_RESIDUAL, EPI_TANH
 from .sampling import RowPredictor, SamplerMixin
-
-
-class _Res:
-    """A residual-stream value of the fp32-stream mode (Engine residual_dtype="fp32"): `f` the fp32 value that travels along
-    the residual path, `h` its bf16 rounding, which the contractions read as their operand.  Row slices keep the pair."""
-    __slots__ = ("f", "h")
-
-    def __init__(self, f, h):
-        self.f, self.h = f, h
-
-    def __getitem__(self, s):
-        return _Res(self.f[s], self.h[s])
-
-
-def _h(x):
-    """what a contraction reads of a stream value (the tensor itself in the bf16-stream mode)"""
-    return x.h if isinstance(x, _Res) else x
-
-
-def _f(x):
-    """what the residual path reads of a stream value"""
-    return x.f if isinstance(x, _Res) else x
-
-
-class _Att:
-    """LxmertAttention + LxmertAttentionOutput parameters (fused q/k/v views)."""
-
-    def __init__(self, eng, prefix, self_name):
-        st = eng.store
-        qkv_w = [f"{prefix}.{self_name}.{n}.weight" for n in ("query", "key", "value")]
-        qkv_b = [f"{prefix}.{self_name}.{n}.bias" for n in ("query", "key", "value")]
-        self.wqkv, self.gwqkv = st.fused(qkv_w, st.compute), st.fused(qkv_w, st.grad)
-        self.bqkv, self.gbqkv = st.fused(qkv_b, st.master), st.fused(qkv_b, st.grad)
-        o = f"{prefix}.output"
-        self.wo, self.gwo = st.cview(o + ".dense.weight"), st.gview(o + ".dense.weight")
-        self.bo, self.gbo = st.view(o + ".dense.bias"), st.gview(o + ".dense.bias")
-        self.g, self.gg = st.view(o + ".LayerNorm.weight"), st.gview(o + ".LayerNorm.weight")
-        self.b, self.gb = st.view(o + ".LayerNorm.bias"), st.gview(o + ".LayerNorm.bias")
+from .tasks import TaskMixin
 
 
 _RESERVED_STREAMS = {}
@@ -98,616 +66,7 @@ def comm_stream(device):
     return _RESERVED_STREAMS[key][3]
 
 
-class SelfAttBlock:
-    """LxmertSelfAttentionLayer (HF:304-316): y = LN(dense(attn(x,x,mask)) + x).  `masked` = language rows (key padding mask, or
-    -- packed language rows -- per-example row offsets instead: engine.Engine pack_lang)."""
-
-    def __init__(self, eng, prefix, n_tok, masked, tag):
-        self.e, self.n, self.masked, self.tag = eng, n_tok, masked, tag
-        self.p = _Att(eng, prefix, "self")
-        Mc = eng.MLc if masked else eng.MV          # row capacity (the active row count of a packed language side varies per batch)
-        d = eng.d
-        self.qkv = eng.act(Mc, 3 * d)
-        self.ctx = eng.act(Mc, d)
-        self.z = eng.zact(Mc, d)
-        self.lse = eng.f32(eng.B * eng.H * n_tok)
-        self.keep = eng.keep_bits(n_tok, n_tok)
-        self.mean, self.rstd = eng.f32(Mc), eng.f32(Mc)
-        self.site = eng.new_site(2)
-
-    @property
-    def M(self):
-        return self.e.ML if self.masked else self.e.MV
-
-    def _att_args(self):
-        """(key mask, packed-row keyword arguments) of this block's attention core"""
-        e = self.e
-        if not self.masked:
-            return e.vkmask, {}
-        if e.packed:
-            return None, dict(q_off=e.loff, k_off=e.loff, q_pad=e.ML, k_pad=e.ML)
-        return e.kmask, {}
-
-    def fwd(self, x, y):
-        self.e.run_steps(self.fwd_steps(x, y))
-
-    def fwd_steps(self, x, y):
-        """the forward as a generator: every dense contraction is YIELDED (ops.GemmCall) instead of launched, everything else is
-        issued as the generator advances -- Engine.run_steps launches each yielded call, Engine.run_pair advances a visual and a
-        language block of this class in lock step and launches their contractions two at a time (xl_gemm_pair)."""
-        e, p, d, M = self.e, self.p, self.e.d, self.M
-        ops, tag = e.ops, self.tag
-        qkv, ctx, z = self.qkv[:M], self.ctx[:M], self.z[:M]
-        yield GemmCall(_h(x), p.wqkv, qkv, p.bqkv, None, None, M, 3 * d, d, d, d, 3 * d, tag=tag)
-        km, vl = self._att_args()
-        ops.block = tag
-        ops.sdpa_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], km, ctx, self.lse, e.B, e.H, self.n, self.n,
-                     e.dh, 3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site), keep_bits=e.kb(self.keep), **vl)
-        yield GemmCall(ctx, p.wo, z, p.bo, _f(x), None, M, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
-                       p_drop=e.p_hid, seed=e.seed(self.site + 1), tag=tag, **e.rkw)
-        ops.block = tag
-        e.ln_fwd(z, p.g, p.b, y, self.mean, self.rstd, M, d)
-        self.x = x
-
-    def probs(self):
-        """attention probabilities [B, H, n, n] fp32 of the last forward (after dropout, as HF returns them)"""
-        e, d, M = self.e, self.e.d, self.M
-        qkv = self.qkv[:M]
-        out = torch.zeros(e.B, e.H, self.n, self.n, dtype=torch.float32, device=e.dev)
-        km, vl = self._att_args()
-        vl = {k: v for k, v in vl.items() if k in ("q_off", "k_off")}
-        e.ops.attn_probs(qkv, qkv[:, d:], km, self.lse, out, e.B, e.H, self.n, self.n, e.dh, 3 * d, 3 * d, e.scale, e.p_attn,
-                         e.seed(self.site), **vl)
-        return out
-
-    def bwd(self, dy, dx):
-        self.e.run_steps(self.bwd_steps(dy, dx))
-
-    def bwd_steps(self, dy, dx):
-        e, p, d, M = self.e, self.p, self.e.d, self.M
-        ops, tag = e.ops, self.tag
-        ops.block = tag
-        e.wgrad_sync()                  # the previous block's weight-gradient GEMMs still read the shared scratch
-        qkv, ctx, z = self.qkv[:M], self.ctx[:M], self.z[:M]
-        dz = e.tmp("dz", M, d, res=True)
-        dzm = e.ln_bwd_dense(dy, z, p.g, self.mean, self.rstd, dz, p.gg, p.gb, p.gbo, M, d, self.site + 1)
-        e.wgrad_defer(dzm, ctx, p.gwo, d, d, M, d, d, d)
-        dctx = e.tmp("dctx", M, d)
-        yield GemmCall(dzm, p.wo, dctx, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, tag=tag)
-        dqkv = e.tmp("dqkv", M, 3 * d)
-        km, vl = self._att_args()
-        ops.block = tag
-        ops.sdpa_bwd(qkv, qkv[:, d:], qkv[:, 2 * d:], km, dctx, self.lse, dqkv, dqkv[:, d:],
-                     dqkv[:, 2 * d:], e.B, e.H, self.n, self.n, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d,
-                     e.scale, e.p_attn, e.seed(self.site), bias_grad=p.gbqkv, ws=e.ws, keep_bits=e.kb(self.keep), **vl)      # + d(b_q | b_k | b_v)
-        e.wgrad_defer(dqkv, _h(self.x), p.gwqkv, 3 * d, d, M, 3 * d, d, d)
-        e.wgrad_flush(pair=True)        # this layer's four weight gradients: launched together with the next layer's
-        yield GemmCall(dqkv, p.wqkv, dx, None, dz, None, M, d, 3 * d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                       epilogue=EPI_RESIDUAL, tag=tag, **e.rkw)
-
-
-class FFNBlock:
-    """LxmertIntermediate + LxmertOutput (HF:325-342): y = LN(W2 gelu(W1 x + b1) + b2 + x).  `lang`: language rows (their
-    active count follows the batch when the language rows are packed)."""
-
-    def __init__(self, eng, p_inter, p_out, lang, tag):
-        self.e, self.lang, self.tag = eng, lang, tag
-        st = eng.store
-        self.w1, self.gw1 = st.cview(p_inter + ".dense.weight"), st.gview(p_inter + ".dense.weight")
-        self.b1, self.gb1 = st.view(p_inter + ".dense.bias"), st.gview(p_inter + ".dense.bias")
-        self.w2, self.gw2 = st.cview(p_out + ".dense.weight"), st.gview(p_out + ".dense.weight")
-        self.b2, self.gb2 = st.view(p_out + ".dense.bias"), st.gview(p_out + ".dense.bias")
-        self.g, self.gg = st.view(p_out + ".LayerNorm.weight"), st.gview(p_out + ".LayerNorm.weight")
-        self.b, self.gb = st.view(p_out + ".LayerNorm.bias"), st.gview(p_out + ".LayerNorm.bias")
-        d, dff = eng.d, eng.dff
-        Mc = eng.MLc if lang else eng.MV
-        self.pre = eng.act(Mc, dff)
-        self.h = eng.act(Mc, dff)
-        self.z = eng.zact(Mc, d)
-        self.mean, self.rstd = eng.f32(Mc), eng.f32(Mc)
-        self.site = eng.new_site(1)
-        self.rows = None                # row count of a forward on a row SUBSET (Engine: the last cross layer's visual side
-                                        # on the masked rows only); None = all rows of the side
-
-    @property
-    def M(self):
-        if self.rows is not None:
-            return self.rows
-        return self.e.ML if self.lang else self.e.MV
-
-    def fwd(self, x, y):
-        self.e.run_steps(self.fwd_steps(x, y))
-
-    def fwd_steps(self, x, y):
-        """(a generator of the block's dense contractions: see SelfAttBlock.fwd_steps)"""
-        e, d, dff, M = self.e, self.e.d, self.e.dff, self.M
-        ops, tag = e.ops, self.tag
-        pre, h, z = self.pre[:M], self.h[:M], self.z[:M]
-        # self.pre holds gelu'(pre-activation): erf and exp(-x^2/2) are in registers in the forward epilogue anyway, and the
-        # backward epilogue becomes a multiply (no second erf + exp per element of the [M, dff] gradient)
-        yield GemmCall(_h(x), self.w1, h, self.b1, None, pre, M, dff, d, d, d, dff, ldx=dff, epilogue=EPI_GELU_DG, tag=tag)
-        yield GemmCall(h, self.w2, z, self.b2, _f(x), None, M, d, dff, dff, dff, d, ldr=d, epilogue=EPI_RESIDUAL,
-                       p_drop=e.p_hid, seed=e.seed(self.site), tag=tag, **e.rkw)
-        ops.block = tag
-        e.ln_fwd(z, self.g, self.b, y, self.mean, self.rstd, M, d)
-        self.x = x
-
-    def bwd(self, dy, dx):
-        self.e.run_steps(self.bwd_steps(dy, dx))
-
-    def bwd_steps(self, dy, dx):
-        e, d, dff, M = self.e, self.e.d, self.e.dff, self.M
-        ops, tag = e.ops, self.tag
-        ops.block = tag
-        e.wgrad_sync()
-        pre, h, z = self.pre[:M], self.h[:M], self.z[:M]
-        # own scratch names: the two weight gradients registered here are launched together with the attention block's
-        # (which runs next on this stream and flushes), so dz / dzm / dpre must outlive that block's scratch use
-        dz = e.tmp("f_dz", M, d, res=True)
-        dzm = e.ln_bwd_dense(dy, z, self.g, self.mean, self.rstd, dz, self.gg, self.gb, self.gb2, M, d, self.site,
-                             tmp_name="f_dzm")
-        e.wgrad_defer(dzm, h, self.gw2, d, dff, M, d, dff, dff)
-        dpre = e.tmp("dpre", M, dff)
-        yield GemmCall(dzm, self.w2, dpre, None, None, pre, M, dff, d, d, dff, dff, ldx=dff, a_kmajor=1, b_kmajor=0,
-                       epilogue=EPI_MULAUX, colsum=self.gb1, ws=e.ws_gemm, tag=tag)      # d(b1) = column sums of dpre, in the same epilogue
-        e.wgrad_defer(dpre, _h(self.x), self.gw1, dff, d, M, dff, d, d)
-        yield GemmCall(dpre, self.w1, dx, None, dz, None, M, d, dff, dff, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                       epilogue=EPI_RESIDUAL, tag=tag, **e.rkw)
-
-
-class CrossAttBlock:
-    """LxmertXLayer.cross_att (HF:377-398): ONE LxmertCrossAttentionLayer applied in both directions on the
-    pre-update inputs.  Rows = [visual (B*V) ; language (ML)] -- the visual rows first, so that the language rows, whose count
-    follows the batch when they are packed (Engine pack_lang), are the tail of every buffer."""
-
-    def __init__(self, eng, prefix, need_lang, tag, need_vis=True):
-        """need_lang / need_vis: whether the language / visual rows of the OUTPUT are consumed.  The last cross layer of a
-        masked-visual-token step needs only the visual side, the one of the pooled-output / language tasks (VQA, word_mask,
-        matched) only the language side: the other direction of the attention, its output projection and LayerNorm are
-        skipped (their parameters get no gradient in the reference either)."""
-        assert need_lang or need_vis
-        self.e, self.need_lang, self.need_vis, self.tag = eng, need_lang, need_vis, tag
-        self.p = _Att(eng, prefix, "att")
-        d = eng.d
-        self.qkv = eng.act(eng.MXc, 3 * d)
-        self.ctx = eng.act(eng.MXc, d)
-        self.z = eng.zact(eng.MXc, d)
-        self.lse_l = eng.f32(eng.B * eng.H * eng.L)
-        self.lse_v = eng.f32(eng.B * eng.H * eng.V)
-        self.keep_l, self.keep_v = eng.keep_bits(eng.L, eng.V), eng.keep_bits(eng.V, eng.L)
-        self.mean, self.rstd = eng.f32(eng.MXc), eng.f32(eng.MXc)
-        self.site = eng.new_site(3)
-
-    def _lq(self):
-        """packed-row arguments of the attention with LANGUAGE queries over visual keys"""
-        e = self.e
-        return dict(q_off=e.loff, q_pad=e.ML) if e.packed else {}
-
-    def _lk(self):
-        """(key mask, packed-row arguments) of the attention with visual queries over LANGUAGE keys"""
-        e = self.e
-        return (None, dict(k_off=e.loff, k_pad=e.ML)) if e.packed else (e.kmask, {})
-
-    def fwd(self, X, Y):
-        e, p, d = self.e, self.p, self.e.d
-        ops, ML, MV, MX = e.ops, e.ML, e.MV, e.MX
-        ops.block = self.tag
-        L_, V_ = e.lr, e.vr
-        qkv_l, qkv_v = L_(self.qkv), V_(self.qkv)
-        Xh, Xf = _h(X), _f(X)           # (fp32 stream: the contractions read the bf16 copy, the residual epilogue the fp32 value)
-        if not self.need_vis:
-            ops.gemm(L_(Xh), p.wqkv, qkv_l, p.bqkv, None, None, ML, d, d, d, d, 3 * d)                    # Q of language rows
-            ops.gemm(V_(Xh), p.wqkv[d:], qkv_v[:, d:], p.bqkv[d:], None, None, MV, 2 * d, d, d, d, 3 * d)  # K,V of visual rows
-            ops.sdpa_fwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, L_(self.ctx), self.lse_l, e.B, e.H, e.L, e.V, e.dh,
-                         3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site), keep_bits=e.kb(self.keep_l), **self._lq())
-            ops.gemm(L_(self.ctx), p.wo, L_(self.z), p.bo, L_(Xf), None, ML, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
-                     p_drop=e.p_hid, seed=e.seed(self.site + 2), **e.rkw)
-            e.ln_fwd(L_(self.z), p.g, p.b, L_(Y), L_(self.mean), L_(self.rstd), ML, d)
-            self.X = X
-            return
-        if self.need_lang:
-            ops.gemm(Xh[:MX], p.wqkv, self.qkv[:MX], p.bqkv, None, None, MX, 3 * d, d, d, d, 3 * d)
-            # language queries over visual keys/values (no mask: visual_attention_mask is None in every caller)
-            ops.sdpa_fwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, L_(self.ctx), self.lse_l, e.B, e.H, e.L, e.V, e.dh,
-                         3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site), keep_bits=e.kb(self.keep_l), **self._lq())
-        else:
-            ops.gemm(V_(Xh), p.wqkv, qkv_v, p.bqkv, None, None, MV, d, d, d, d, 3 * d)                    # Q of visual rows
-            ops.gemm(L_(Xh), p.wqkv[d:], qkv_l[:, d:], p.bqkv[d:], None, None, ML, 2 * d, d, d, d, 3 * d)  # K,V of language rows
-        # visual queries over language keys/values, padded language keys excluded
-        km, vl = self._lk()
-        ops.sdpa_fwd(qkv_v, qkv_l[:, d:], qkv_l[:, 2 * d:], km, V_(self.ctx), self.lse_v, e.B, e.H, e.V, e.L, e.dh,
-                     3 * d, 3 * d, 3 * d, d, e.scale, e.p_attn, e.seed(self.site + 1), keep_bits=e.kb(self.keep_v), **vl)
-        M = MX if self.need_lang else MV           # rows [0, M): visual rows, then (both directions) the language rows
-        ops.gemm(self.ctx[:M], p.wo, self.z[:M], p.bo, Xf[:M], None, M, d, d, d, d, d, ldr=d, epilogue=EPI_RESIDUAL,
-                 p_drop=e.p_hid, seed=e.seed(self.site + 2), **e.rkw)
-        e.ln_fwd(self.z[:M], p.g, p.b, Y[:M], self.mean[:M], self.rstd[:M], M, d)
-        self.X = X
-
-    def probs(self):
-        """cross-attention probabilities of the LANGUAGE queries over the visual keys, [B, H, L, V] fp32 -- what
-        LxmertXLayer.forward hands out as its attention output (HF:417-449: `attention_probs = lang_att_output[1:]`)"""
-        e, d = self.e, self.e.d
-        assert self.need_lang, "this cross layer skipped its language direction (dead-branch elimination)"
-        qkv_l, qkv_v = e.lr(self.qkv), e.vr(self.qkv)
-        out = torch.zeros(e.B, e.H, e.L, e.V, dtype=torch.float32, device=e.dev)
-        vl = {k: v for k, v in self._lq().items() if k == "q_off"}
-        e.ops.attn_probs(qkv_l, qkv_v[:, d:], e.vkmask, self.lse_l, out, e.B, e.H, e.L, e.V, e.dh, 3 * d, 3 * d, e.scale, e.p_attn,
-                         e.seed(self.site), **vl)
-        return out
-
-    def bwd(self, dY, dX):
-        e, p, d = self.e, self.p, self.e.d
-        ops, ML, MV, MX = e.ops, e.ML, e.MV, e.MX
-        ops.block = self.tag
-        e.wgrad_sync()
-        if not self.need_vis:
-            return self._bwd_lang_only(dY, dX)
-        L_, V_ = e.lr, e.vr
-        M = MX if self.need_lang else MV
-        dz_full = e.tmp("dz", MX, d, res=True)
-        dz = dz_full[:M]
-        dzm = e.ln_bwd_dense(dY[:M], self.z[:M], p.g, self.mean[:M], self.rstd[:M], dz, p.gg, p.gb, p.gbo, M, d,
-                             self.site + 2)
-        e.wgrad_defer(dzm, self.ctx[:M], p.gwo, d, d, M, d, d, d)
-        dctx_full = e.tmp("dctx", MX, d)
-        dctx = dctx_full[:M]
-        ops.gemm(dzm, p.wo, dctx, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0)
-        dqkv = e.tmp("dqkv", MX, 3 * d)
-        dqkv_l, dqkv_v = L_(dqkv), V_(dqkv)
-        qkv_l, qkv_v = L_(self.qkv), V_(self.qkv)
-        km, vl = self._lk()
-        ops.sdpa_bwd(qkv_v, qkv_l[:, d:], qkv_l[:, 2 * d:], km, V_(dctx_full), self.lse_v, dqkv_v, dqkv_l[:, d:],
-                     dqkv_l[:, 2 * d:], e.B, e.H, e.V, e.L, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d, e.scale,
-                     e.p_attn, e.seed(self.site + 1), bias_grad=p.gbqkv, ws=e.ws, keep_bits=e.kb(self.keep_v), **vl)
-        X = _h(self.X)
-        if self.need_lang:
-            ops.sdpa_bwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, L_(dctx_full), self.lse_l, dqkv_l, dqkv_v[:, d:],
-                         dqkv_v[:, 2 * d:], e.B, e.H, e.L, e.V, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d, e.scale,
-                         e.p_attn, e.seed(self.site), bias_grad=p.gbqkv, ws=e.ws, keep_bits=e.kb(self.keep_l), **self._lq())      # both directions share the projections
-            e.wgrad_defer(dqkv, X[:MX], p.gwqkv, 3 * d, d, MX, 3 * d, d, d)
-            e.wgrad_flush()
-            ops.gemm(dqkv, p.wqkv, dX[:MX], None, dz_full, None, MX, d, 3 * d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                     epilogue=EPI_RESIDUAL, **e.rkw)
-        else:
-            e.wgrad_defer(dqkv_v, V_(X), p.gwqkv, d, d, MV, 3 * d, d, d)
-            e.wgrad_defer(dqkv_l[:, d:], L_(X), p.gwqkv[d:], 2 * d, d, ML, 3 * d, d, d)
-            e.wgrad_flush()
-            ops.gemm(dqkv_v, p.wqkv, V_(dX), None, dz, None, MV, d, d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0,
-                     epilogue=EPI_RESIDUAL, **e.rkw)
-            e.gemm_dx_plain(dqkv_l[:, d:], p.wqkv[d:], L_(dX), ML, d, 2 * d, 3 * d, d)
-
-    def _bwd_lang_only(self, dY, dX):
-        e, p, d = self.e, self.p, self.e.d
-        ops, ML, MV, MX = e.ops, e.ML, e.MV, e.MX
-        L_, V_ = e.lr, e.vr
-        X = _h(self.X)
-        dz = L_(e.tmp("dz", MX, d, res=True))
-        dzm = e.ln_bwd_dense(L_(dY), L_(self.z), p.g, L_(self.mean), L_(self.rstd), dz, p.gg, p.gb, p.gbo, ML, d, self.site + 2)
-        e.wgrad_defer(dzm, L_(self.ctx), p.gwo, d, d, ML, d, d, d)
-        dctx = L_(e.tmp("dctx", MX, d))
-        ops.gemm(dzm, p.wo, dctx, None, None, None, ML, d, d, d, d, d, a_kmajor=1, b_kmajor=0)
-        dqkv = e.tmp("dqkv", MX, 3 * d)
-        dqkv_l, dqkv_v = L_(dqkv), V_(dqkv)
-        qkv_l, qkv_v = L_(self.qkv), V_(self.qkv)
-        ops.sdpa_bwd(qkv_l, qkv_v[:, d:], qkv_v[:, 2 * d:], e.vkmask, dctx, self.lse_l, dqkv_l, dqkv_v[:, d:], dqkv_v[:, 2 * d:],
-                     e.B, e.H, e.L, e.V, e.dh, 3 * d, 3 * d, 3 * d, d, 3 * d, 3 * d, 3 * d, e.scale, e.p_attn, e.seed(self.site),
-                     bias_grad=p.gbqkv, ws=e.ws, keep_bits=e.kb(self.keep_l), **self._lq())
-        e.wgrad_defer(dqkv_l, L_(X), p.gwqkv, d, d, ML, 3 * d, d, d)
-        e.wgrad_defer(dqkv_v[:, d:], V_(X), p.gwqkv[d:], 2 * d, d, MV, 3 * d, d, d)
-        e.wgrad_flush()
-        ops.gemm(dqkv_l, p.wqkv, L_(dX), None, dz, None, ML, d, d, 3 * d, d, d, ldr=d, a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL,
-                 **e.rkw)
-        e.gemm_dx_plain(dqkv_v[:, d:], p.wqkv[d:], V_(dX), MV, d, 2 * d, 3 * d, d)
-
-
-class AnswerHead:
-    """LxmertVisualAnswerHead on pooled_output (HF:602-614: Linear(d,2d) -> GeLU -> LayerNorm(2d) -> Linear(2d,A)) with
-    BCEWithLogitsLoss on soft targets -- the VQA/GQA fine-tune step (ref tasks/vqa_model.py:22-72, vqa.py:166-187)."""
-
-    def __init__(self, eng, num_answers, pair=False):
-        self.e, self.A, self.pair = eng, num_answers, pair
-        st, d = eng.store, eng.d
-        # pair head (NLVR2, ref tasks/nlvr2_model.py:80-86): pooled_output [2P, d] of the flattened (statement, image) rows is
-        # read as [P, 2d] -- a view of the same contiguous buffer -- by a head whose first Linear is (2d, 2d)
-        assert not pair or eng.B % 2 == 0, "the pair head needs an even number of encoder rows (two images per statement)"
-        B = self.Bh = eng.B // 2 if pair else eng.B
-        self.din = 2 * d if pair else d
-        p = "answer_head.logit_fc"
-        self.w0, self.gw0 = st.cview(p + ".0.weight"), st.gview(p + ".0.weight")
-        self.b0, self.gb0 = st.view(p + ".0.bias"), st.gview(p + ".0.bias")
-        self.g, self.gg = st.view(p + ".2.weight"), st.gview(p + ".2.weight")
-        self.b, self.gb = st.view(p + ".2.bias"), st.gview(p + ".2.bias")
-        self.w3, self.gw3 = st.cview(p + ".3.weight"), st.gview(p + ".3.weight")
-        self.b3, self.gb3 = st.view(p + ".3.bias"), st.gview(p + ".3.bias")
-        self.Ap = (num_answers + 7) // 8 * 8
-        self.pre, self.h, self.hn = eng.act(B, 2 * d), eng.act(B, 2 * d), eng.act(B, 2 * d)
-        self.mean, self.rstd = eng.f32(B), eng.f32(B)
-        self.logit = torch.zeros(B, num_answers, dtype=torch.float32, device=eng.dev)
-        self.targets = torch.zeros(B, num_answers, dtype=torch.float32, device=eng.dev)
-        self.dlogit = eng.act(B, self.Ap)
-        self.dhn, self.dh, self.dpre = eng.act(B, 2 * d), eng.act(B, 2 * d), eng.act(B, 2 * d)
-        self.dpooled, self.dz = eng.act(eng.B, d), eng.act(eng.B, d)
-        self.loss = eng.f32(1)
-        # pretraining QA branch (ref lxrt/modeling.py:292-304): CrossEntropyLoss over one answer id per example (-100 = none)
-        self.labels = torch.full((B,), -100, dtype=torch.int64, device=eng.dev)
-        self.counts, self._ones, self._nm = eng.f32(4), torch.ones(B, dtype=torch.uint8, device=eng.dev), eng.f32(B)
-        self.row_argmax = torch.zeros(B, dtype=torch.int32, device=eng.dev)
-        self.row_lse, self.row_maxprob = eng.f32(B), eng.f32(B)
-
-    def fwd(self, pooled):
-        e, d, B, A, din = self.e, self.e.d, self.Bh, self.A, self.din
-        ops = e.ops
-        pooled = pooled.view(B, din)
-        ops.gemm(pooled, self.w0, self.h, self.b0, None, self.pre, B, 2 * d, din, din, din, 2 * d, ldx=2 * d, epilogue=EPI_GELU)
-        ops.layernorm_fwd(self.h, self.g, self.b, self.hn, self.mean, self.rstd, B, 2 * d, 1e-12)
-        ops.gemm(self.hn, self.w3, self.logit, self.b3, None, None, B, A, 2 * d, 2 * d, 2 * d, A, out_f32=True)
-        return self.logit
-
-    def loss_fwd_bwd(self, want_grad=True):
-        B, A = self.Bh, self.A
-        self.e.ops.zero(self.loss)
-        self.e.ops.bce_logits_fwd_bwd(self.logit, self.targets, self.dlogit if want_grad else None, self.loss, B, A, A, A, self.Ap)
-        return self.loss
-
-    def ce_loss_fwd_bwd(self, want_grad=True):
-        """qa_loss = CrossEntropyLoss()(answer_score, qa_labels) (ref lxrt/modeling.py:295-298; ignore_index -100) and its
-        d(logit); also records qa_pred = argmax (ref :300)."""
-        B, A = self.Bh, self.A
-        ops = self.e.ops
-        ops.zero(self.loss)
-        ops.mask_counts(self.labels, self._ones, self.counts, self._nm, B, 1)          # counts[0] = #labels != -100
-        if want_grad and self.Ap > A:
-            ops.zero(self.dlogit)                                                      # pad columns
-        ops.ce_fwd_bwd(self.logit, self.labels, self.counts, self.dlogit if want_grad else None, self.loss, self.row_lse,
-                       self.row_argmax, self.row_maxprob, B, A, A, self.Ap, 1.0)
-        return self.loss
-
-    def bwd(self, pooled, cls_rows, d_cls, accumulate=False):
-        """consumes dlogit; accumulates the head's and the pooler's parameter gradients; writes (or, accumulate=True, adds)
-        d(lang_output[:, 0]) into d_cls (a [B, d] view with row stride L*d)."""
-        self.bwd_to_pooled(pooled)
-        self.e.pooler_backward(self.dpooled, self.dz, cls_rows, d_cls, accumulate=accumulate)
-
-    def bwd_to_pooled(self, pooled):
-        """consumes dlogit; accumulates the head's parameter gradients; leaves d(pooled_output) in self.dpooled."""
-        e, d, B, A, Ap, din = self.e, self.e.d, self.Bh, self.A, self.Ap, self.din
-        ops, st = e.ops, e.store
-        pooled, dpooled = pooled.view(B, din), self.dpooled.view(B, din)
-        ops.colsum(self.dlogit, self.gb3_pad(), B, Ap, Ap, ws=e.ws_wide("answer", Ap))      # pad columns of dlogit are zero
-        e.wgrad_defer(self.dlogit, self.hn, self.gw3, A, 2 * d, B, Ap, 2 * d, 2 * d)
-        ops.gemm(self.dlogit, self.w3, self.dhn, None, None, None, B, 2 * d, A, Ap, 2 * d, 2 * d, a_kmajor=1, b_kmajor=0)
-        ops.layernorm_bwd(self.dhn, self.h, self.g, self.mean, self.rstd, self.dh, self.gg, self.gb, None, B, 2 * d, ws=e.ws)
-        ops.gelu_bwd(self.dh, self.pre, self.dpre, B * 2 * d)
-        ops.colsum(self.dpre, self.gb0, B, 2 * d, 2 * d, ws=e.ws)
-        e.wgrad_defer(self.dpre, pooled, self.gw0, 2 * d, din, B, 2 * d, din, din)
-        ops.gemm(self.dpre, self.w0, dpooled, None, None, None, B, din, 2 * d, 2 * d, din, din, a_kmajor=1, b_kmajor=0)
-
-    def gb3_pad(self):
-        """bias-gradient view padded to the 8-column granule of dlogit (the bias unit is padded in the flat buffer)."""
-        m = self.e.store.index["answer_head.logit_fc.3.bias"]
-        return self.e.store.grad[m.offset:m.offset + self.Ap]
-
-
-class LangHeads:
-    """LxmertPreTrainingHeads (HF:589-657) for the `word_mask` and `matched` pretraining branches (ref lxrt/modeling.py:
-    211-235): MLM = decoder(LN(gelu(dense(lang)))) + bias with the decoder TIED to the word-embedding matrix, vocab-way CE
-    over the masked tokens; matched = seq_relationship(pooled_output), 2-way CE."""
-
-    def __init__(self, eng):
-        self.e = eng
-        st, d, ML, B = eng.store, eng.d, eng.MLd, eng.B
-        self.has_mlm = "cls.predictions.bias" in st.index and eng.task in ("word_mask", "all")
-        self.has_rel = "cls.seq_relationship.weight" in st.index and eng.task in ("matched", "all")
-        self.loss = eng.f32(2)                  # [lm_loss, matched_loss]
-        self.counts, self.dummy, self.rel_counts = eng.f32(4), eng.f32(B), eng.f32(4)
-        if self.has_mlm:
-            t = "cls.predictions.transform"
-            self.wt, self.gwt = st.cview(t + ".dense.weight"), st.gview(t + ".dense.weight")
-            self.bt, self.gbt = st.view(t + ".dense.bias"), st.gview(t + ".dense.bias")
-            self.g, self.gg = st.view(t + ".LayerNorm.weight"), st.gview(t + ".LayerNorm.weight")
-            self.b, self.gb = st.view(t + ".LayerNorm.bias"), st.gview(t + ".LayerNorm.bias")
-            self.vb = st.view("cls.predictions.bias")
-            self.Vn = eng.cfg.vocab_size
-            self.Vp = (self.Vn + 7) // 8 * 8
-            self.pre, self.h, self.hn = eng.act(ML, d), eng.act(ML, d), eng.act(ML, d)
-            self.mean, self.rstd = eng.f32(ML), eng.f32(ML)
-            self.scores = torch.zeros(ML, self.Vp, dtype=torch.float32, device=eng.dev)       # row stride padded to 8
-            self.dscores = eng.act(ML, self.Vp)
-            self.word_labels = torch.full((B, eng.L), -100, dtype=torch.int64, device=eng.dev)
-            # masked-row mode (training step, row list from the data loader): the 30522-way decoder, its loss and their
-            # backward run on the labelled rows only - exact, the loss reads nothing else (same idea as Engine._hrows)
-            self.rows = torch.zeros(ML, dtype=torch.int32, device=eng.dev)
-            self.labels_c = torch.zeros(ML, dtype=torch.int64, device=eng.dev)
-            self.n_rows = 0
-            # the tied decoder's tail for the caption sampler and the validation pass (the padded word-embedding operand is one)
-            self.word_pred = RowPredictor(eng, self.Vn, d, eng.MLc, lambda: st.cview("bert.embeddings.word_embeddings.weight"),
-                                          lambda: self.vb_ban, self.Vp, self.Vp)
-        if self.has_rel:
-            self.wr, self.gwr = st.cview("cls.seq_relationship.weight"), st.gview("cls.seq_relationship.weight")
-            self.br, self.gbr = st.view("cls.seq_relationship.bias"), st.gview("cls.seq_relationship.bias")
-            self.rel = torch.zeros(B, 8, dtype=torch.float32, device=eng.dev)                # 2 columns used
-            self.drel = eng.act(B, 8)
-            self.matched_labels = torch.zeros(B, dtype=torch.int64, device=eng.dev)
-            self.dpooled, self.dz = eng.act(B, d), eng.act(B, d)
-
-    def _gvb_pad(self):
-        m = self.e.store.index["cls.predictions.bias"]
-        return self.e.store.grad[m.offset:m.offset + self.Vp]
-
-    # ---- word_mask
-    def set_rows(self, word_rows):
-        """word_rows: flat indices b*L+l of the labelled positions (host tensor / list: its length is the launch size), or None."""
-        self.n_rows = 0
-        if word_rows is not None and 0 < len(word_rows) < self.e.MLd:
-            idx = torch.as_tensor(word_rows, dtype=torch.int64)
-            n = int(idx.numel())
-            self.n_rows = self.e.pad_rows(self.rows, idx, n, self.e.MLd)
-
-    def mlm_fwd(self, lang):
-        e, d = self.e, self.e.d
-        ops, st = e.ops, e.store
-        M = self.n_rows if self.n_rows else e.MLd
-        if self.n_rows:
-            self.x = e.tmp("mlm_x", e.MLd, d)[:M]
-            ops.gather_rows(lang, self.rows, self.x, M, d, d, d)
-        else:
-            self.x = lang
-        ops.gemm(self.x, self.wt, self.h, self.bt, None, self.pre, M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
-        ops.layernorm_fwd(self.h, self.g, self.b, self.hn, self.mean, self.rstd, M, d, 1e-12)
-        ops.gemm(self.hn, st.cview("bert.embeddings.word_embeddings.weight"), self.scores, self.vb, None, None,
-                 M, self.Vn, d, d, d, self.Vp, out_f32=True)
-        return self.scores
-
-    def mlm_loss_bwd(self, d_lang):
-        """CE over the masked tokens (labels -100 ignored) + backward down to d(language_output) (written to d_lang, which
-        the caller has zeroed)."""
-        self.mlm_loss()
-        return self.mlm_bwd(d_lang)
-
-    def mlm_loss(self):
-        """lm_loss and d(scores) (nothing of the parameter gradients is touched)."""
-        e, Vn, Vp = self.e, self.Vn, self.Vp
-        ops = e.ops
-        M = self.n_rows if self.n_rows else e.MLd
-        ops.zero(self.loss[0:1])
-        ops.mask_counts(self.word_labels, e.kmask, self.counts, self.dummy, e.B, e.L)
-        labels = self.word_labels
-        if self.n_rows:
-            labels = self.labels_c[:M]
-            ops.gather_labels(self.word_labels, self.rows, labels, M)
-        ops.ce_fwd_bwd(self.scores, labels, self.counts, self.dscores, self.loss[0:], None, None, None,
-                       M, Vn, Vp, Vp, 1.0)
-        return self.loss
-
-    def mlm_bwd(self, d_lang):
-        e, d, Vn, Vp = self.e, self.e.d, self.Vn, self.Vp
-        ops, st = e.ops, e.store
-        M = self.n_rows if self.n_rows else e.MLd
-        emb = "bert.embeddings.word_embeddings.weight"
-        ops.colsum(self.dscores, self._gvb_pad(), M, Vp, Vp, ws=e.ws_wide("mlm", Vp))
-        e.wgrad_defer(self.dscores, self.hn, st.gview(emb), Vn, d, M, Vp, d, d, once=False)  # tied decoder: d(word embeddings) also
-                                                                                            # receives the embedding scatter-add
-        dhn = e.tmp("dctx", e.MLd, d)
-        ops.gemm(self.dscores, st.cview(emb), dhn, None, None, None, M, d, Vn, Vp, d, d, a_kmajor=1, b_kmajor=0)
-        dh = e.tmp("dz", e.MLd, d)
-        ops.layernorm_bwd(dhn, self.h, self.g, self.mean, self.rstd, dh, self.gg, self.gb, None, M, d, ws=e.ws)
-        dpre = e.tmp("dzm", e.MLd, d)
-        ops.gelu_bwd(dh, self.pre, dpre, M * d)
-        ops.colsum(dpre, self.gbt, M, d, d, ws=e.ws)
-        e.wgrad_defer(dpre, self.x, self.gwt, d, d, M, d, d, d)
-        e.wgrad_flush()
-        if self.n_rows:
-            dx = e.tmp("mlm_dx", e.MLd, d, res=True)[:M]      # (fp32 stream: the heads' gradients enter it in fp32)
-            ops.gemm(dpre, self.wt, dx, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **e.rkw)
-            ops.scatter_rows(dx, self.rows, d_lang, M, d, d, d)
-        else:
-            ops.gemm(dpre, self.wt, d_lang, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **e.rkw)
-        return self.loss
-
-    # ---- prediction over the vocabulary (caption sampler, SamplerMixin.sample_words_nar): the word-side twin of the codebook head's
-    # step.  The head runs on the rows of the last cross layer's language output AS THEY LIE -- packed rows lang_off[b] + l (rounded up
-    # to the row tile with zero rows) or dense rows b*L + l -- and leaves per row the predicted / drawn token id, its probability and
-    # the log-sum-exp.  Banned ids are -1e30 in the decoder bias, the mechanism of the codebook's pad columns (sampling.RowPredictor).
-    def fused_predict_available(self):
-        return self.word_pred.available(self.e.ML)
-
-    def _prepare_predict(self, banned_ids):
-        """buffers of the predict paths (row capacity MLc: a packed row count is rounded up to the row tile, which may exceed B*L)
-        and the decoder bias with the banned ids at -1e30"""
-        e, d = self.e, self.e.d
-        Mc = e.MLc
-        if getattr(self, "p_hn", None) is None:
-            own = Mc > e.MLd
-            self.p_pre, self.p_h, self.p_hn = (e.act(Mc, d) for _ in range(3)) if own else (self.pre, self.h, self.hn)
-            self.p_mean, self.p_rstd = (e.f32(Mc), e.f32(Mc)) if own else (self.mean, self.rstd)
-            self.p_scores = torch.zeros(Mc, self.Vp, dtype=torch.float32, device=e.dev) if own else self.scores
-            self.row_prob, self.row_lse = e.f32(Mc), e.f32(Mc)
-            self.row_id = torch.zeros(Mc, dtype=torch.int32, device=e.dev)
-            self.vb_ban = torch.zeros(self.Vp, dtype=torch.float32, device=e.dev)
-            self.word_pred.logits, self.word_pred.out = self.p_scores, (self.row_prob, self.row_id, self.row_lse)
-        self.vb_ban[:self.Vn].copy_(self.vb)
-        if self.Vp > self.Vn:
-            self.vb_ban[self.Vn:].fill_(-1e30)
-        ban = torch.as_tensor(banned_ids, dtype=torch.int64).reshape(-1)
-        if ban.numel() and (int(ban.min()) < 0 or int(ban.max()) >= self.Vn):
-            raise ValueError(f"banned_ids outside the vocabulary [0, {self.Vn})")
-        if ban.numel() >= self.Vn or ban.unique().numel() >= self.Vn:
-            raise ValueError("banned_ids leaves no token to predict")
-        self.vb_ban[ban.to(e.dev)] = -1e30
-
-    def predict(self, lang, M, fused, temperature=None, launch_seed=0, trunc=None):
-        """lang: the head's input rows [M, d].  Fills row_id / row_prob / row_lse[:M]: greedy (softmax-max / argmax), a draw from
-        softmax(logits / temperature), or a truncated draw (always through the logits, as on the image side)."""
-        e, d = self.e, self.e.d
-        ops = e.ops
-        ops.block = "head"
-        hn = self.p_hn[:M]
-        ops.gemm(lang, self.wt, self.p_h[:M], self.bt, None, self.p_pre[:M], M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
-        ops.layernorm_fwd(self.p_h[:M], self.g, self.b, hn, self.p_mean, self.p_rstd, M, d, 1e-12)
-        self.word_pred.run(hn, M, fused, temperature, launch_seed, trunc)
-
-    # ---- validation (Engine.evaluate_task): the head forward-only, loss and accuracy from xl_rowscore_combine / xl_score_rows
-    def mlm_evaluate(self, lang, totals, row_pred):
-        """MLM head on the labelled rows (set_rows) or on all rows: totals += {sum nll, labelled rows, rows predicted right}"""
-        e, d = self.e, self.e.d
-        ops = e.ops
-        ops.block = "head"
-        M = self.n_rows if self.n_rows else e.MLd
-        x, labels = lang, self.word_labels
-        if self.n_rows:
-            x = e.eval_buf("mlm_x", e.MLd, d)[:M]              # (not the backward scratch of mlm_fwd)
-            ops.gather_rows(lang, self.rows, x, M, d, d, d)
-            labels = self.labels_c[:M]
-            ops.gather_labels(self.word_labels, self.rows, labels, M)
-        hn = self.hn[:M]
-        ops.gemm(x, self.wt, self.h[:M], self.bt, None, self.pre[:M], M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
-        ops.layernorm_fwd(self.h[:M], self.g, self.b, hn, self.mean, self.rstd, M, d, 1e-12)
-        self.word_pred.score(hn, M, labels, row_pred, totals, bias=self.vb, logits=self.scores)    # (nothing is banned here)
-        return M
-
-    # ---- matched
-    def rel_fwd(self, pooled):
-        e, d, B = self.e, self.e.d, self.e.B
-        e.ops.gemm(pooled, self.wr, self.rel, self.br, None, None, B, 2, d, d, d, 8, out_f32=True)
-        return self.rel
-
-    def rel_loss_bwd(self, pooled, cls_rows, d_cls, extra_dpooled=None):
-        self.rel_loss()
-        return self.rel_bwd(pooled, cls_rows, d_cls, extra_dpooled)
-
-    def rel_loss(self):
-        e, B = self.e, self.e.B
-        e.ops.zero(self.loss[1:2])
-        self.rel_counts.fill_(float(B))                                 # every example carries a matched label
-        e.ops.ce_fwd_bwd(self.rel, self.matched_labels, self.rel_counts, self.drel, self.loss[1:], None, None, None, B, 2, 8, 8, 1.0)
-        return self.loss
-
-    def rel_bwd(self, pooled, cls_rows, d_cls, extra_dpooled=None):
-        e, d, B = self.e, self.e.d, self.e.B
-        ops = e.ops
-        # the two output rows of seq_relationship: tiny contractions, done on the 8-column padded gradient
-        g8 = torch.zeros(8, d, dtype=torch.float32, device=e.dev) if not hasattr(self, "_g8") else self._g8
-        self._g8 = g8
-        g8.zero_()
-        ops.gemm(self.drel, pooled, g8, None, None, None, 8, d, B, 8, d, d, a_kmajor=0, b_kmajor=0, out_f32=True)
-        self.gwr.add_(g8[:2])
-        gb8 = torch.zeros(8, dtype=torch.float32, device=e.dev) if not hasattr(self, "_gb8") else self._gb8
-        self._gb8 = gb8
-        gb8.zero_()
-        ops.colsum(self.drel, gb8, B, 8, 8, ws=e.ws)
-        e.flush_reductions()                     # consumed right away
-        self.gbr.add_(gb8[:2])
-        w8 = torch.zeros(8, d, dtype=e.cdtype, device=e.dev) if not hasattr(self, "_w8") else self._w8
-        self._w8 = w8
-        w8[:2].copy_(self.wr)
-        ops.gemm(self.drel, w8, self.dpooled, None, None, None, B, d, 8, 8, d, d, a_kmajor=1, b_kmajor=0)
-        if extra_dpooled is not None:            # task_qa model: the answer head's d(pooled_output) joins here
-            self.dpooled.add_(extra_dpooled)
-        e.pooler_backward(self.dpooled, self.dz, cls_rows, d_cls)
-        return self.loss
-
-
-class Engine(SamplerMixin):
+class Engine(TaskMixin, SamplerMixin):
     """Static-shape forward/backward program.  `need_lang`: whether lang/pooled outputs of the last cross layer are
     consumed (False for the masked-visual-token step)."""
 
@@ -845,13 +204,18 @@ class Engine(SamplerMixin):
         self.cid = torch.zeros(B, V, dtype=torch.int64, device=self.dev)
         self.vmask = torch.zeros(B, V, dtype=torch.uint8, device=self.dev)
         self.labels = torch.full((B, V), -100, dtype=torch.int64, device=self.dev)
-        self._hrows, self._hvis = None, None
         self.feat_tgt, self._feat_tgt_buf = None, None
         self.compact_head = os.environ.get("XL_COMPACT_HEAD", "1") != "0"   # training step: codebook head on the masked rows only
         # ... and with it the visual feed-forward block of the LAST cross layer: nothing but the head reads its output, so on
         # the other rows it is as dead as the head is (encoder_forward(ffn_rows=)); 0: all rows, as the reference computes them
         self.compact_last_ffn = os.environ.get("XL_COMPACT_LAST_FFN", "1") != "0"
         self._ffn_rows_run, self._ffn_in_c, self._vis_c, self._dvis_c = None, None, None, None
+        # state that a caller switches on for a call (sampling.py, match.py) or that exists once somebody has needed it
+        self._reuse_lang_stack = self._reuse_vis_stack = False      # samplers: the stack's output of the loop's first pass still stands
+        self._x0_given, self._packed_head = False, False            # match.MatchRunner: X[0] is given / caption sampler: packed head rows
+        self.embeds_mode, self._emb_tab, self._order_checked = False, None, False    # set_inputs: inputs_embeds staging, word_order check
+        self._dpooled, self._dpool_z, self._eval_bufs = None, None, {}               # backward_from_outputs(d_pooled=) / eval_buf scratch
+        self._task_run, self._qa_run, self._step_rows_run = None, False, None        # what task_forward ran, for task_backward
         self.task = getattr(store, "task", "vis_mask")
         # answer head on pooled_output: the VQA/GQA fine-tune model, or a pretraining model built with task_qa (then its CE
         # loss joins every task's loss, ref lxrt/modeling.py:292-304)
@@ -862,14 +226,11 @@ class Engine(SamplerMixin):
             assert need_lang, "this task reads the language / pooled output: build the engine with need_lang=True"
         # ---- head (ref lxrt/modeling.py:38-53) + losses
         h = "obj_predict_head"
-        self.hd = {k: (st.cview(n) if c else st.view(n), st.gview(n)) for k, n, c in (
-            ("wt", h + ".transform.dense.weight", True), ("bt", h + ".transform.dense.bias", False),
-            ("gt", h + ".transform.LayerNorm.weight", False), ("bbt", h + ".transform.LayerNorm.bias", False),
-            ("wf", h + ".linear_feat.weight", True), ("bf", h + ".linear_feat.bias", False),
-            ("bc", h + ".out_cluster.bias", False))}
+        self.hd = {k: (st.cview(n) if c else st.view(n), st.gview(n)) for k, n, c in (       # (the transform's parameters: head_tr)
+            ("wf", h + ".linear_feat.weight", True), ("bf", h + ".linear_feat.bias", False), ("bc", h + ".out_cluster.bias", False))}
         self.Kp = (self.K + 7) // 8 * 8
-        self.t_pre, self.t_h, self.t_y = self.act(self.MV, d), self.act(self.MV, d), self.act(self.MV, d)
-        self.t_mean, self.t_rstd = self.f32(self.MV), self.f32(self.MV)
+        self.head_tr = HeadTransform(self, h + ".transform.dense", h + ".transform.LayerNorm", d, d, self.eps, self.MV)
+        self.t_pre, self.t_h, self.t_y, self.t_mean, self.t_rstd = self.head_tr.bufs
         self.feat = self.act(self.MV, self.F)
         n_head_rows = self.MV if self.task in ("vis_mask", "all") else 8     # the codebook head is only read by vis_mask steps
         self.logits = torch.zeros(n_head_rows, self.K, dtype=torch.float32, device=self.dev)
@@ -881,9 +242,8 @@ class Engine(SamplerMixin):
         self.row_argmax = torch.zeros(self.MV, dtype=torch.int32, device=self.dev)
         self.code_pred = RowPredictor(self, self.K, self.F, self.MV, lambda: st.centroids_c, lambda: self.hd["bc"][0], self.K, self.Kp,
                                       self.logits, (self.row_maxprob, self.row_argmax, self.row_lse))
-        self.mrows = torch.zeros(self.MV, dtype=torch.int32, device=self.dev)         # ids b*V+v of the masked positions
-        self.labels_c = torch.zeros(self.MV, dtype=torch.int64, device=self.dev)
-        self.n_mrows = 0
+        self.mask_rows = RowSubset(self, self.MV)     # ids b*V+v of the masked positions: the codebook head's row list
+        self.mrows = self.mask_rows.idx
         self.mf_tmp = self.f32(d)
         self.mf_tmp_c = self.act(1, d)
         # ---- activation-gradient ping-pong
@@ -919,6 +279,10 @@ class Engine(SamplerMixin):
             streams += [torch.cuda.current_stream()] + ([self.side] if self.side is not None else [])
             for s_ in streams:
                 self._slab_ws.append(ops.gemm_workspace(256, s_))
+
+    @property
+    def n_mrows(self):                  # padded length of the masked-row list (0: none)
+        return self.mask_rows.n
 
     # ------------------------------------------------------------ row layout: [visual (MV) ; language (ML active of MLc)]
     @property
@@ -1075,7 +439,6 @@ class Engine(SamplerMixin):
 
     def defer_reductions(self, on):
         """backward of a training step: second stages of the column reductions are combined per layer (one launch)."""
-        import os
         if on and os.environ.get("XL_DEFER_REDUCE", "1") == "0":
             return
         if on != self._deferred:
@@ -1501,7 +864,7 @@ class Engine(SamplerMixin):
         self.embeds_mode = inputs_embeds is not None
         if self.embeds_mode:
             assert input_ids is None and tuple(inputs_embeds.shape) == (B, L, self.d), (inputs_embeds.shape, (B, L, self.d))
-            if getattr(self, "_emb_tab", None) is None:
+            if self._emb_tab is None:
                 self._emb_tab = torch.zeros(B * L + 1, self.d, dtype=self.cdtype, device=self.dev)
                 self._emb_grad = torch.zeros(B * L + 1, self.d, dtype=torch.float32, device=self.dev)
                 self._emb_ids = torch.arange(1, B * L + 1, dtype=torch.int64, device=self.dev).view(B, L)
@@ -1512,7 +875,7 @@ class Engine(SamplerMixin):
             self.ids.copy_(input_ids, non_blocking=True)
             if word_order is None:
                 word_order = torch.sort(input_ids.reshape(-1), stable=True).indices
-            elif not getattr(self, "_order_checked", False):
+            elif not self._order_checked:
                 # the embedding backward gives every word-table row ONE writer -- the block that owns the row's run in this order -- and
                 # commits with a plain read-modify-write: an order computed from OTHER ids (before MLM masking, re-tokenisation ...) makes
                 # several owners race on a row, silently.  One check (a host round trip) on the first loader-supplied order.
@@ -1565,7 +928,7 @@ class Engine(SamplerMixin):
                 if self.compact_head and self.task in ("vis_mask", "all"):
                     # the only host <-> device round trip of a step: how many positions are masked (sizes the head's launches)
                     idx = masked_rows.reshape(-1) if masked_rows is not None else (vis_mask.reshape(-1) != 0).nonzero().reshape(-1)
-                    self.n_mrows = self.pad_rows(self.mrows, idx, int(idx.numel()), self.MV)
+                    self.mask_rows.set(idx)
         else:
             self.feats.copy_(visual_feats.reshape(self.MV, self.F), non_blocking=True)
         if obj_labels is not None:
@@ -1579,7 +942,7 @@ class Engine(SamplerMixin):
 
     def d_inputs_embeds(self):
         """gradient w.r.t. the inputs_embeds of the last backward ([B, L, d] fp32 view; valid until the next backward)."""
-        assert getattr(self, "embeds_mode", False)
+        assert self.embeds_mode
         return self._emb_grad[1:].view(self.B, self.L, self.d)
 
     def hidden_states(self):
@@ -1658,7 +1021,7 @@ class Engine(SamplerMixin):
         n_layers = cfg.l_layers if n_layers is None else n_layers
         e = "bert.embeddings"
         self._pr("emb")
-        emb = getattr(self, "embeds_mode", False)
+        emb = self.embeds_mode
         ops.embed_ln_fwd(self._emb_ids if emb else self.ids, self.tt,
                          self._emb_tab if emb else st.cview(e + ".word_embeddings.weight"), st.cview(e + ".position_embeddings.weight"),
                          st.cview(e + ".token_type_embeddings.weight"), st.view(e + ".LayerNorm.weight"),
@@ -1725,15 +1088,15 @@ class Engine(SamplerMixin):
         # samplers: the text does not change between refinement steps and, without dropout, neither does the output of the
         # language stack (embeddings + l_layers self-attention layers: it never sees the visual tokens) -- it still sits in
         # the language rows of X[0] from the loop's first pass (no later layer writes there), so the later passes skip it.  Exact.
-        skip_lang = getattr(self, "_reuse_lang_stack", False) and self.p_hid == 0 and self.p_attn == 0
+        skip_lang = self._reuse_lang_stack and self.p_hid == 0 and self.p_attn == 0
         # caption sampler, the mirror image: the picture does not change between refinement steps and neither does the output of
         # the feature encoder + r_layers visual stack (they never see the text) -- it still sits in the visual rows of X[0] from
         # the loop's first pass (no later layer writes there), so the later passes skip them.  Exact under the same condition.
-        skip_vis = getattr(self, "_reuse_vis_stack", False) and self.p_hid == 0 and self.p_attn == 0
+        skip_vis = self._reuse_vis_stack and self.p_hid == 0 and self.p_attn == 0
         # caption-image matching (match.MatchRunner): X[0] is GIVEN -- both stacks ran once on engines of their own batch sizes and
         # xl_pair_expand laid their outputs out pair by pair -- so neither stack runs here.  Exact under the same condition, which
         # the runner establishes for the call (with dropout the stacks would have to run here, over inputs nobody staged).
-        x0_given = getattr(self, "_x0_given", False)
+        x0_given = self._x0_given
         assert not x0_given or (self.p_hid == 0 and self.p_attn == 0), "_x0_given needs dropout off"
         skip_lang, skip_vis = skip_lang or x0_given, skip_vis or x0_given
         assert x0_given or not (skip_lang and skip_vis)
@@ -1783,7 +1146,7 @@ class Engine(SamplerMixin):
                 self.join()
         Xl = self.X[-1]
         self.lang_final, self.vis_final = _h(self.lr(Xl)), _h(self.vr(Xl))      # (the heads read the bf16 copy of an fp32 stream)
-        if self.packed and self.need_lang and not getattr(self, "_packed_head", False):   # language_output in the reference's [B, L, d] layout
+        if self.packed and self.need_lang and not self._packed_head:   # language_output in the reference's [B, L, d] layout
             self.lang_final = self._dense_lang(self.lang_final, self.lang_pad)
         self._pr("heads")                   # pooler and every head on top of the encoder
         if want_pooled and self.need_lang:
@@ -1791,405 +1154,6 @@ class Engine(SamplerMixin):
             ops.gemm(self.lang_final, st.cview("bert.pooler.dense.weight"), self.pooled, st.view("bert.pooler.dense.bias"),
                      None, None, self.B, d, d, self.L * d, d, d, epilogue=EPI_TANH)
         return self.lang_final, self.vis_final, self.pooled
-
-    # The head runs either on all B*V visual rows (inference, sampler, the nn.Module API) or, inside the training step, on the
-    # masked rows only: both losses read nothing else (ref lxrt/modeling.py:253-256: labels -100 elsewhere; :273-287: the
-    # SmoothL1 term is multiplied by vis_mask), so with `--vis_mask_predict` masks (n ~ U{1..64}) half of the head's rows --
-    # and of its 10k-codebook contractions -- are never needed.  `_hrows` = None (all rows) or (rows int32, n).
-    def _head_rows(self):
-        return self._hrows[1] if self._hrows is not None else self.MV
-
-    def head_forward(self, want_logits=True):
-        """LxmertVisualObjHead.forward (ref lxrt/modeling.py:38-53): returns (feat, logits)."""
-        ops, d, F, K = self.ops, self.d, self.F, self.K
-        ops.block = "head"
-        M = self._head_rows()
-        hd = self.hd
-        vis = self.vis_final
-        if self._hrows is not None and self._ffn_rows_run is not None:
-            assert self._ffn_rows_run[1] == M
-            self._hvis_buf = _h(self._vis_c)                   # the last visual feed-forward block ran on these rows only
-            vis = self._hvis_buf[:M]
-        elif self._hrows is not None:
-            self._hvis_buf = self.tmp("vis_c", self.MV, d)     # kept: the backward contracts over it (tmp() there may hand out the
-            vis = self._hvis_buf[:M]                           # other scratch set -- the generation flips with the layers' backward)
-            ops.gather_rows(self.vis_final, self._hrows[0], vis, M, d, d, d)
-        self._hvis = vis
-        ops.gemm(vis, hd["wt"][0], self.t_h, hd["bt"][0], None, self.t_pre, M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
-        ops.layernorm_fwd(self.t_h, hd["gt"][0], hd["bbt"][0], self.t_y, self.t_mean, self.t_rstd, M, d, self.eps)
-        ops.gemm(self.t_y, hd["wf"][0], self.feat, hd["bf"][0], None, None, M, F, d, d, d, F)
-        if want_logits:
-            ops.gemm(self.feat, self.store.centroids_c, self.logits, hd["bc"][0], None, None, M, K, F, F, F, K, out_f32=True)
-        return self.feat, self.logits
-
-    def losses_forward_backward(self, want_grad=True, feat_loss=True):
-        """ref lxrt/modeling.py:237-290.  Leaves d(logits) / d(feat) for head_backward; returns the loss buffer
-        [obj_loss, feat_loss] (device, fp32)."""
-        ops, F, K = self.ops, self.F, self.K
-        M = self._head_rows()
-        ops.zero(self.losses)
-        ops.mask_counts(self.labels, self.vmask, self.counts, self.nmask, self.B, self.V)
-        labels = self.labels
-        rows = None
-        if self._hrows is not None:
-            rows = self._hrows[0]
-            labels = self.labels_c[:M]
-            ops.gather_labels(self.labels, rows, labels, M)
-        ops.ce_fwd_bwd(self.logits, labels, self.counts, self.dlogits if want_grad else None, self.losses[0:],
-                       None, None, None, M, K, K, self.Kp, 1.0)
-        self.with_feat_loss = feat_loss
-        if feat_loss:
-            ops.featloss_fwd_bwd(self.feat, self.store.centroids_c, self.cid, self.vmask, self.nmask,
-                                 self.dfeat if want_grad else None, self.losses[1:], self.B, self.V, F, 1.0,
-                                 rows=rows, n_rows=M if rows is not None else 0, targets=self.feat_tgt)
-        return self.losses
-
-    def pooler_backward(self, dpooled, dz, cls_rows, d_cls, accumulate=False):
-        """LxmertPooler backward (HF:566-572): pooled = tanh(W_p cls + b_p).  cls_rows / d_cls are [B, d] views of the
-        language output / its gradient with row stride L*d (the [CLS] rows); accumulate: d_cls += instead of =."""
-        ops, st, d, B, L = self.ops, self.store, self.d, self.B, self.L
-        ops.tanh_bwd(dpooled, self.pooled, dz, B * d)
-        ops.colsum(dz, st.gview("bert.pooler.dense.bias"), B, d, d, ws=self.ws)
-        self.wgrad_defer(dz, cls_rows, st.gview("bert.pooler.dense.weight"), d, d, B, d, L * d, d)
-        self.wgrad_flush()
-        if accumulate:              # in-place: every output element is read (residual) and written by the same lane
-            ops.gemm(dz, st.cview("bert.pooler.dense.weight"), d_cls, None, d_cls, None, B, d, d, d, d, L * d, ldr=L * d,
-                     a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL, **self.rkw)
-        else:
-            ops.gemm(dz, st.cview("bert.pooler.dense.weight"), d_cls, None, None, None, B, d, d, d, d, L * d,
-                     a_kmajor=1, b_kmajor=0, **self.rkw)
-
-    # ---- QA branch of a task_qa pretraining model (ref lxrt/modeling.py:292-304): rides on every task
-    def _qa_forward(self, qa_labels):
-        """answer_score = answer_head(pooled_output) and qa_loss / d(answer_score); True when the branch is active."""
-        if not self.task_qa:
-            assert qa_labels is None, "qa_labels given but the model has no QA head (build the store with num_answers > 0)"
-            return False
-        assert qa_labels is not None, "a task_qa model adds qa_loss in every branch: label_dict['qa_labels'] is required"
-        self.answer.labels.copy_(qa_labels.reshape(-1), non_blocking=True)
-        self.answer.fwd(self.pooled)
-        self.answer.ce_loss_fwd_bwd(True)
-        return True
-
-    def backward_from_outputs(self, d_lang=None, d_vis=None, d_pooled=None):
-        """backward of LxmertModel.forward from gradients of its three outputs (any may be None): ACCUMULATES into store.grad
-        (HF:691-822; the pooler's gradient joins the [CLS] rows of d(language_output))."""
-        assert self.need_lang, "needs the language side of the last cross layer (engine built with need_lang=True)"
-        d = self.d
-        if self._ffn_rows_run is not None:          # the last forward was a masked-visual-token step's: the vision output exists
-            if d_vis is not None:                   # at the masked rows only, in compact form (encoder_forward ffn_rows)
-                raise RuntimeError("backward_from_outputs(d_vis=): the last forward computed the vision output at the masked rows "
-                                   "only; run encoder_forward() for a backward from a vision-output gradient")
-            self._dvis_c = Engine._NO_VIS_GRAD
-        self.begin_backward()
-        GA = self.GA
-        if d_lang is None or d_vis is None:
-            self.zero_out_grads(GA)
-        if d_lang is not None:
-            self.glang(GA).copy_(d_lang.reshape(self.MLd, d))
-        if d_vis is not None:
-            self.vr(GA).copy_(d_vis.reshape(self.MV, d))
-        if d_pooled is not None:
-            if not hasattr(self, "_dpooled"):
-                self._dpooled, self._dpool_z = self.act(self.B, d), self.act(self.B, d)
-            self._dpooled.copy_(d_pooled.reshape(self.B, d))
-            cls_rows, d_cls = self._cls_views(GA)
-            self.pooler_backward(self._dpooled, self._dpool_z, cls_rows, d_cls, accumulate=True)
-        self.encoder_backward(have_lang_grad=True)
-
-    def glang(self, G):
-        """where the heads leave d(language_output) in the reference's dense [B*L, d] layout: the language rows of the gradient
-        buffer G themselves, or -- packed language rows -- a dense side buffer that encoder_backward gathers into them."""
-        return self.glang_pad if self.packed else self.lr(G)
-
-    def zero_out_grads(self, G):
-        """d(language_output) = d(vision_output) = 0 (the caller then writes what its loss produces)"""
-        self.ops.zero(G[:self.MX])
-        if self.packed:
-            self.ops.zero(self.glang_pad)
-
-    def _cls_views(self, G):
-        """[B, d] views with row stride L*d of the [CLS] rows of language_output and of its gradient"""
-        B, L, d = self.B, self.L, self.d
-        return self.lang_final.view(B, L * d)[:, :d], self.glang(G).view(B, L * d)[:, :d]
-
-    # Every branch of XLxmertForPretraining.forward (ref lxrt/modeling.py:154-308) as two phases: task_forward = encoder + heads
-    # + losses (and the loss gradients w.r.t. the head outputs: no parameter gradient is touched), task_backward = everything
-    # that accumulates into store.grad.  The trainer runs them back to back around one clear of the gradient buffer
-    # (*_forward_backward below); the nn.Module surface runs them from autograd's forward / backward.
-    def task_forward(self, task, word_labels=None, word_rows=None, matched_labels=None, qa_labels=None, feat_loss=True,
-                     want_grad=True):
-        """returns {name: 0-d/1-element device tensor} with the reference's out_dict keys (lm_loss / matched_loss / obj_loss,
-        feat_loss / qa_loss)."""
-        assert task in ("vis_mask", "word_mask", "matched", "qa"), task
-        lh = self.lang_heads
-        self._task_run = task
-        out = {}
-        if task == "vis_mask":
-            use_rows = want_grad and self.compact_head and self.has_vmask and 0 < self.n_mrows < self.MV
-            self._hrows_step = (self.mrows, self.n_mrows) if use_rows else None
-            self.encoder_forward(want_pooled=self.task_qa, ffn_rows=self._hrows_step)
-            self._hrows = self._hrows_step
-            try:
-                self.head_forward()
-                losses = self.losses_forward_backward(want_grad, feat_loss)
-            finally:
-                self._hrows = None
-            out["obj_loss"] = losses[0:1]
-            if feat_loss:
-                out["feat_loss"] = losses[1:2]
-        elif task == "word_mask":
-            wl = word_labels.clone()
-            wl[wl < 0] = -100           # the reference's data code writes -1, its loss ignores -100: any negative = not masked
-            lh.word_labels.copy_(wl, non_blocking=True)
-            lh.set_rows(word_rows if want_grad else None)      # labelled positions (from the data loader): masked-row head
-            self.encoder_forward(want_pooled=self.task_qa)
-            lh.mlm_fwd(self.lang_final)
-            out["lm_loss"] = lh.mlm_loss()[0:1]
-        elif task == "matched":
-            lh.matched_labels.copy_(matched_labels, non_blocking=True)
-            self.encoder_forward(want_pooled=True)
-            lh.rel_fwd(self.pooled)
-            out["matched_loss"] = lh.rel_loss()[1:2]
-        else:
-            assert self.task_qa, "task 'qa' needs a model built with the QA head (num_answers > 0)"
-            self.encoder_forward(want_pooled=True)
-        if self._qa_forward(qa_labels):
-            out["qa_loss"] = self.answer.loss[0:1]
-        self._qa_run = "qa_loss" in out
-        return out
-
-    # ---- validation pass (ref pretrain/lxmert_pretrain.py:553-673 evaluate_epoch; tasks/vqa.py:259-311 predict / evaluate): one task
-    # per batch, forward only, model.eval() semantics.  The losses need of the logits only (max, sum exp, the label's logit) per row
-    # and the accuracy the argmax: on the bf16 path the big heads' contractions end in XL_EPI_ROWSCORE and the logits never reach
-    # memory; the small heads (and fp32 engines, rows off the 256 grid, XL_FUSED_PREDICT=0) go through xl_score_rows over fp32 logits.
-    def eval_buf(self, name, M, N, dtype=None):
-        """scratch of the validation pass: its own (the backward scratch generations -- tmp() -- are not touched)"""
-        dt = self.cdtype if dtype is None else dtype
-        key = (name, M, N, dt)
-        bufs = self.__dict__.setdefault("_eval_bufs", {})
-        if key not in bufs:
-            bufs[key] = torch.zeros(M, N, dtype=dt, device=self.dev)
-        return bufs[key]
-
-    def _eval_totals(self, key):
-        """fp32[4] of xl_rowscore_combine / xl_score_rows {sum nll, valid rows, rows predicted right, -}, zeroed for this call"""
-        t = self.eval_buf("tot_" + key, 1, 4, torch.float32).view(4)
-        self.ops.zero(t)
-        return t
-
-    @staticmethod
-    def _eval_out(out, key, tot):
-        """the mean loss (what task_forward(want_grad=False) calls `key`: sum / max(count, 1)) and the additive totals"""
-        out[key] = tot[0:1] / tot[1:2].clamp(min=1.0)
-        out[key + "_sum"], out[key + "_count"], out[key + "_correct"] = tot[0:1].clone(), tot[1:2].clone(), tot[2:3].clone()
-
-    def evaluate_task(self, task, word_labels=None, word_rows=None, matched_labels=None, qa_labels=None, targets=None, labels=None,
-                      feat_loss=True):
-        """Forward-only losses and accuracies of one task on the batch set_inputs staged: `vis_mask`, `word_mask`, `matched`, `qa`
-        (arguments as task_forward) and the fine-tune tasks `vqa` (targets [B, A] soft scores) and `nlvr2` (labels [P]).
-        Dropout is off for the call whatever the engine was built with; the step seed, store.grad, the parameters, the optimizer
-        state, the accumulation flags and the backward scratch are not touched.  Returns {name: device tensor}, no host
-        synchronisation: the reference's loss keys (obj_loss, feat_loss, lm_loss, matched_loss, qa_loss; `loss` for vqa / nlvr2) --
-        each mean is what task_forward(want_grad=False) returns for the same inputs -- and per classification loss <key>_sum,
-        <key>_count, <key>_correct (additive over batches: EvalMeter), qa_pred (ref lxrt/modeling.py:300), and for vqa / nlvr2
-        `score`, `pred` = logit.max(1).  The tensors are valid until the next evaluate_task."""
-        assert task in ("vis_mask", "word_mask", "matched", "qa", "vqa", "nlvr2"), task
-        p_saved = (self.p_hid, self.p_attn)
-        self.p_hid = self.p_attn = 0.0
-        try:
-            return self._evaluate_task(task, word_labels, word_rows, matched_labels, qa_labels, targets, labels, feat_loss)
-        finally:
-            self.p_hid, self.p_attn = p_saved
-
-    def _eval_pred(self, key, n):
-        return self.eval_buf("pred_" + key, 1, n, torch.int32).view(n)
-
-    def _evaluate_task(self, task, word_labels, word_rows, matched_labels, qa_labels, targets, labels, feat_loss):
-        ops, lh, ans = self.ops, self.lang_heads, self.answer
-        out = {}
-        if task in ("vqa", "nlvr2"):
-            assert ans is not None and not self.task_qa, "vqa / nlvr2 need a fine-tune model (ParamStore task='vqa' / 'nlvr2')"
-            B, A = ans.Bh, ans.A
-            pred, score = self._eval_pred("ans", B), self.eval_buf("score_ans", 1, B, torch.float32).view(B)
-            if task == "vqa":
-                ans.targets.copy_(targets, non_blocking=True)
-                self.vqa_forward()
-                out["loss"] = ans.loss_fwd_bwd(False)                                   # BCEWithLogitsLoss, no d(logit)
-                ops.score_rows(ans.logit, B, A, A, None, None, pred, score, None)
-                out["loss_sum"], out["loss_count"] = out["loss"] * float(B), torch.full_like(out["loss"], float(B))
-                # the reference's VQA accuracy (tasks/vqa.py:288-297 evaluate): the soft score of the predicted answer
-                out["loss_correct"] = ans.targets.gather(1, pred.long()[:, None]).sum().reshape(1)
-            else:
-                assert ans.pair, "build the store with task='nlvr2'"
-                ans.labels.copy_(labels.reshape(-1), non_blocking=True)
-                self.vqa_forward()
-                tot = self._eval_totals("ans")
-                ops.score_rows(ans.logit, B, A, A, ans.labels, None, pred, score, tot)
-                self._eval_out(out, "loss", tot)
-            out["pred"], out["score"] = pred, score
-            return out
-        if task == "vis_mask":
-            assert self.task in ("vis_mask", "all"), "the codebook head belongs to a model built for task 'vis_mask' / 'all'"
-            use_rows = self.compact_head and self.has_vmask and 0 < self.n_mrows < self.MV
-            rows = (self.mrows, self.n_mrows) if use_rows else None
-            self.encoder_forward(want_pooled=self.task_qa, ffn_rows=rows)
-            self._eval_vis_head(out, rows, feat_loss)
-        elif task == "word_mask":
-            wl = word_labels.clone()
-            wl[wl < 0] = -100
-            lh.word_labels.copy_(wl, non_blocking=True)
-            lh.set_rows(word_rows)
-            self.encoder_forward(want_pooled=self.task_qa)
-            tot = self._eval_totals("lm")
-            lh.mlm_evaluate(self.lang_final, tot, self._eval_pred("lm", self.MLd))
-            self._eval_out(out, "lm_loss", tot)
-        elif task == "matched":
-            lh.matched_labels.copy_(matched_labels, non_blocking=True)
-            self.encoder_forward(want_pooled=True)
-            lh.rel_fwd(self.pooled)
-            tot = self._eval_totals("matched")
-            ops.score_rows(lh.rel, self.B, 2, 8, lh.matched_labels, None, None, None, tot)
-            self._eval_out(out, "matched_loss", tot)
-        else:
-            assert self.task_qa, "task 'qa' needs a model built with the QA head (num_answers > 0)"
-            self.encoder_forward(want_pooled=True)
-        if self.task_qa:
-            assert qa_labels is not None, "a task_qa model adds qa_loss in every branch: label_dict['qa_labels'] is required"
-            ans.labels.copy_(qa_labels.reshape(-1), non_blocking=True)
-            ans.fwd(self.pooled)
-            tot, pred = self._eval_totals("qa"), self._eval_pred("qa", ans.Bh)
-            ops.score_rows(ans.logit, ans.Bh, ans.A, ans.A, ans.labels, None, pred, None, tot)
-            self._eval_out(out, "qa_loss", tot)
-            out["qa_pred"] = pred
-        else:
-            assert qa_labels is None, "qa_labels given but the model has no QA head (build the store with num_answers > 0)"
-        return out
-
-    def _eval_vis_head(self, out, rows, feat_loss):
-        """LxmertVisualObjHead (ref lxrt/modeling.py:38-53) and both of its losses on the masked rows only (exact: the losses read
-        nothing else; pad entries of the row list are zero rows with label -100) or, without a row list, on all rows"""
-        ops, d, F, hd = self.ops, self.d, self.F, self.hd
-        ops.block = "head"
-        M = rows[1] if rows is not None else self.MV
-        vis, labels = self.vis_final, self.labels
-        if rows is not None:
-            if self._ffn_rows_run is not None:                 # the last visual feed-forward block ran on these rows only
-                assert self._ffn_rows_run[1] == M
-                vis = _h(self._vis_c)[:M]
-            else:
-                vis = self.eval_buf("vis_c", self.MV, d)[:M]
-                ops.gather_rows(self.vis_final, rows[0], vis, M, d, d, d)
-            labels = self.labels_c[:M]
-            ops.gather_labels(self.labels, rows[0], labels, M)
-        ops.gemm(vis, hd["wt"][0], self.t_h, hd["bt"][0], None, self.t_pre, M, d, d, d, d, d, ldx=d, epilogue=EPI_GELU)
-        ops.layernorm_fwd(self.t_h, hd["gt"][0], hd["bbt"][0], self.t_y, self.t_mean, self.t_rstd, M, d, self.eps)
-        ops.gemm(self.t_y, hd["wf"][0], self.feat, hd["bf"][0], None, None, M, F, d, d, d, F)
-        tot, pred = self._eval_totals("obj"), self._eval_pred("obj", self.MV)[:M]        # (pred: the head's rows, in row-list order)
-        self.code_pred.score(self.feat, M, labels, pred, tot)
-        self._eval_out(out, "obj_loss", tot)
-        if feat_loss:
-            ops.zero(self.losses[1:2])
-            ops.mask_counts(self.labels, self.vmask, self.counts, self.nmask, self.B, self.V)
-            ops.featloss_fwd_bwd(self.feat, self.store.centroids_c, self.cid, self.vmask, self.nmask, None, self.losses[1:], self.B,
-                                 self.V, F, 1.0, rows=rows[0] if rows is not None else None, n_rows=M if rows is not None else 0,
-                                 targets=self.feat_tgt)
-            out["feat_loss"] = self.losses[1:2]
-
-    def task_backward(self):
-        """backward of the branch task_forward ran last; ACCUMULATES into store.grad."""
-        task, qa, lh, ans = self._task_run, self._qa_run, self.lang_heads, self.answer
-        self.begin_backward()
-        GA = self.GA
-        if task == "vis_mask":
-            self._hrows = self._hrows_step
-            try:
-                self.head_backward(self.vr(GA), report=not qa)
-            finally:
-                self._hrows = None
-            if self.need_lang:          # the language side of the last cross layer exists: zero gradient ...
-                self.ops.zero(self.glang(GA))
-            if qa:                      # ... unless the QA branch reads pooled_output
-                cls_rows, d_cls = self._cls_views(GA)
-                ans.bwd(self.pooled, cls_rows, d_cls)
-                self._ready_heads()
-            self.encoder_backward(self.need_lang)
-            return
-        self.zero_out_grads(GA)
-        cls_rows, d_cls = self._cls_views(GA)
-        if task == "word_mask":
-            lh.mlm_bwd(self.glang(GA))
-            if qa:
-                ans.bwd(self.pooled, cls_rows, d_cls, accumulate=True)     # the MLM gradient of the [CLS] rows is there
-        elif task == "matched":
-            extra = None
-            if qa:
-                ans.bwd_to_pooled(self.pooled)
-                extra = ans.dpooled
-            lh.rel_bwd(self.pooled, cls_rows, d_cls, extra_dpooled=extra)
-        else:
-            ans.bwd(self.pooled, cls_rows, d_cls)
-        self._ready_heads()
-        self.encoder_backward(True)
-
-    def _task_step(self, task, **kw):
-        out = self.task_forward(task, **kw)
-        self.clear_grads()
-        self.task_backward()
-        return out
-
-    def qa_forward_backward(self, qa_labels):
-        """XLxmertForPretraining.forward(task='qa') + backward on a task_qa model (ref lxrt/modeling.py:154-210, 292-306):
-        un-masked codebook features in, total_loss = qa_loss.  Returns the device loss buffer [1]."""
-        return self._task_step("qa", qa_labels=qa_labels)["qa_loss"]
-
-    def word_mask_forward_backward(self, word_labels, word_rows=None, qa_labels=None):
-        """XLxmertForPretraining.forward(task='word_mask') + backward (ref lxrt/modeling.py:211-219): un-masked codebook
-        features in (set_inputs(cluster_ids=..., vis_mask=None)), MLM loss over `word_labels` (negative = ignored)."""
-        return self._task_step("word_mask", word_labels=word_labels, word_rows=word_rows, qa_labels=qa_labels)["lm_loss"]
-
-    def matched_forward_backward(self, matched_labels, qa_labels=None):
-        """XLxmertForPretraining.forward(task='matched') + backward (ref lxrt/modeling.py:221-229)."""
-        return self._task_step("matched", matched_labels=matched_labels, qa_labels=qa_labels)["matched_loss"]
-
-    def vqa_forward(self):
-        """VQAModel.forward (ref tasks/vqa_model.py:22-72): real grid features -> encoder -> pooled_output -> answer head."""
-        self.encoder_forward(want_pooled=True)
-        return self.answer.fwd(self.pooled)
-
-    def vqa_forward_backward(self, targets):
-        """one VQA/GQA fine-tune forward + backward (ref tasks/vqa.py:166-189): BCEWithLogitsLoss(logit, target).backward().
-        Gradients land in store.grad; returns the device loss buffer [1]."""
-        ans = self.answer
-        ans.targets.copy_(targets, non_blocking=True)
-        self.vqa_forward()
-        self.zero_accumulated_grads()
-        loss = ans.loss_fwd_bwd(True)
-        GA = self.GA
-        self.zero_out_grads(GA)                      # only the [CLS] rows of the language output carry gradient
-        cls_rows, d_cls = self._cls_views(GA)
-        ans.bwd(self.pooled, cls_rows, d_cls)
-        self._ready_heads()
-        self.encoder_backward(True)
-        return loss
-
-    def nlvr2_forward_backward(self, labels):
-        """one NLVR2 fine-tune forward + backward (ref tasks/nlvr2.py:72 CrossEntropyLoss over the 2-way logit of each
-        statement; tasks/nlvr2_model.py:50-86: encoder over the flattened [2P] (statement, image) rows, pooled outputs of a
-        statement's two images concatenated).  `labels` [P] int64.  Returns the device loss buffer [1]."""
-        ans = self.answer
-        assert ans is not None and ans.pair, "build the store with task='nlvr2'"
-        ans.labels.copy_(labels.reshape(-1), non_blocking=True)
-        self.vqa_forward()
-        self.zero_accumulated_grads()
-        loss = ans.ce_loss_fwd_bwd(True)
-        GA = self.GA
-        self.zero_out_grads(GA)
-        cls_rows, d_cls = self._cls_views(GA)
-        ans.bwd(self.pooled, cls_rows, d_cls)
-        self._ready_heads()
-        self.encoder_backward(True)
-        return loss
 
     # ------------------------------------------------------------ backward
     def zero_accumulated_grads(self):
@@ -2217,51 +1181,6 @@ class Engine(SamplerMixin):
         self._gen_guard = {"v": {}, "l": {}}    # (the previous backward ended with wgrad_sync_all on both streams)
         self.grad_is_zero = False
         self._lane_lo = {"v": 0, "l": self.store.language_range()[0]}
-
-    def head_backward(self, d_vis, report=True):
-        """consumes dlogits/dfeat from losses_forward_backward; writes d(vision_output) into d_vis.  report=False: another
-        head's backward (QA branch) still follows before the head gradients are final."""
-        ops, d, MV, F, K = self.ops, self.d, self.MV, self.F, self.K
-        ops.block = "head"
-        M = self._head_rows()
-        hd = self.hd
-        ops.colsum(self.dlogits, hd["bc"][1], M, self.Kp, self.Kp, ws=self.ws_wide("codebook", self.Kp))      # pad columns are zero; the bias unit is padded
-        dfeat = self.tmp("dfeat", MV, F)
-        if self.with_feat_loss:
-            ops.gemm(self.dlogits, self.store.centroids_c, dfeat, None, self.dfeat, None, M, F, K, self.Kp, F, F, ldr=F,
-                     a_kmajor=1, b_kmajor=0, epilogue=EPI_RESIDUAL)
-        else:
-            ops.gemm(self.dlogits, self.store.centroids_c, dfeat, None, None, None, M, F, K, self.Kp, F, F, a_kmajor=1, b_kmajor=0)
-        ops.colsum(dfeat, hd["bf"][1], M, F, F, ws=self.ws)
-        # weight gradients contract over the rows: round a compacted row count up to the K tile with zero gradient rows
-        Mk = min(MV, (M + 63) // 64 * 64)
-        if Mk > M:
-            ops.zero(dfeat[M:Mk])
-        self.wgrad_defer(dfeat, self.t_y, hd["wf"][1], F, d, Mk, F, d, d)
-        dty = self.tmp("dz", MV, d)
-        ops.gemm(dfeat, hd["wf"][0], dty, None, None, None, M, d, F, F, d, d, a_kmajor=1, b_kmajor=0)
-        dth = self.tmp("dctx", MV, d)
-        ops.layernorm_bwd(dty, self.t_h, hd["gt"][0], self.t_mean, self.t_rstd, dth, hd["gt"][1], hd["bbt"][1], None, M, d, ws=self.ws)
-        dtp = self.tmp("dzm", MV, d)
-        ops.gelu_bwd(dth, self.t_pre, dtp, M * d)
-        ops.colsum(dtp, hd["bt"][1], M, d, d, ws=self.ws)
-        if Mk > M:
-            ops.zero(dtp[M:Mk])
-        hv = self._hvis if self._hrows is None else self._hvis_buf
-        self.wgrad_defer(dtp, hv, hd["wt"][1], d, d, Mk, d, d, d)
-        self.wgrad_flush()
-        if self._hrows is None:
-            ops.gemm(dtp, hd["wt"][0], d_vis, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **self.rkw)
-        else:                       # gradient of the masked rows, scattered into an otherwise zero d(vision_output)
-            dvc = self.tmp("dvis_c", MV, d, res=True)          # (fp32 stream: the head's gradient enters it in fp32)
-            ops.gemm(dtp, hd["wt"][0], dvc, None, None, None, M, d, d, d, d, d, a_kmajor=1, b_kmajor=0, **self.rkw)
-            if self._ffn_rows_run is not None:          # ... or handed over compact: the last visual feed-forward block's
-                self._dvis_c = dvc[:M]                  # backward runs on these rows too (_encoder_backward); d_vis is not written
-            else:
-                ops.zero(d_vis)
-                ops.scatter_rows(dvc, self._hrows[0], d_vis, M, d, d, d)
-        if report:
-            self._ready_heads()
 
     def encoder_backward(self, have_lang_grad=False):
         """d(outputs) are expected in GA ([lang ; vis] rows; the language rows are ignored unless have_lang_grad)."""
@@ -2371,7 +1290,7 @@ class Engine(SamplerMixin):
             else:
                 ops.layernorm_bwd(dy, self.emb_pre, st.view(e + ".LayerNorm.weight"), self.emb_mean, self.emb_rstd, dpre,
                                   st.gview(e + ".LayerNorm.weight"), st.gview(e + ".LayerNorm.bias"), None, MLd, d, ws=self.ws)
-            emb = getattr(self, "embeds_mode", False)
+            emb = self.embeds_mode
             if emb:                                   # d(inputs_embeds) instead of d(word_embeddings): see set_inputs
                 ops.zero(self._emb_grad)
             ops.embed_bwd(dpre, self._emb_ids if emb else self.ids, self.tt,
@@ -2432,11 +1351,3 @@ class Engine(SamplerMixin):
             self._report("v", lo, flush=True)        # (already there: the last visual layer reported it)
             self._lane_lo["v"] = hi
             self._report("v", st.n_used, flush=True)
-
-    # ------------------------------------------------------------ whole vis_mask step (forward + backward)
-    def vis_mask_forward_backward(self, feat_loss=True, qa_labels=None):
-        """XLxmertForPretraining.forward(task='vis_mask') + loss.backward() (ref lxrt/modeling.py:154-308,
-        lxmert_pretrain.py:338).  Gradients land in store.grad; returns the device loss buffer [obj_loss, feat_loss]
-        (a task_qa model's qa_loss is in self.answer.loss)."""
-        self._task_step("vis_mask", feat_loss=feat_loss, qa_labels=qa_labels)
-        return self.losses

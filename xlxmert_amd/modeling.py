@@ -302,6 +302,7 @@ class XLxmertForPretraining(nn.Module):
         self.mask_feat = nn.Parameter(self._store.view("mask_feat"))
         self.mask_feat.grad = self._store.gview("mask_feat")
         self.vis_emb = None
+        self._match_key, self._match_runner = None, None        # caption-image matching: the runner of the last geometry asked for
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         from .trainer import init_reference_weights
         init_reference_weights(self._store, seed=0)
@@ -469,7 +470,7 @@ class XLxmertForPretraining(nn.Module):
                 raise ValueError(f"visual_pos is needed for {V} visual tokens (not a square grid)")
             visual_pos = self._grid_pos(g, M, vis.device)
         key = (N, M, L, V, chunk_pairs)
-        if getattr(self, "_match_key", None) != key:
+        if self._match_key != key:
             self._match_runner = MatchRunner(self.config, self._store, self.bert._ops, N, M, L, V, chunk_pairs=chunk_pairs,
                                              residual_dtype=self.bert._residual_dtype)
             self._match_key = key
@@ -701,7 +702,7 @@ class _VqaFn(torch.autograd.Function):
         ans.dlogit[:, :ans.A].copy_(d_logit)
         eng.zero_out_grads(eng.GA)
         cls_rows, d_cls = eng._cls_views(eng.GA)
-        ans.bwd(eng.pooled, cls_rows, d_cls)
+        ans.bwd(cls_rows, d_cls)
         eng.encoder_backward(True)            # gradients accumulate into the flat buffer: call model.zero_grad() per step
         return None, None
 

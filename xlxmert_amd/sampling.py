@@ -187,12 +187,6 @@ class SamplerMixin:
         self.code_pred.from_logits(self.MV)
         return self.row_maxprob, self.row_argmax
 
-    def predict_codes_fused(self):
-        """head_forward(want_logits=False) and code_pred.prepare() must have run: self.feat -> (max prob, argmax) per row, no
-        logits in memory."""
-        self.code_pred.run(self.feat, self.MV, True)
-        return self.row_maxprob, self.row_argmax
-
     def _predict_step(self, fused, temperature=None, seed=0, trunc=None):
         self.head_forward(want_logits=False)
         self.code_pred.run(self.feat, self.MV, fused, temperature, seed, trunc)
@@ -372,7 +366,7 @@ class SamplerMixin:
         if lh is None or not lh.has_mlm or not self.need_lang:
             raise RuntimeError("sample_words_nar needs the MLM head: a store with task 'word_mask' or 'all' (cls.predictions.*) and an "
                                "engine built with need_lang=True")
-        if getattr(self, "embeds_mode", False):
+        if self.embeds_mode:
             raise ValueError("sample_words_nar feeds token ids: set_inputs(input_ids=...), not inputs_embeds")
         P, T = int(prefix_len), int(n_steps)
         if L > CAPTION_MAX_L:

@@ -599,7 +599,7 @@ class PretrainStep:
         if self.plan_mode and qa_labels is None and not accumulating:
             return self._planned_step()
         losses = self._eager_vis_mask(exchange, update, qa_labels)
-        if qa_labels is not None:               # (qa_labels are copied after the encoder forward: Engine._qa_forward)
+        if qa_labels is not None:               # (qa_labels are copied after the encoder forward: TaskMixin._stage_qa_labels)
             self._mark_consumed(batch)
         return losses
 
