@@ -225,12 +225,15 @@ def fake_ops_for(dtype, res32, evaluate=False):
     return EvalFakeOps(dtype) if evaluate else FakeOpsRes(dtype) if res32 else FakeOps(dtype)
 
 
-def tiny_engine(task, variant, qa=False, need_lang=None, evaluate=False, make_ops=fake_ops_for, device="cpu", wrap=RecordingOps):
+def tiny_engine(task, variant, qa=False, need_lang=None, evaluate=False, make_ops=fake_ops_for, device="cpu", wrap=None):
     """the smallest engine that still takes every branch: test_trainer_cpu.TINY, B=4, L=8, V=16, row lists padded to 8.
     task: the store's task; qa: a task_qa store (NUM_QA answers).  Returns (engine, batch on `device`).
     make_ops / device / wrap (here and in the scenario callables): nothing in the repository passes them; they let the same scenarios
-    run over HipOps on a device under a recorder that also renders streams (profiles/engine_split/gpu_trace_equivalence.txt)."""
+    run over HipOps on a device under a recorder that also renders streams (profiles/engine_split/gpu_trace_equivalence.txt).
+    wrap=None is this module's RecordingOps AS BOUND WHEN THE SCENARIO RUNS: tests/test_stream_audit_cpu.py puts an access-checking
+    proxy under it for every scenario, also those that take no keyword."""
     from test_trainer_cpu import TINY, oracle_cfg
+    wrap = wrap or RecordingOps
     from xlxmert_amd.trainer import synthetic_batch
     dtype, packed, drop, residual = ENGINE_VARIANTS[variant]
     cfg = XLxmertConfig(**dict(TINY, max_position_embeddings=64, num_clusters=100))
@@ -291,8 +294,9 @@ def _step(task, variant, qa=False, switches=None, **stage_kw):
 
 
 def _finetune(task, dtype):
-    def run(make_ops=fake_ops_for, device="cpu", wrap=RecordingOps):
+    def run(make_ops=fake_ops_for, device="cpu", wrap=None):
         import test_engine_cpu as E
+        wrap = wrap or RecordingOps
         make = E.make_vqa_engine if task == "vqa" else E.make_nlvr2_engine
         with env(**ENGINE_ENV):
             eng, inp = make(load_golden(task + "_tiny"), wrap(make_ops(dtype, False, False)), device=device, dtype=dtype)

@@ -147,6 +147,7 @@ class Engine(TaskMixin, SamplerMixin):
         self._pending = {"v": [], "l": []}
         self._held, self._held_layers, self._gen = {"v": [], "l": []}, {"v": 0, "l": 0}, {"v": 0, "l": 0}
         self._pending_block = {"v": "", "l": ""}
+        self._shared_ev, self._shared_pending = None, False      # (see wgrad_defer, once=False)
         self.act_bytes = 0
         st, d = store, self.d
         # ---- blocks
@@ -573,8 +574,11 @@ class Engine(TaskMixin, SamplerMixin):
 
     def wgrad_defer(self, dY, X, dW, M, N, K, lda, ldb, ldc, once=True):
         """register dW[M,N] += dY[K,M]^T X[K,N]; launched with the block's other weight gradients by wgrad_flush().
-        once: this tensor gets no other gradient contribution in the step (False: the MLM decoder tied to the word embeddings)."""
-        self._pending[self._tag].append((dY, X, dW, M, N, K, lda, ldb, ldc, bool(once and self.dw_overwrite), self._gen[self._tag]))
+        once: this tensor gets no other gradient contribution in the step (False: the MLM decoder tied to the word embeddings -- the
+        other contribution, the embedding scatter-add, comes from the language stream: its launch records an event that the scatter-add
+        waits for, see _encoder_backward)."""
+        self._pending[self._tag].append((dY, X, dW, M, N, K, lda, ldb, ldc, bool(once and self.dw_overwrite), self._gen[self._tag],
+                                         not once))
         self._pending_block[self._tag] = getattr(self.ops, "block", "")
 
     def _flat_range(self, dW, M, N, ldc):
@@ -703,6 +707,14 @@ class Engine(TaskMixin, SamplerMixin):
                 if ride and i + 8 >= len(probs):
                     # the column-sum combines pending on this stream ride behind the weight gradients, off the dX chain
                     self.ops.flush_reductions_on(cur)
+            if any(pr[11] for pr in probs[i:i + 8]):
+                # a gradient that ANOTHER stream adds into as well (the tied decoder: the language stream's embedding scatter-add is
+                # not behind this companion stream unless a scratch set happens to be reused in between): an event of its own, never
+                # re-recorded elsewhere, for that stream to wait on
+                if self._shared_ev is None:
+                    self._shared_ev = self.ops.new_event()
+                self.ops.event_record(self._shared_ev, dw)
+                self._shared_pending = True
             self._dw_busy[tag] = True
         if dw is not None:
             ev = self._guard_event(tag)
@@ -1179,6 +1191,7 @@ class Engine(TaskMixin, SamplerMixin):
         self._gen = {"v": 0, "l": 0}
         self._ws_i = {"v": 0, "l": 0}
         self._gen_guard = {"v": {}, "l": {}}    # (the previous backward ended with wgrad_sync_all on both streams)
+        self._shared_pending = False
         self.grad_is_zero = False
         self._lane_lo = {"v": 0, "l": self.store.language_range()[0]}
 
@@ -1293,6 +1306,9 @@ class Engine(TaskMixin, SamplerMixin):
             emb = self.embeds_mode
             if emb:                                   # d(inputs_embeds) instead of d(word_embeddings): see set_inputs
                 ops.zero(self._emb_grad)
+            elif self._shared_pending:                # the tied decoder's weight gradient adds into d(word_embeddings) on a companion
+                ops.stream_wait(self._shared_ev, torch.cuda.current_stream())      # stream of the main stream: behind it, then add
+                self._shared_pending = False
             ops.embed_bwd(dpre, self._emb_ids if emb else self.ids, self.tt,
                           self._emb_grad if emb else st.gview(e + ".word_embeddings.weight"),
                           st.gview(e + ".position_embeddings.weight"), st.gview(e + ".token_type_embeddings.weight"),
