@@ -51,10 +51,17 @@ extern "C" {
 #define XL_EPI_RESIDUAL 2   /* C = dropout(acc+bias) + residual                   HF:276-279, 338-341 */
 #define XL_EPI_DGELU    3   /* C = acc * gelu_erf'(aux)          (backward of XL_EPI_GELU)            */
 #define XL_EPI_TANH     4   /* C = tanh(acc+bias)                                        HF:566-572   */
-#define XL_EPI_ROWMAX   5   /* no C: aux[(n/64)*M + m] = float4{max, sum exp(x - max), argmax (int bits), 0} of x = acc+bias over the
-                             * 64-column segment n/64 of row m -- the sampler's softmax(-1).max(-1) over the 10k codebook without the
+#define XL_EPI_ROWMAX   5   /* no C: aux[(n/64)*M + m] = float4{max, sum exp(x - max), argmax (int bits), 0} of x = alpha * acc + bias over
+                             * the 64-column segment n/64 of row m -- the sampler's softmax(-1).max(-1) over the 10k codebook without the
                              * logits ever reaching memory (ref tasks/imggen_model.py:229-235); finish with xl_rowmax_combine.  bf16
-                             * operands, a_kmajor = b_kmajor = 1, M and N multiples of 256 (pad N with zero rows and bias -1e30) */
+                             * operands, a_kmajor = b_kmajor = 1, M and N multiples of 256 (pad N with zero rows and bias -1e30).
+                             * Pad columns need a bias: bias = NULL means that every column is real (this holds for the two siblings
+                             * below as well).  With a slab workspace on the launch's stream (xl_gemm_set_workspace) a launch of more
+                             * than 256 tiles whose last round is short and whose K reaches the tail-split threshold runs the last
+                             * round's tiles as K slices: their last arriver sums the slices in its registers and runs this epilogue
+                             * over the sums -- the same records within the same bounds, the slices of a tile added in arrival order
+                             * (two slices: one bit pattern; more: the last bits may vary from run to run).  XL_EPI_ROWSAMPLE and
+                             * XL_EPI_ROWSCORE always run whole 256x256 tiles.                                                      */
 #define XL_EPI_GELU_DG  6   /* C = gelu_erf(acc+bias); aux = gelu_erf'(acc+bias): the derivative is saved instead of the
                              * pre-activation (same bytes; erf and exp(-x^2/2) are already in registers), so that the backward
                              * epilogue is a multiply -- XL_EPI_MULAUX -- instead of a second erf + exp per element        */

@@ -89,6 +89,49 @@ def check_totals(before, after, labels, n_cols, got_nll, got_pred, what="totals"
     return [("totals nll sum", r), ("totals count", 0.0), ("totals correct", 0.0)]
 
 
+def rowscore_combine_bounds(ws, n_seg, M, labels, n_cols):
+    """xl_rowscore_combine on the records `ws` it read (fp32, the kernel's own: exact inputs), as bounds.check_rowmax_combine checks
+    xl_rowmax_combine.  The merge of (max, sum exp, argmax) is rowmax_combine_kernel's: row_pred is exact (the lowest column among
+    the segments that hold the global maximum), row_max is exact (a maximum of inputs), lse within bounds.rowmax_combine_bounds;
+    x_label = the maximum over the label slots (one is not -inf) is exact, and row_nll = lse - x_label rounds once more (SLACK U32
+    |nll|, as score_rows_bounds has it); exactly 0 for a label outside [0, n_cols).
+    Returns (nll, its bound, row_pred, row_max, valid)."""
+    mx, se, idx, slot = Bd.rowmax_records(ws, n_seg, M)
+    lse, _, b_lse, _, _ = Bd.rowmax_combine_bounds(mx, se, n_seg)
+    gmx = mx.amax(0)
+    pred = torch.where(mx == gmx[None, :], idx, torch.full_like(idx, 2 ** 31 - 1)).amin(0)
+    valid = valid_labels(labels, n_cols) if labels is not None else torch.zeros(M, dtype=torch.bool, device=ws.device)
+    nll = torch.where(valid, lse - slot.double().amax(0), torch.zeros_like(lse))
+    b_nll = torch.where(valid, b_lse + SLACK * U32 * nll.abs() + TINY, torch.zeros_like(lse))
+    return nll, b_nll, pred, gmx, valid
+
+
+def check_rowscore_combine(ws, n_seg, M, labels, n_cols, got_nll, got_pred, got_max, what="rowscore_combine"):
+    nll, b_nll, pred, gmx, _ = rowscore_combine_bounds(ws, n_seg, M, labels, n_cols)
+    res = []
+    if got_pred is not None:
+        res.append(("row_pred", check_exact(got_pred[:M].long(), pred, f"{what} row_pred")))
+    if got_max is not None:
+        res.append(("row_max", check_exact(got_max[:M].double(), gmx, f"{what} row_max")))
+    if got_nll is not None:
+        res.append(("row_nll", check(got_nll[:M], nll, b_nll, f"{what} row_nll")))
+    return res
+
+
+def check_totals_ref(before, after, valid, hits, nll, b_nll, what="totals"):
+    """check_totals for a launch that returned no row_nll or no row_pred: the counts against `valid` and the float64 hits (exact
+    wherever row_pred is: on the kernel's own records, on logits in memory), the nll sum against the float64 row_nll -- the fp32
+    sum bound of check_totals plus the rows' own bounds sum_m b_nll."""
+    M = valid.numel()
+    assert float(after[1]) == float(before[1]) + int(valid.sum()), (what, "count", float(after[1]), float(before[1]), int(valid.sum()))
+    assert float(after[2]) == float(before[2]) + int(hits.sum()), (what, "correct", float(after[2]), float(before[2]), int(hits.sum()))
+    ref = nll.sum()
+    b = Bd.sum_bound(nll.abs().sum() + b_nll.sum(), M, ref) + b_nll.sum() + U32 * (before[0].double().abs() + after[0].double().abs())
+    r = check((after.double() - before.double())[0:1], ref.reshape(1), b.reshape(1), f"{what} nll sum")
+    check_exact(after[3:4], before[3:4], f"{what} fourth float")
+    return [("totals nll sum", r), ("totals count", 0.0), ("totals correct", 0.0)]
+
+
 def score_rows_bounds(x, labels):
     """xl_score_rows over float64 copies x [M, K] of the fp32 logits it read"""
     M, K = x.shape

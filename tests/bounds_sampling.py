@@ -84,10 +84,51 @@ def check_rows(y, g, e, n_seg, got_p, got_idx, got_lse, what):
     assert bool((y.gather(1, got_idx.long()[:, None])[:, 0] > -1e29).all()), f"{what}: a pad column was drawn"
     n_adm, _ = check_draw(y, g, e, got_idx, f"{what} row draw")
     lse, p, b_lse, b_p, _, _ = lse_prob_bounds(y, e, got_idx, n_seg)
-    res = [("row draw admissible", 0.0),
-           ("row_lse", Bd.check(got_lse, lse, b_lse, f"{what} row_lse")),
-           ("row_prob", Bd.check(got_p, p, b_p, f"{what} row_prob"))]
+    res = [("row draw admissible", 0.0)]
+    if got_lse is not None:                                                          # (an output the call was not given: no row)
+        res.append(("row_lse", Bd.check(got_lse, lse, b_lse, f"{what} row_lse")))
+    if got_p is not None:
+        res.append(("row_prob", Bd.check(got_p, p, b_p, f"{what} row_prob")))
     return res, n_adm[:, 0]
+
+
+def check_combine(ws, n_seg, M, seed, got_p, got_idx, got_lse, what="rowsample_combine"):
+    """xl_rowsample_combine on the records `ws` it read (fp32, the kernel's own: exact inputs), as bounds.check_rowmax_combine checks
+    xl_rowmax_combine.  Nothing new is derived:
+      row_lse    the merge of (max, sum exp) is rowmax_combine_kernel's: bounds.rowmax_combine_bounds
+      row_id     the candidates are the segments' (s, y_s); z_s = y_s + g(seed, m, s) is draw_error with e = 0 (y_s is an input): E = G_ABS
+                 + U32 |z|, none for the candidate of an all-pad segment; bounds.check_admissible over the n_seg candidates of a row, the
+                 lowest column where a row is exact
+      row_prob   exp(y_s - lse) at the kernel's own index: lse_prob_bounds' expression with e_s = 0 and the combine's lse bound
+    Without a row_id the index is the float64 draw's, and a row that admits more than one candidate is left out of row_prob."""
+    import fake_ops_sampling as FS
+    dev = ws.device
+    mx, se, idx, ys = Bd.rowmax_records(ws, n_seg, M)                                # [n_seg, M]
+    lse, _, b_lse, _, _ = Bd.rowmax_combine_bounds(mx, se, n_seg)
+    ys = ys.double()
+    g = FS.gumbel_noise(seed, torch.arange(M, device=dev)[None, :], idx)
+    En, z = draw_error(ys, g, torch.zeros_like(ys))
+    zt, E = z.t().contiguous(), En.amax(0)
+    first = (zt == zt.amax(-1, keepdim=True)).double().argmax(-1)
+    res = []
+    if got_idx is not None:
+        hit = idx == got_idx[:M].long()[None, :]
+        assert bool(hit.any(0).all()), f"{what}: a row_id that is no segment's candidate"
+        seg = hit.double().argmax(0)
+        Bd.check_admissible(zt, seg, E, f"{what} row_id")
+        res.append(("row_id admissible", 0.0))
+        keep = torch.ones(M, dtype=torch.bool, device=dev)
+    else:
+        seg = first
+        keep = Bd.argmax_admissible(zt, first, E)[1] == 1
+    if got_lse is not None:
+        res.append(("row_lse", Bd.check(got_lse[:M], lse, b_lse, f"{what} row_lse")))
+    if got_p is not None:
+        d = ys.gather(0, seg[None, :])[0] - lse
+        p = torch.exp(d)
+        b_p = U32 * p + SLACK * p * (b_lse + 2 * U32 * d.abs() + 3 * U32) + TINY
+        res.append(("row_prob", Bd.check(got_p[:M][keep], p[keep], b_p[keep], f"{what} row_prob")))
+    return res
 
 
 def check_records(aux, y, g, e, what):

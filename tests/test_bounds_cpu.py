@@ -625,8 +625,9 @@ TINY = dict(vocab_size=200, hidden_size=128, num_attention_heads=2, intermediate
             visual_feat_dim=64, num_clusters=96, l_layers=2, x_layers=2, r_layers=2)
 
 
-@pytest.mark.parametrize("workload", ["nar_sampler", "ar_sampler", "vqa", "nlvr2", "word_mask", "matched", "output_attentions"])
-def test_recorded_workloads_pass_over_the_host_restatement(workload):
+@pytest.mark.parametrize("workload", ["nar_sampler", "ar_sampler", "vqa", "nlvr2", "word_mask", "matched", "output_attentions",
+                                      "temperature_sampler", "evaluate_fused", "evaluate_logits"])
+def test_recorded_workloads_pass_over_the_host_restatement(workload, monkeypatch):
     """the recording proxy, every checker and the "must have called" sets of tests/test_workload_bounds_gpu.py, driven here by the
     fp32 host restatement on bf16 storage at a tiny geometry: an honest implementation of every op is inside every bound, and the
     GPU tests' own code runs wherever the suite runs"""
@@ -646,6 +647,15 @@ def test_recorded_workloads_pass_over_the_host_restatement(workload):
         W.nlvr2_step(cfg, O.make_nlvr2_state_dict(oc, 41), 4, "cpu", ops)
     elif workload in ("word_mask", "matched"):
         W.lang_step(cfg, O.make_cls_state_dict(oc, 41), workload, 4, "cpu", ops)
+    elif workload == "temperature_sampler":
+        rec = W.temperature_sampler(cfg, oc, O.make_state_dict(oc, 19), 4, dev="cpu", ops=_predict_ops_cls()(torch.bfloat16))
+        assert len(rec.sharp) == 2
+    elif workload in ("evaluate_fused", "evaluate_logits"):
+        if workload == "evaluate_logits":
+            monkeypatch.setenv("XL_FUSED_PREDICT", "0")
+        cfg, oc = W._cfgs(**dict(TINY, max_position_embeddings=64))          # (64 tokens a row: 256 language rows at bs 4)
+        W.evaluate_tasks(cfg, oc, (O.make_state_dict(oc, 19), O.make_cls_state_dict(oc, 41)), 4, workload == "evaluate_fused", "cpu",
+                         _predict_ops_cls()(torch.bfloat16))
     else:
         W.attentions_forward(cfg, oc, O.make_state_dict(oc, 19), 4, "cpu", ops)
 
@@ -1396,3 +1406,291 @@ def test_sdpa_rejected_calls_raise_and_write_nothing_over_the_restated_argument_
     import test_sdpa_edges_bounds_gpu as S
     from fake_ops_sdpa import Refused, SdpaOps
     S.run_rejected(S.DTYPES[dt], ops=SdpaOps(S.DTYPES[dt], checks=True), dev="cpu", error=Refused)
+
+
+# ------------------------------------------------------------------------------------------------------------------ predict-tail edges
+# tests/test_predict_edges_bounds_gpu.py over the host restatement: the same calls (tests/predict_edge_cases.py), the same recorder,
+# the same label, count and outside-view assertions.  The 272-tile shape runs for the XL_EPI_ROWMAX arm only.
+def _predict_ops_cls():
+    from fake_ops_eval import EvalFakeOps
+    from fake_ops_sampling import SamplingFakeOps, first_argmax
+
+    class PredictOps(SamplingFakeOps, EvalFakeOps):
+        """FakeOps with the XL_EPI_ROWSAMPLE and the XL_EPI_ROWSCORE branches of gemm and the combines / logits kernels of both (each
+        gemm passes an epilogue it does not know on to the next class); XL_EPI_ROWMAX with the documented tie rule spelled out.  alpha
+        and a NULL bias are FakeOps.gemm's own: x = alpha acc (+ bias)."""
+
+        def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1, out_f32=False,
+                 epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
+            if epilogue != BD.EPI_ROWMAX:
+                return super().gemm(A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr, ldx, a_kmajor, b_kmajor, out_f32,
+                                    epilogue, alpha, accumulate, p_drop, seed, colsum, ws)
+            self.calls.append(("gemm", M, N, K, a_kmajor, b_kmajor, epilogue))
+            x = alpha * (torch.as_strided(A, (M, K), (lda, 1)).to(self.compute) @ torch.as_strided(B, (N, K), (ldb, 1)).to(self.compute).t())
+            if bias is not None:
+                x = x + torch.as_strided(bias, (N,), (1,)).to(self.compute)[None, :]
+            n_seg = N // 64
+            xs = x.view(M, n_seg, 64)
+            loc = first_argmax(xs)
+            mx = xs.amax(-1)
+            rec = aux.view(-1)[:n_seg * M * 4].view(n_seg, M, 4)
+            rec[..., 0].copy_(mx.t())
+            rec[..., 1].copy_(torch.exp(xs - mx[..., None]).sum(-1).t())
+            rec.view(torch.int32)[..., 2].copy_((loc + torch.arange(n_seg)[None, :] * 64).to(torch.int32).t())
+            rec[..., 3].zero_()
+    return PredictOps
+
+
+PREDICT_EDGE_RUNS = {"fused": ("run_fused", {}), "rounds-two_rounds": ("run_rounds", dict(tail=False, epis=(BD.EPI_ROWMAX,))),
+                     "rounds-tail_split": ("run_rounds", dict(tail=True, epis=(BD.EPI_ROWMAX,))),
+                     **{f"switches-{sw}": ("run_switches", dict(sw=sw)) for sw in ("mfma_128_only", "duo_everywhere", "wgrad_slabs")},
+                     "combines": ("run_combines", {}), "logits": ("run_logits", {})}
+
+
+@pytest.mark.parametrize("run", list(PREDICT_EDGE_RUNS))
+def test_predict_edge_cases_pass_over_the_host_restatement(run):
+    """an honest implementation (fp32 arithmetic on bf16 storage that reads the logical extents only and stores into the logical
+    views only) is inside every bound at the inputs of the edge cases, the ambiguity cap holds at every launch (asserted inside the
+    case module), and every sweep reaches the kernel labels the GPU tests expect"""
+    import test_predict_edges_bounds_gpu as P
+    fn, kw = PREDICT_EDGE_RUNS[run]
+    ops = _predict_ops_cls()(torch.bfloat16)
+    if fn == "run_switches":
+        kw = dict(kw, ops_default=_predict_ops_cls()(torch.bfloat16))
+    getattr(P, fn)(ops=ops, dev="cpu", **kw)
+
+
+def _last_argmax(z):
+    n = z.shape[-1]
+    return n - 1 - (z.flip(-1) == z.amax(-1, keepdim=True)).to(torch.uint8).argmax(-1)
+
+
+def _faulty_predict_ops(fault):
+    """the host restatement of the predict tail with ONE kernel fault, applied at every call it can apply to (`applied` counts the
+    calls it changed):
+      pad_as_k_term                         the leading-dimension pad element behind the last row of A enters as one more K term
+      ragged_k_tile_dropped                 the last, ragged K tile (K % 64 of a K above 64) is dropped
+      alpha_ignored_by_rowmax               XL_EPI_ROWMAX computes acc + bias
+      bias_of_first_column_tile_everywhere  every column tile adds the bias of columns 0 .. 255
+      tie_to_higher_column                  an exact tie inside a segment (a row of logits in memory) goes to the higher column
+      tie_to_later_segment_in_combine       equal maxima of two segments: the combine keeps the later segment's column
+      label_truncated_to_32_bits            the epilogue cuts a label to its low 32 bits (2^32 + 5 becomes column 5)
+      labels_of_row_m_plus_64_swapped       the two quads of a wave's 128 rows take each other's labels
+      second_row_tile_reads_first_tiles_labels   labels[m % 256]
+      pad_column_label_counted_valid        the combine accepts a label below 64 n_seg instead of below n_cols
+      noise_row_local_to_tile               the noise function is given the row inside the tile
+      noise_column_local_to_segment         the noise function is given the column inside the segment
+      rows_past_grid_cap_skipped            the scores kernels stop at 1024 blocks: later rows are neither written nor counted
+      totals_ticket_not_reset               a ticket set is left at its last count: its second launch never finds a last block
+      record_stored_past_aux                one record lands behind the (N / 64) M records of aux"""
+    Base = _predict_ops_cls()
+    from fake_ops_sampling import EPI_ROWSAMPLE, gumbel_noise
+    from fake_ops_eval import EPI_ROWSCORE
+    ROW = (BD.EPI_ROWMAX, EPI_ROWSAMPLE, EPI_ROWSCORE)
+
+    class FaultyPredictOps(Base):
+        def __init__(self):
+            super().__init__(torch.bfloat16)
+            self.fault, self.applied, self.totals_launches, self._in_gemm = fault, 0, 0, False
+
+        def _g(self, seed, M, cols, device):
+            rows = torch.arange(M, device=device)
+            if self._in_gemm and self.fault == "noise_row_local_to_tile":
+                rows = rows % 256
+            if self._in_gemm and self.fault == "noise_column_local_to_segment":
+                cols = cols % 64
+            return gumbel_noise(seed, rows[:, None], cols[None, :], self.compute, self.noise)
+
+        def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1, out_f32=False,
+                 epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
+            f = self.fault
+            assert epilogue in ROW
+            n_seg = N // 64
+            if f == "pad_as_k_term" and lda > K:
+                A2 = torch.zeros(M, K + 1, dtype=A.dtype)
+                A2[:, :K] = torch.as_strided(A, (M, K), (lda, 1))
+                A2[M - 1, K] = A[(M - 1) * lda + K]
+                B2 = torch.zeros(N, K + 1, dtype=B.dtype)
+                B2[:, :K] = torch.as_strided(B, (N, K), (ldb, 1))
+                B2[:, K] = B2[:, K - 1]
+                A, B, K, lda, ldb = A2.reshape(-1), B2.reshape(-1), K + 1, K + 1, K + 1
+                self.applied += 1
+            if f == "ragged_k_tile_dropped" and K > 64 and K % 64:
+                K -= K % 64
+                self.applied += 1
+            if f == "alpha_ignored_by_rowmax" and epilogue == BD.EPI_ROWMAX and alpha != 1.0:
+                alpha = 1.0
+                self.applied += 1
+            if f == "bias_of_first_column_tile_everywhere" and bias is not None and N > 256:
+                bias = torch.as_strided(bias, (256,), (1,)).repeat(N // 256)
+                self.applied += 1
+            if epilogue == EPI_ROWSCORE:
+                lab = residual.reshape(-1)[:M].clone()
+                if f == "label_truncated_to_32_bits":
+                    lab = ((lab & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000
+                if f == "labels_of_row_m_plus_64_swapped":
+                    lab = lab.view(M // 128, 2, 64).flip(1).reshape(-1)
+                if f == "second_row_tile_reads_first_tiles_labels":
+                    lab = lab[torch.arange(M) % 256]
+                self.applied += int(not torch.equal(lab, residual.reshape(-1)[:M]))
+                residual = lab
+            self._in_gemm = True
+            self.applied += int(epilogue == EPI_ROWSAMPLE and ((f == "noise_row_local_to_tile" and M > 256)
+                                                               or (f == "noise_column_local_to_segment" and N > 64)))
+            super().gemm(A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr, ldx, a_kmajor, b_kmajor, out_f32, epilogue, alpha,
+                         accumulate, p_drop, seed, colsum, ws)
+            self._in_gemm = False
+            if f == "tie_to_higher_column" and epilogue != EPI_ROWSAMPLE:
+                x = alpha * (torch.as_strided(A, (M, K), (lda, 1)).float() @ torch.as_strided(B, (N, K), (ldb, 1)).float().t())
+                if bias is not None:
+                    x = x + torch.as_strided(bias, (N,), (1,))[None, :]
+                idx = (_last_argmax(x.view(M, n_seg, 64)) + torch.arange(n_seg)[None, :] * 64).to(torch.int32).t()
+                slot = aux.view(-1)[:n_seg * M * 4].view(n_seg, M, 4).view(torch.int32)[..., 2]
+                self.applied += int(not torch.equal(slot, idx))
+                slot.copy_(idx)
+            if f == "record_stored_past_aux":
+                torch.as_strided(aux, (4,), (1,), aux.storage_offset() + n_seg * M * 4).fill_(1.0)
+                self.applied += 1
+
+        def _later_segment(self, ws, n_seg, M, out):
+            if self.fault != "tie_to_later_segment_in_combine" or out is None:
+                return
+            rec = ws.view(-1)[:n_seg * M * 4].view(n_seg, M, 4)
+            mx, idx = rec[..., 0], rec.view(torch.int32)[..., 2]
+            last = torch.where(mx == mx.amax(0)[None, :], idx, torch.full_like(idx, -1)).amax(0)
+            self.applied += int(not torch.equal(out[:M], last))
+            out[:M].copy_(last)
+
+        def rowmax_combine(self, ws, n_seg, M, row_maxprob, row_argmax, row_lse=None):
+            super().rowmax_combine(ws, n_seg, M, row_maxprob, row_argmax, row_lse)
+            self._later_segment(ws, n_seg, M, row_argmax)
+
+        def _totals(self, totals):
+            """the ticket fault: the launch whose ticket set was used before never sees a last block -- totals stay as they are"""
+            if totals is None:
+                return None
+            self.totals_launches += 1
+            if self.fault == "totals_ticket_not_reset" and self.totals_launches > 8:
+                self.applied += 1
+                return None
+            return totals
+
+        def rowscore_combine(self, ws, n_seg, M, labels, n_cols, row_nll=None, row_pred=None, row_max=None, totals=None):
+            f = self.fault
+            totals = self._totals(totals)
+            if f == "pad_column_label_counted_valid" and labels is not None:
+                lab = labels.reshape(-1)[:M]
+                if bool(((lab >= n_cols) & (lab < 64 * n_seg)).any()):
+                    n_cols = 64 * n_seg
+                    self.applied += 1
+            if f == "rows_past_grid_cap_skipped" and M > 64 * 1024:
+                assert n_seg == 1
+                M = 64 * 1024
+                self.applied += 1
+            super().rowscore_combine(ws, n_seg, M, labels, n_cols, row_nll, row_pred, row_max, totals)
+            self._later_segment(ws, n_seg, M, row_pred)
+
+        def score_rows(self, logits, M, K, ldl, labels, row_nll=None, row_pred=None, row_max=None, totals=None):
+            totals = self._totals(totals)
+            if self.fault == "rows_past_grid_cap_skipped" and M > 4 * 1024:
+                M = 4 * 1024
+                self.applied += 1
+            super().score_rows(logits, M, K, ldl, labels, row_nll, row_pred, row_max, totals)
+            if self.fault == "tie_to_higher_column" and row_pred is not None:
+                last = _last_argmax(torch.as_strided(logits, (M, K), (ldl, 1)))
+                self.applied += int(not torch.equal(row_pred[:M].long(), last))
+                row_pred[:M].copy_(last)
+    return FaultyPredictOps()
+
+
+PREDICT_FAULTS = {
+    "pad_as_k_term": ("fused",), "ragged_k_tile_dropped": ("fused",), "alpha_ignored_by_rowmax": ("fused",),
+    "bias_of_first_column_tile_everywhere": ("fused",), "tie_to_higher_column": ("fused", "logits"),
+    "tie_to_later_segment_in_combine": ("fused", "combines"), "label_truncated_to_32_bits": ("fused",),
+    "labels_of_row_m_plus_64_swapped": ("fused",), "second_row_tile_reads_first_tiles_labels": ("fused",),
+    "pad_column_label_counted_valid": ("fused", "combines"), "noise_row_local_to_tile": ("fused",),
+    "noise_column_local_to_segment": ("fused",), "rows_past_grid_cap_skipped": ("combines", "logits"),
+    "totals_ticket_not_reset": ("combines",), "record_stored_past_aux": ("fused",)}
+PREDICT_FAULT_SWEEPS = {"fused": dict(shapes=None), "combines": dict(strict=False), "logits": dict(Ks=(2, 65))}
+
+
+@pytest.mark.parametrize("fault", list(PREDICT_FAULTS))
+def test_predict_edge_cases_reject_plausible_kernel_faults(fault):
+    """the same recorder runs as the honest pass, over an implementation with one fault: it must fail at EVERY call the fault
+    changed (each such call shows the fault on its own), and only there"""
+    import re
+    import predict_edge_cases as PE
+    import test_predict_edges_bounds_gpu as P
+    for family in PREDICT_FAULTS[fault]:
+        ops = _faulty_predict_ops(fault)
+        kw = dict(PREDICT_FAULT_SWEEPS[family])
+        if family == "fused":
+            kw["shapes"] = PE.FUSED_SHAPES
+        rec, n = getattr(P, "run_" + family)(ops=ops, dev="cpu", **kw)
+        assert len(rec.checked) + len(rec.failures) == n and ops.applied > 0, (family, len(rec.checked), len(rec.failures), n, ops.applied)
+        print(f"{fault} / {family}: applied at {ops.applied} of {n} calls, {len(rec.failures)} failed")
+        assert len(rec.failures) == ops.applied, (fault, family, ops.applied, len(rec.failures), rec.failures[:3])
+        word = "outside" if fault == "record_stored_past_aux" else "beyond their bound|differ|not admissible|count|correct|candidate"
+        assert all(re.search(word, f) for f in rec.failures), rec.failures[:3]
+
+
+class RejectingPredictOps:
+    """the argument checks xl_gemm makes for the three row-reducing epilogues, and those of the combines and logits kernels, restated
+    (csrc/gemm.hip, csrc/rowops.hip): (-1) XL_ERR_BAD_SHAPE, (-5) XL_ERR_BAD_ARG.  Nothing is computed: every call of the rejected
+    family must be refused."""
+
+    def __init__(self, dtype):
+        self.dtype, self.tr_read = dtype, True
+
+    def set_lds_transpose_read(self, enable):
+        self.tr_read = bool(enable)
+
+    def workspace_floats(self, N):
+        return 256 * 10 * N
+
+    @staticmethod
+    def _al(t, k=16):
+        return t is not None and t.data_ptr() % k == 0
+
+    def gemm(self, A, B, C, bias, residual, aux, M, N, K, lda, ldb, ldc, ldr=0, ldx=0, a_kmajor=1, b_kmajor=1, out_f32=False,
+             epilogue=EPI_NONE, alpha=1.0, accumulate=0, p_drop=0.0, seed=0, colsum=None, ws=None):
+        assert epilogue in (5, 9, 10) and M > 0 and N > 0 and K > 0
+        ok = (self.dtype == torch.bfloat16 and A.dtype == torch.bfloat16 and a_kmajor and b_kmajor and M % 256 == 0 and N % 256 == 0
+              and K % 8 == 0 and lda % 8 == 0 and ldb % 8 == 0 and self._al(aux) and self._al(A) and self._al(B)
+              and (bias is None or self._al(bias)) and not accumulate and colsum is None and self.tr_read)
+        if epilogue in (9, 10):
+            ok = ok and p_drop == 0
+        if epilogue == 10:
+            ok = ok and self._al(residual, 8)
+        if not ok:
+            raise Refused(f"xl_gemm failed (-1): the row-reducing epilogue {epilogue} takes bf16 K-major operands with M, N multiples of 256")
+        raise AssertionError("not reached by the rejected family")
+
+    def _combine(self, what, ws, n_seg, M, n_cols=1):
+        if not (ws is not None and n_seg > 0 and M > 0 and self._al(ws) and 0 < n_cols <= 64 * n_seg):
+            raise Refused(f"{what} failed (-5): bad args")
+        raise AssertionError("not reached by the rejected family")
+
+    def rowmax_combine(self, ws, n_seg, M, row_maxprob, row_argmax, row_lse=None):
+        self._combine("xl_rowmax_combine", ws, n_seg, M)
+
+    def rowsample_combine(self, ws, n_seg, M, seed, row_prob, row_id, row_lse=None):
+        self._combine("xl_rowsample_combine", ws, n_seg, M)
+
+    def rowscore_combine(self, ws, n_seg, M, labels, n_cols, row_nll=None, row_pred=None, row_max=None, totals=None):
+        self._combine("xl_rowscore_combine", ws, n_seg, M, n_cols)
+
+    def score_rows(self, logits, M, K, ldl, labels, row_nll=None, row_pred=None, row_max=None, totals=None):
+        if not (logits is not None and M > 0 and K > 0 and ldl >= K):
+            raise Refused(f"xl_score_rows failed (-5): M={M} K={K} ldl={ldl}")
+        raise AssertionError("not reached by the rejected family")
+
+    def sample_rows(self, logits, M, K, ldl, inv_T, seed, row_prob, row_id, row_lse=None):
+        if not (logits is not None and M > 0 and K > 0 and ldl >= K and 0 < inv_T < math.inf):
+            raise Refused(f"xl_sample_rows failed (-5): M={M} K={K} ldl={ldl} inv_T={inv_T}")
+        raise AssertionError("not reached by the rejected family")
+
+
+def test_predict_rejected_calls_raise_and_write_nothing_over_the_restated_argument_checks():
+    import test_predict_edges_bounds_gpu as P
+    P.run_rejected(ops=RejectingPredictOps(torch.bfloat16), ops_f32=RejectingPredictOps(torch.float32), dev="cpu", error=Refused)

@@ -13,7 +13,13 @@ flush covers, or a destination that also received an unrecorded contribution, fa
 
 Stray stores.  Around every gemm / gemm_wgrad_group call the whole storage of every output (C, a written aux, the column-sum
 target) is held bit for bit -- as integers -- to its content before the call everywhere outside the logical views the call may
-write: the row "C outside view".  A store into a pad column of C or past row M-1 lands in a neighbouring tensor.
+write: the row "C outside view".  A store into a pad column of C or past row M-1 lands in a neighbouring tensor.  The launches without a
+C (XL_EPI_ROWMAX / ROWSAMPLE / ROWSCORE) hold the storage of aux outside its (N / 64) M records of four floats: "aux outside view".
+
+The predict tail.  Those three epilogues are checked record by record against the float64 logits alpha A B^T + bias (alpha and a NULL
+bias included), their combines and the logits twins xl_sample_rows / xl_score_rows on what they read, and a combine behind a checked
+launch once more against the float64 logits of the whole row ("composed" rows).  Recorder(ops, every_call=True) checks every call,
+whether or not its signature was seen: alpha, seeds and temperatures are no part of a signature (tests/predict_edge_cases.py).
 
 Kernel labels.  The recorder remembers the GEMM switches it forwards (set_gemm_pingpong / _duo / _wgrad_slabs / _tail_split,
 set_lds_transpose_read, the slab workspace registered per stream); gemm_kernel / wgrad_group_kernel restate the dispatch of
@@ -33,8 +39,12 @@ import pytest
 import torch
 
 import bounds as BD
+import bounds_eval as BE
+import bounds_sampling as BS
 import lxmert_oracle as O
 from fake_ops import FakeOps, ce_in_regs, keep_scale
+from fake_ops_eval import EPI_ROWSCORE
+from fake_ops_sampling import EPI_ROWSAMPLE, gumbel_noise
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +59,7 @@ NON_NUMERIC = {"zero", "stream_fork", "new_event", "event_record", "stream_wait"
 
 
 # sampler ops: the signature also carries the step index (Recorder.mark), so that every refinement step is checked
-STEP_KEYED = {"rowmax_combine", "remask_lowest", "sampler_update", "sampler_ar_update"}
+STEP_KEYED = {"rowmax_combine", "rowsample_combine", "remask_lowest", "sampler_update", "sampler_ar_update"}
 # the column-sum outputs whose second stage xl_set_deferred_reduce(1) postpones to the next flush of the producing stream
 REDUCE_OUTS = {"gemm": ("colsum",), "layernorm_bwd": ("dgamma", "dbeta", "dbias_prev"), "sdpa_bwd": ("bias_grad",),
                "visn_ln_bwd": ("dgv", "dbv", "dgb", "dbb", "dwbox", "dbbox", "dbias_visn"), "colsum": ("out",),
@@ -87,6 +97,23 @@ def _ws_holds(sw, tiles, slabs):
     return sw["ws_slabs"] > 0 and tiles * 4 <= 16384 and slabs <= sw["ws_slabs"]
 
 
+ROW_EPILOGUES = {5: "ROWMAX", 9: "ROWSAMPLE", 10: "ROWSCORE"}      # no C: segment records in aux (include/xlxmert_hip.h)
+
+
+def _tail_split(sw, tiles, K):
+    """the tail split of a ping-pong launch of 256x256 tiles: more than one round, a last round of at most tail_max tiles, K >=
+    tail_min_k, and a slab workspace on the stream that holds the remainder's slices -> the label suffix, "" without a split"""
+    if tiles > 256 and 0 < tiles % 256 <= sw["tail_max"] and K >= sw["tail_min_k"]:
+        rem = tiles % 256
+        S = min(256 // rem, K // 512, 8)
+        if S >= 2:
+            kper_t = ((K + S - 1) // S + 63) // 64 * 64
+            S = (K + kper_t - 1) // kper_t
+            if S >= 2 and _ws_holds(sw, rem, rem * S):
+                return f" + tail split {rem}x{S}"
+    return ""
+
+
 def gemm_vec_epi(C, ldc, out_f32, epilogue, residual=None, ldr=0, aux=None, ldx=0):
     """p.vec_epi of xl_gemm: 16-byte rows of C and of the epilogue's operand"""
     v = bool(_al16(C)) and (ldc % 4 == 0 if out_f32 else ldc % 8 == 0)
@@ -113,6 +140,12 @@ def gemm_kernel(M, N, K, lda, ldb, A, B, out_f32, epilogue, a_kmajor=1, b_kmajor
     ragged edge tiles take the scalar store), " + fused colsum" / " + separate colsum".  Held against the kernel names of a
     rocprofv3 --kernel-trace run of tests/test_gemm_edges_bounds_gpu.py once: profiles/bounds_gemm_edges.txt."""
     sw = dict(gemm_switches(), **(sw or {}))
+    if epilogue in ROW_EPILOGUES:
+        # XL_EPI_ROWMAX / ROWSAMPLE / ROWSCORE: the preconditions leave bf16 K-major operands on whole 256x256 tiles, and use_pp is
+        # forced whatever set_gemm_pingpong says; no duo / 192-wide tile, no K split.  ROWMAX alone is not excluded from the tail split
+        # (its siblings are, and assert tail_tiles == 0): the last tiles run as K slices whose last arriver runs the epilogue
+        name = f"ping-pong 256x256 {ROW_EPILOGUES[epilogue]} epilogue"
+        return name + (_tail_split(sw, (M // 256) * (N // 256), K) if epilogue == BD.EPI_ROWMAX else "")
     mfma = A.dtype == torch.bfloat16 and lda % 8 == 0 and ldb % 8 == 0 and bool(_al16(A)) and bool(_al16(B))
     may_split = mfma and out_f32 and epilogue == BD.EPI_NONE
     t256 = ((M + 255) // 256) * ((N + 255) // 256)
@@ -148,14 +181,8 @@ def gemm_kernel(M, N, K, lda, ldb, A, B, out_f32, epilogue, a_kmajor=1, b_kmajor
         name += f" split-K {split} " + ("slabs" if slabs else "atomics")
     elif accumulate:
         name += " += atomics"
-    if pp and not duo and split == 1 and not atomic and tiles > 256 and 0 < tiles % 256 <= sw["tail_max"] and K >= sw["tail_min_k"]:
-        rem = tiles % 256
-        S = min(256 // rem, K // 512, 8)
-        if S >= 2:
-            kper_t = ((K + S - 1) // S + 63) // 64 * 64
-            S = (K + kper_t - 1) // kper_t
-            if S >= 2 and _ws_holds(sw, rem, rem * S):
-                name += f" + tail split {rem}x{S}"
+    if pp and not duo and split == 1 and not atomic:
+        name += _tail_split(sw, tiles, K)
     ragged = tile is not None and (M % tile or N % tile)
     if mfma and not atomic:
         if not vec_epi:
@@ -338,6 +365,7 @@ def _k_schedule(a):
     return "schedule_step_kernel decay" + (" clamped" if done >= a["total_steps"] else "")
 
 
+SCORE_MAX_BLOCKS = 1024       # csrc/rowops.hip: the grid cap of rowscore_combine_kernel (64 rows a block) and score_rows_kernel (4 rows)
 _ROWOP = {
     "layernorm_fwd": lambda a: f"ln_fwd_kernel<{_tn(a['x'])}> NIT={_nit(a['N'], 64 * _vec(a['x']))}",
     "layernorm_bwd": _k_layernorm_bwd,
@@ -364,6 +392,12 @@ _ROWOP = {
     "cast_from_f32": lambda a: f"cast_from_f32_kernel<{_tn(a['dst'])}>",
     "cast_to_f32": lambda a: f"cast_to_f32_kernel<{_tn(a['src'])}>",
     "take_f32": lambda a: "take_f32_kernel", "put_f32": lambda a: "put_f32_kernel",
+    "rowsample_combine": lambda a: "rowsample_combine_kernel",
+    "rowscore_combine": lambda a: ("rowscore_combine_kernel" + (" second pass" if _cdiv(a["M"], 64) > SCORE_MAX_BLOCKS else "")
+                                   + (" + totals" if a["totals"] is not None else "")),
+    "sample_rows": lambda a: "sample_rows_kernel",
+    "score_rows": lambda a: ("score_rows_kernel" + (" second pass" if _cdiv(a["M"], 4) > SCORE_MAX_BLOCKS else "")
+                             + (" + totals" if a["totals"] is not None else "") + ("" if a["labels"] is not None else " no labels")),
     "rowmax_combine": lambda a: "rowmax_combine_kernel", "remask_lowest": lambda a: "remask_lowest_kernel",
     "sampler_update": lambda a: "sampler_update_kernel",
     "sampler_ar_update": lambda a: "sampler_ar_update_kernel " + ("(fixed position)" if a["fixed_pos"] >= 0 else "(most confident)"),
@@ -383,6 +417,8 @@ def rowop_kernel(name, a):
       colsum_kernel rows_per_block=R slabs=G   (R doubles until G <= 128 with a workspace)
       ce_row_kernel<4,1024> / <5,256> / <2,256> [row loop]  or  ce_kernel (scalar)
       sumsq_kernel grid=G [unrolled] [single] [tail];  adamw_kernel passes=k ...;  schedule_step_kernel warm-up / decay [clamped]
+      rowscore_combine_kernel / score_rows_kernel [second pass] [+ totals] [no labels]   second pass: more than 1024 blocks of 64 / 4
+                     rows, the blocks walk on by the grid
     An entry point without a branch is labelled by its kernel and element type."""
     f = _ROWOP.get(name)
     return f(a) if f is not None else name
@@ -522,6 +558,12 @@ ROW_OUTS = {
     "schedule_step": lambda a: [_t(a["step"], 1), _t(a["lr_and_steps"], 4)],
     "adamw": _o_adamw,
     "rowmax_combine": lambda a: [_t(a["row_maxprob"], a["M"]), _t(a["row_argmax"], a["M"]), _t(a["row_lse"], a["M"])],
+    "rowsample_combine": lambda a: [_t(a["row_prob"], a["M"]), _t(a["row_id"], a["M"]), _t(a["row_lse"], a["M"])] + _held(a["ws"]),
+    "sample_rows": lambda a: [_t(a["row_prob"], a["M"]), _t(a["row_id"], a["M"]), _t(a["row_lse"], a["M"])] + _held(a["logits"]),
+    "rowscore_combine": lambda a: [_t(a["row_nll"], a["M"]), _t(a["row_pred"], a["M"]), _t(a["row_max"], a["M"]), _t(a["totals"], 3)]
+    + _held(a["ws"], a["labels"]),
+    "score_rows": lambda a: [_t(a["row_nll"], a["M"]), _t(a["row_pred"], a["M"]), _t(a["row_max"], a["M"]), _t(a["totals"], 3)]
+    + _held(a["logits"], a["labels"]),
     "remask_lowest": lambda a: [_t(a["vis_mask"], a["B"] * a["V"])],
     "sampler_update": lambda a: [_t(a["code_ids"], a["n"])],
     "sampler_ar_update": lambda a: [_t(a[k], a["B"] * a["V"]) for k in ("code_ids", "vis_mask", "visited")],
@@ -532,8 +574,11 @@ ROW_OUTS = {
 class Recorder:
     """stands in for the step's HipOps: forwards every attribute, checks the first call of each signature"""
 
-    def __init__(self, ops):
+    def __init__(self, ops, every_call=False):
         object.__setattr__(self, "_ops", ops)
+        object.__setattr__(self, "_every", bool(every_call))      # check every call, whether or not its signature was seen before
+        object.__setattr__(self, "_rowrec", {})         # aux pointer -> (epilogue, float64 logits, error, noise / labels) of a checked
+        #                                                 XL_EPI_ROWSAMPLE / ROWSCORE launch, for the composed check at its combine
         object.__setattr__(self, "_ref", FakeOps(ops.dtype, compute=torch.float64))
         object.__setattr__(self, "_seen", set())
         object.__setattr__(self, "rows", [])
@@ -647,17 +692,17 @@ class Recorder:
                 key += (("kernel", self._sdpa_kernel(name[5:], a)[0]),)
             elif name == "attn_probs":
                 key += (("kernel", "attn_probs_kernel"), ("n_kblk", (a["nk"] + 63) // 64))
-            elif name == "gemm" and a["epilogue"] != BD.EPI_ROWMAX:     # (the same for the GEMM switches and leading dimensions)
+            elif name == "gemm":                    # (the same for the GEMM switches and leading dimensions)
                 key += (("kernel", self._gemm_kernel(a)),)
             elif name == "gemm_wgrad_group":
                 key += (("kernel", tuple(wgrad_group_kernel(a["problems"], a["overwrite_mask"], self._switches())[1])),)
             elif name in self._rowops():            # (the same for the launchers of csrc/rowops.hip and csrc/optim.hip)
                 object.__setattr__(self, "_kern", rowop_kernel(name, a))
                 key += (("kernel", self._kern),)
-            if name in STEP_KEYED or (name == "gemm" and a["epilogue"] == BD.EPI_ROWMAX):
+            if name in STEP_KEYED or (name == "gemm" and a["epilogue"] in (BD.EPI_ROWMAX, EPI_ROWSAMPLE)):
                 key += (("step", self._tag),)
             dests = self._dests(name, a) if self._deferred else []
-            force = self._overlaps_recorded(dests) or key in self._force
+            force = self._overlaps_recorded(dests) or key in self._force or self._every
             if key in self._seen and not force:
                 self._note_dests(dests, False, key)
                 return attr(*args, **kw)
@@ -806,16 +851,21 @@ class Recorder:
         return " ".join(f"{k}={a[k]}" for k in keys if k in a and not isinstance(a[k], torch.Tensor))
 
     # ------------------------------------------------------------------------------------------------ contractions
-    def _gemm_pre(self, s, M, N, K):
+    def _gemm_pre(self, s, M, N, K, parts=False):
+        """float64 alpha A B^T + bias and |alpha| |A| |B|^T + |bias| (alpha as the kernel receives it: fp32); parts: also the
+        contraction's share |alpha| |A| |B|^T alone and |bias| [1, N] (zeros without a bias), what bounds.rowmax_logit_error takes"""
         A = (_v2(s["A"], M, K, s["lda"]) if s["a_kmajor"] else _v2(s["A"], K, M, s["lda"]).t())
         B = (_v2(s["B"], N, K, s["ldb"]) if s["b_kmajor"] else _v2(s["B"], K, N, s["ldb"]).t())
-        al = float(s["alpha"])
+        al = float(torch.tensor(float(s["alpha"]), dtype=torch.float32))
         pre = al * (A @ B.t())
-        absprod = abs(al) * (A.abs() @ B.abs().t())
+        absdot = abs(al) * (A.abs() @ B.abs().t())
+        b_abs = torch.zeros(1, N, dtype=torch.float64, device=pre.device)
+        absprod = absdot
         if s["bias"] is not None:
             b = torch.as_strided(s["bias"], (N,), (1,))
-            pre, absprod = pre + b[None, :], absprod + b.abs()[None, :]
-        return pre, absprod
+            b_abs = b.abs()[None, :]
+            pre, absprod = pre + b[None, :], absdot + b_abs
+        return (pre, absprod, absdot, b_abs) if parts else (pre, absprod)
 
     def _switches(self):
         """the forwarded switches with the slab workspace of the CURRENT stream (where the next call is queued)"""
@@ -857,8 +907,8 @@ class Recorder:
 
     def chk_gemm(self, a, s, run):
         M, N, K, epi = a["M"], a["N"], a["K"], a["epilogue"]
-        if epi == BD.EPI_ROWMAX:
-            return self._chk_gemm_rowmax(a, s, run)
+        if epi in ROW_EPILOGUES:
+            return self._chk_gemm_rows(a, s, run)
         outs = [(a["C"], (M, N), (a["ldc"], 1))]
         if epi in (BD.EPI_GELU, BD.EPI_GELU_DG):
             outs.append((a["aux"], (M, N), (a["ldx"], 1)))
@@ -894,20 +944,37 @@ class Recorder:
             self._sum_out(res, "colsum", torch.as_strided(a["colsum"], (N,), (1,)), ref_cs, cs_prev, bcs, kern)
         return res
 
-    def _chk_gemm_rowmax(self, a, s, run):
-        """XL_EPI_ROWMAX: no C; the segment records in aux against float64 logits (bounds.check_rowmax_records).  The logits and
-        their error stay with the recorder for the composed check at the rowmax_combine that reads these records."""
-        M, N, K = a["M"], a["N"], a["K"]
-        assert a["a_kmajor"] and a["b_kmajor"] and a["alpha"] == 1.0 and a["bias"] is not None
-        A, B = _v2(s["A"], M, K, a["lda"]), _v2(s["B"], N, K, a["ldb"])
-        b = torch.as_strided(s["bias"], (N,), (1,))
-        pre = A @ B.t() + b[None, :]
-        e = BD.rowmax_logit_error(pre, A.abs() @ B.abs().t(), b.abs()[None, :], K)
+    def _chk_gemm_rows(self, a, s, run):
+        """XL_EPI_ROWMAX / ROWSAMPLE / ROWSCORE: no C; the segment records in aux against the float64 logits x = alpha A B^T + bias
+        (bounds.check_rowmax_records, bounds_sampling.check_records, bounds_eval.check_rowscore_records), and the storage of aux
+        outside its (N / 64) M records of four floats held to its earlier bits.
+        alpha and a NULL bias need no term of their own: bounds.rowmax_logit_error is K U32 (|alpha| |A| |B|^T + |bias|) + 2 U32 |x|
+        as bounds.gemm_bounds has it, so _gemm_pre's |alpha|-scaled contraction share and a bias share of zero go in as they are
+        (alpha scales the fp32 accumulator once: one rounding, inside the 2 U32 |x|; without a bias no addition follows).
+        The logits and their error stay with the recorder for the composed check at the combine that reads these records."""
+        M, N, K, epi = a["M"], a["N"], a["K"], a["epilogue"]
+        assert a["a_kmajor"] and a["b_kmajor"] and a["C"] is None and N % 64 == 0
+        n_seg = N // 64
+        guard = self._guard([(a["aux"], (n_seg * M * 4,), (1,))], "aux outside view")
+        pre, _, absdot, b_abs = self._gemm_pre(s, M, N, K, parts=True)
+        e = BD.rowmax_logit_error(pre, absdot, b_abs, K)
         run()
-        kern = "ping-pong 256x256 ROWMAX epilogue"
-        res, n_adm = BD.check_rowmax_records(a["aux"], pre, e)
-        object.__setattr__(self, "_rowmax", (a["aux"].data_ptr(), pre, e))
-        return [(w, r, kern) for w, r in res]
+        kern = self._gemm_kernel(a)
+        what = f"gemm {ROW_EPILOGUES[epi]}"
+        if epi == BD.EPI_ROWMAX:
+            res, n_adm = BD.check_rowmax_records(a["aux"], pre, e, what)
+        elif epi == EPI_ROWSAMPLE:
+            g = gumbel_noise(a["seed"], torch.arange(M, device=pre.device)[:, None], torch.arange(N, device=pre.device)[None, :])
+            res, n_adm = BS.check_records(a["aux"], pre, g, e, what)
+        else:
+            lab = s["residual"].reshape(-1)[:M]
+            res = BE.check_rowscore_records(a["aux"], pre, e, lab, what)
+        out = [(w, r, kern) for w, r in res] + [guard(kern)]
+        if epi == BD.EPI_ROWMAX:
+            object.__setattr__(self, "_rowmax", (a["aux"].data_ptr(), pre, e))
+        else:
+            self._rowrec[a["aux"].data_ptr()] = (epi, pre, e, g if epi == EPI_ROWSAMPLE else lab)
+        return out
 
     def chk_rowmax_combine(self, a, s, run):
         n_seg, M = a["n_seg"], a["M"]
@@ -927,6 +994,85 @@ class Recorder:
             print(f"sharpness step={self._tag}: {100 * share:.1f} % of {n_adm.numel()} rows with more than one admissible column, "
                   f"at most {most} in a row", flush=True)
         return res
+
+    def _sharp(self, n_adm, what):
+        share, most = BD.sharpness(n_adm)
+        self.sharp.append((self._tag, share, most))
+        print(f"sharpness {what} step={self._tag}: {100 * share:.1f} % of {n_adm.numel()} rows with more than one admissible column, "
+              f"at most {most} in a row", flush=True)
+
+    def chk_rowsample_combine(self, a, s, run):
+        """on the records it read (bounds_sampling.check_combine), and -- the records came from a checked XL_EPI_ROWSAMPLE launch with
+        this seed -- composed with it against the float64 logits of the whole row (bounds_sampling.check_rows)"""
+        n_seg, M = a["n_seg"], a["M"]
+        ws_in = a["ws"].reshape(-1)[:n_seg * M * 4].clone()
+        run()
+        kern = self._kern
+        res = [(w, r, kern) for w, r in BS.check_combine(ws_in, n_seg, M, a["seed"], a["row_prob"], a["row_id"], a["row_lse"])]
+        rec = self._rowrec.pop(a["ws"].data_ptr(), None)
+        if rec is not None and rec[0] == EPI_ROWSAMPLE and a["row_id"] is not None:
+            _, y, e, g = rec
+            rows, n_adm = BS.check_rows(y, g, e, n_seg, a["row_prob"][:M] if a["row_prob"] is not None else None, a["row_id"][:M],
+                                        a["row_lse"][:M] if a["row_lse"] is not None else None, "ROWSAMPLE + combine")
+            res += [("composed " + w, r, "ROWSAMPLE epilogue + combine") for w, r in rows]
+            self._sharp(n_adm, "ROWSAMPLE")
+        return res
+
+    def chk_sample_rows(self, a, s, run):
+        M, K = a["M"], a["K"]
+        y, g, e = BS.logits_reference(_v2(s["logits"], M, K, a["ldl"]), K, a["inv_T"], a["seed"])
+        run()
+        assert a["row_id"] is not None, "sample_rows without a row_id: nothing to hold the draw to"
+        rows, n_adm = BS.check_rows(y, g, e, (K + 63) // 64 + 6, a["row_prob"][:M] if a["row_prob"] is not None else None,
+                                    a["row_id"][:M], a["row_lse"][:M] if a["row_lse"] is not None else None, "sample_rows")
+        self._sharp(n_adm, "sample_rows")
+        return [(w, r, self._kern) for w, r in rows]
+
+    def _chk_totals(self, a, M, before, labels, n_cols, nll, b_nll, pred):
+        """totals[0:3] of a scores launch: bounds_eval.check_totals on the outputs returned, or -- without a row_nll / row_pred --
+        check_totals_ref on the float64 ones"""
+        if a["totals"] is None:
+            return []
+        lab = labels if labels is not None else torch.full((M,), -100, dtype=torch.int64, device=a["totals"].device)
+        if a["row_nll"] is not None and a["row_pred"] is not None:
+            return BE.check_totals(before, a["totals"], lab, n_cols, a["row_nll"][:M], a["row_pred"][:M])
+        valid = BE.valid_labels(lab, n_cols)
+        pr = a["row_pred"][:M].long() if a["row_pred"] is not None else pred
+        return BE.check_totals_ref(before, a["totals"], valid, valid & (pr == lab), nll, b_nll)
+
+    def chk_rowscore_combine(self, a, s, run):
+        """on the records it read (bounds_eval.check_rowscore_combine), the totals, and -- the records came from a checked
+        XL_EPI_ROWSCORE launch with these labels -- composed with it against the float64 logits (bounds_eval.check_rowscore_rows)"""
+        n_seg, M, n_cols = a["n_seg"], a["M"], a["n_cols"]
+        ws_in = a["ws"].reshape(-1)[:n_seg * M * 4].clone()
+        lab = s["labels"].reshape(-1)[:M] if a["labels"] is not None else None
+        before = a["totals"].clone() if a["totals"] is not None else None
+        run()
+        kern = self._kern
+        res = [(w, r, kern) for w, r in BE.check_rowscore_combine(ws_in, n_seg, M, lab, n_cols, a["row_nll"], a["row_pred"], a["row_max"])]
+        nll, b_nll, pred, _, _ = BE.rowscore_combine_bounds(ws_in, n_seg, M, lab, n_cols)
+        res += [(w, r, kern) for w, r in self._chk_totals(a, M, before, lab, n_cols, nll, b_nll, pred)]
+        rec = self._rowrec.pop(a["ws"].data_ptr(), None)
+        if rec is not None and rec[0] == EPI_ROWSCORE and lab is not None and torch.equal(rec[3], lab):
+            _, pre, e, _ = rec
+            rows = BE.check_rowscore_rows(pre, e, n_seg, lab, n_cols, a["row_nll"][:M] if a["row_nll"] is not None else None,
+                                          a["row_pred"][:M].long() if a["row_pred"] is not None else None,
+                                          a["row_max"][:M] if a["row_max"] is not None else None)
+            res += [("composed " + w, r, "ROWSCORE epilogue + combine") for w, r in rows]
+        return res
+
+    def chk_score_rows(self, a, s, run):
+        M, K = a["M"], a["K"]
+        x = _v2(s["logits"], M, K, a["ldl"])
+        lab = s["labels"].reshape(-1)[:M] if a["labels"] is not None else None
+        before = a["totals"].clone() if a["totals"] is not None else None
+        run()
+        kern = self._kern
+        res = [(w, r, kern) for w, r in BE.check_score_rows(x, lab, a["row_nll"][:M] if a["row_nll"] is not None else None,
+                                                            a["row_pred"][:M] if a["row_pred"] is not None else None,
+                                                            a["row_max"][:M] if a["row_max"] is not None else None)]
+        nll, b_nll, first, _, _ = BE.score_rows_bounds(x, lab)
+        return res + [(w, r, kern) for w, r in self._chk_totals(a, M, before, lab, K, nll, b_nll, first)]
 
     # ------------------------------------------------------------------------------------------------ sampler index kernels
     def chk_remask_lowest(self, a, s, run):

@@ -1,7 +1,8 @@
 """The float64 instrument of tests/test_kernel_bounds_gpu.py (its recording proxy and tests/bounds.py) pointed at everything else the
 benchmark times: the masked-visual-token step in its DEFAULT reduction mode (deferred second stages, checked at the flushes), the
 Mask-Predict and autoregressive samplers with the fused row-max head, the VQA / NLVR2 fine-tune steps, the word_mask / matched
-language branches and the output_attentions forward.  One recorded bf16 step each at the geometry bench.py times (same
+language branches, the output_attentions forward, a temperature sampler (XL_EPI_ROWSAMPLE head) and the validation pass of the
+codebook head and the tied decoder (Engine.evaluate_task: XL_EPI_ROWSCORE, and xl_score_rows with XL_FUSED_PREDICT=0).  One recorded bf16 step each at the geometry bench.py times (same
 construction as bench.py other_workloads; weights from the oracle's make_*_state_dict), dropout on for the training steps, eager.
 Every test prints its headroom table, fails on a numeric method without a checker, on any element beyond its bound, on a pending
 column sum that no flush covered, and on a kernel of its "must have called" set that the step no longer reaches."""
@@ -188,6 +189,79 @@ def test_ar_sampler_steps_against_float64(mode):
     index on ties) and with fixed_pos >= 0 (top-left to bottom-right), exact at every step, behind the same fused head checks"""
     cfg, oc = _cfgs()
     ar_sampler(cfg, oc, _state_dict("base", 19), 64, mode, 3)
+
+
+def temperature_sampler(cfg, oc, sd, B, T=2, temperature=2.0, dev="cuda", ops=None, seed=NAR_SEED):
+    """Mask-Predict sampling with a temperature: the head runs XL_EPI_ROWSAMPLE + xl_rowsample_combine instead of the row maximum"""
+    t0 = time.time()
+    rec, eng = _sampler_engine(cfg, sd, B, O.make_inputs(oc, seed, B, 20, 8)["input_ids"], dev, ops)
+    assert eng.fused_predict_available(), "the fused head is not in use: the sampler would run the logits path"
+    rec.mark(0)
+    eng.sample_codes_nar(T, on_step=lambda i: rec.mark(i + 1), temperature=temperature, seed=5)
+    _finish(rec, t0, ("gemm", "rowsample_combine", "remask_lowest", "sampler_update", "codebook_gather"), [
+        ("a ROWSAMPLE gemm was not checked at every step", len(_checked(rec, "gemm", epilogue=9, alpha=1.0 / temperature)) == T),
+        ("rowsample_combine was not checked at every step", len(_checked(rec, "rowsample_combine")) == T),
+        ("the composed check did not run at every step", {s[0] for s in rec.sharp} == set(range(T))),
+        ("sampler_update was not checked at every step", len(_checked(rec, "sampler_update")) == T),
+        ("the row-maximum head ran", "rowmax_combine" not in rec.called)])
+    return rec
+
+
+def test_temperature_sampler_every_step_against_float64_logits():
+    """T = 2, two steps, bs 4 (256 grid rows), bf16: the tempered segment records, the admissible draw and the tempered
+    probability of the drawn code at every step, with the launch seed of that step"""
+    cfg, oc = _cfgs()
+    rec = temperature_sampler(cfg, oc, _state_dict("base", 19), 4)
+    for tag, share, most in rec.sharp:
+        assert share <= BD.MAX_SHARE_AMBIGUOUS and most <= BD.MAX_ADMISSIBLE, (tag, share, most)
+
+
+def evaluate_tasks(cfg, oc, sds, B, fused, dev="cuda", ops=None, L=64, V=64):
+    """Engine.evaluate_task("vis_mask") and ("word_mask") on one recorder each: the codebook head and the tied decoder through
+    XL_EPI_ROWSCORE + xl_rowscore_combine (fused) or through fp32 logits and xl_score_rows (the caller sets XL_FUSED_PREDICT=0)"""
+    from xlxmert_amd.engine import Engine
+    from xlxmert_amd.params import ParamStore
+    from xlxmert_amd.trainer import random_word_batch
+    recs = []
+    inp = O.make_inputs(oc, INPUT_SEED, B, L, int(V ** 0.5))
+    for task, sd in zip(("vis_mask", "word_mask"), sds):
+        t0 = time.time()
+        store = ParamStore(cfg, dev, BF, task=task)
+        store.load_named(sd)
+        rec = _recorder(ops)
+        eng = Engine(cfg, store, rec, B, L, V, need_lang=task != "vis_mask")
+        eng.sync_compute_weights()
+        ids, mask, pos = inp["input_ids"], inp["attention_mask"].to(dev), inp["visual_pos"].float().to(dev)
+        if task == "vis_mask":
+            labels = inp["cluster_ids"].clone()
+            labels.view(-1)[::11] = -100
+            eng.set_inputs(ids.to(dev), mask, None, pos, cluster_ids=inp["cluster_ids"].to(dev),
+                           vis_mask=torch.ones(B, V, dtype=torch.bool, device=dev), obj_labels=labels.to(dev))
+            out = eng.evaluate_task("vis_mask")
+            key = "obj_loss"
+        else:
+            ids, wl = random_word_batch(ids, vocab_size=cfg.vocab_size, generator=torch.Generator().manual_seed(4242))
+            eng.set_inputs(ids.to(dev), mask, None, pos, cluster_ids=inp["cluster_ids"].to(dev))
+            out = eng.evaluate_task("word_mask", word_labels=wl.to(dev))
+            key = "lm_loss"
+        assert bool(torch.isfinite(out[key]).all()) and float(out[key + "_count"]) > 0
+        must = ("gemm", "rowscore_combine") if fused else ("gemm", "score_rows")
+        _finish(rec, t0, must, [
+            ("the fused head did not run", not fused or len(_checked(rec, "gemm", epilogue=10)) >= 1),
+            ("the totals were not checked", any(r[1] == "totals count" for r in rec.rows)),
+            ("the other scores path ran too", ("score_rows" if fused else "rowscore_combine") not in rec.called)])
+        recs.append(rec)
+    return recs
+
+
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "logits"])
+def test_evaluate_task_heads_within_bounds(fused, monkeypatch):
+    """the validation pass of the codebook head and of the tied decoder at bs 4 (256 grid rows, 64 tokens a row), once through the fused scores epilogue and once
+    (XL_FUSED_PREDICT=0) through fp32 logits and xl_score_rows"""
+    if not fused:
+        monkeypatch.setenv("XL_FUSED_PREDICT", "0")
+    cfg, oc = _cfgs()
+    evaluate_tasks(cfg, oc, (_state_dict("base", 19), _state_dict("cls", 41)), 4, fused)
 
 
 # ---------------------------------------------------------------------------------------------------------------- fine-tune steps
