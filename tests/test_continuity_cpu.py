@@ -1,6 +1,7 @@
 """Training-state continuity on the CPU (kernels replaced by FakeOps): a run that is stopped, saved, rebuilt in a fresh trainer and
 continued must equal the run that was never stopped, bit for bit -- and every piece of the saved state must be OBSERVED (a restore
-that leaves one out must differ).  Second half: the partial-master guard of the sharded exchange's bf16 gather (gloo, world 2).
+that leaves one out must differ).  Second half: the partial-master guard of the sharded exchange's bf16 gather (gloo, world 2), and a
+SHARDED run stopped and resumed on three ranks: bit for bit after gather_state(), refused (the partial-moments guard) without it.
 
 snapshot() / restore() below are what PretrainStep.state()'s docstring tells a user to do, through public names only; the GPU
 twin (tests/test_continuity_gpu.py) imports them."""
@@ -233,3 +234,148 @@ def test_partial_master_guard_world2_gloo(tmp_path, mode):
     world, port = 2, _free_port()
     mp.spawn(_guard_worker, args=(world, port, str(tmp_path), mode), nprocs=world, join=True)
     assert (tmp_path / "ok0").exists() and (tmp_path / "ok1").exists()
+
+
+# ---------------------------------------------------------------- 5. a SHARDED run stopped and resumed (gloo, world 3)
+# rs+ag: a rank's Adam moments -- and with gather="bf16" its master matrices -- are current on its own shards only.  The checkpoint is
+# written by rank 0 alone and reaches the other ranks through sync_replicas(): without gather_state() first, two thirds of it are stale.
+SH_WORLD, SH_STEPS, SH_CUT = 3, 4, 2
+SH_BUFS = ("master", "compute", "exp_avg", "exp_avg_sq")
+
+
+def sharded_trainer(gather, seed, dev="cpu", ops=None, prepare=None, **kw):
+    """the sharded tiny trainer of the resume tests (the GPU twin passes its device and leaves `ops` to the product); `prepare(store)`
+    runs between the weight load and the constructor -- where a resuming rank 0 puts the checkpoint in"""
+    cfg = XLxmertConfig(**TINY)
+    dtype = torch.bfloat16 if gather == "bf16" else torch.float32
+    store = ParamStore(cfg, dev, dtype, task="vis_mask")
+    store.load_named(O.make_state_dict(oracle_cfg(cfg), seed))
+    if prepare is not None:
+        prepare(store)
+    if ops is None and dev == "cpu":
+        ops = FakeOps(dtype)
+    tr = PretrainStep(cfg, 2, 8, 16, dtype=dtype, device=dev, store=store, ops=ops, total_steps=10, lr=1e-2, weight_decay=0.01,
+                      warmup_ratio=0.3, bucket_mb=0.05, collective="rs+ag", gather=gather, visual_losses="obj,feat", **kw)
+    assert tr.sharded and tr.gather_bf16 == (gather == "bf16") and not store.moments_partial
+    return tr
+
+
+def sharded_step(tr, t, rank, cycle=None):
+    """step t (0-based) on this rank's own minibatch; cycle: the batches repeat with that period (launch geometries that come back:
+    the GPU twin wants plan replays)"""
+    cfg = XLxmertConfig(**TINY)
+    seed = 500 + 10 * (t % cycle if cycle else t) + rank
+    tr.step({k: v.to(tr.device) for k, v in synthetic_batch(cfg, 2, 8, 4, seed=seed).items()})
+
+
+def sharded_bufs(tr):
+    """compute copy as the steps left it, then -- gathered -- master weights and both moments"""
+    tr.sync()
+    n = tr.store.n_used
+    out = {"compute": tr.store.compute[:n].cpu().clone()}
+    tr.gather_state()
+    m, v = tr.store.moments()
+    out.update(master=tr.store.master[:n].cpu().clone(), exp_avg=m[:n].cpu().clone(), exp_avg_sq=v[:n].cpu().clone())
+    return out
+
+
+def save_checkpoint(tr, path, raw=False):
+    """what PretrainStep.state() tells a caller to save.  raw: around the guards, as a caller could before they existed -- the buffers
+    as this rank holds them and the counters read one by one"""
+    st = tr.store
+    tr.sync()
+    if raw:
+        m, v = st.exp_avg, st.exp_avg_sq
+        state = {"t": tr.t, "micro": tr.micro, "step_dev": int(tr.step_dev.item())}
+    else:
+        (m, v), state = st.moments(), tr.state()
+    torch.save({"master": st.master.cpu().clone(), "exp_avg": m.cpu().clone(), "exp_avg_sq": v.cpu().clone(),
+                "centroids": st.centroids.cpu().clone(), "state": state}, path)
+
+
+def resume_sharded(gather, rank, path, seed=8, **kw):
+    """every rank: a fresh store (other weights, another codebook) and a fresh trainer; rank 0 alone copies the saved buffers in before
+    the constructor runs, whose sync_replicas() hands them to the others; all ranks load the counters"""
+    ck = torch.load(path)
+
+    def put(store):
+        store.ensure_adam_state()
+        for k in ("master", "exp_avg", "exp_avg_sq"):
+            getattr(store, k).copy_(ck[k])
+        store.set_centroids(ck["centroids"])
+    tr = sharded_trainer(gather, seed, prepare=put if rank == 0 else None, **kw)
+    tr.load_state(ck["state"])
+    return tr
+
+
+def _sharded_resume_worker(rank, world, port, out_dir, gather, with_gather):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(2)
+    ref = sharded_trainer(gather, 3)
+    for t in range(SH_STEPS):
+        sharded_step(ref, t, rank)
+    want = sharded_bufs(ref)
+    tr = sharded_trainer(gather, 3)
+    for t in range(SH_CUT):
+        sharded_step(tr, t, rank)
+    path = os.path.join(out_dir, "ckpt.pt")
+    assert tr.store.moments_partial and tr.store.master_partial == (gather == "bf16")
+    with pytest.raises(RuntimeError, match="gather_state"):
+        tr.state()
+    with pytest.raises(RuntimeError, match="gather_state"):
+        tr.store.moments()
+    if with_gather:
+        tr.gather_state()
+        assert not tr.store.moments_partial and not tr.store.master_partial
+    if rank == 0:
+        save_checkpoint(tr, path, raw=not with_gather)
+    dist.barrier()
+    tr2 = resume_sharded(gather, rank, path)
+    assert (tr2.t, tr2.micro, int(tr2.step_dev.item())) == (SH_CUT, SH_CUT, SH_CUT) and not tr2.store.moments_partial
+    for t in range(SH_CUT, SH_STEPS):
+        sharded_step(tr2, t, rank)
+        assert tr2.store.moments_partial                    # up again after every update
+    got = sharded_bufs(tr2)
+    assert tr2.verify_replicas() == []
+    if with_gather:
+        for k in SH_BUFS:
+            assert torch.equal(got[k], want[k]), (gather, rank, k, (got[k].float() - want[k].float()).abs().max().item())
+        assert tr2.state() == {"t": SH_STEPS, "micro": SH_STEPS, "step_dev": SH_STEPS}
+    else:
+        # the control: rank 0's stale moments went to every rank, nothing raised, the replicas agree -- and the run is another one
+        d = (got["master"] - want["master"]).abs().max().item()
+        print(f"sharded resume WITHOUT gather_state ({gather}, rank {rank}): max |master - uninterrupted| = {d:.3e}")
+        assert not torch.equal(got["master"], want["master"]) and not torch.equal(got["exp_avg"], want["exp_avg"])
+        assert torch.isfinite(got["master"]).all()
+    torch.save(got, os.path.join(out_dir, f"got{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("gather", ["fp32", "bf16"])
+def test_sharded_run_resumes_bit_for_bit_world3_gloo(tmp_path, gather):
+    """collective="rs+ag" on three ranks (fp32 store with the fp32 gather, bf16 store with the bf16 gather): two steps, gather_state()
+    on every rank, rank 0 alone saves master, moments, codebook and state(); three fresh trainers from other weights, rank 0's filled
+    from the file before its constructor broadcasts; two more steps.  Compute copy, master weights and both moments (gathered) equal
+    the uninterrupted four-step run bit for bit on every rank.  Before the gather, state() and ParamStore.moments() raise."""
+    port = _free_port()
+    mp.spawn(_sharded_resume_worker, args=(SH_WORLD, port, str(tmp_path), gather, True), nprocs=SH_WORLD, join=True)
+    got = [torch.load(tmp_path / f"got{r}.pt") for r in range(SH_WORLD)]
+    for g in got[1:]:
+        for k in SH_BUFS:
+            assert torch.equal(got[0][k], g[k]), k
+
+
+@pytest.mark.parametrize("gather", ["fp32", "bf16"])
+def test_sharded_checkpoint_without_gather_state_is_refused_world3_gloo(tmp_path, gather):
+    """the same sequence with gather_state() left out: state() and ParamStore.moments() raise a RuntimeError that names
+    gather_state() -- the guard this test came with.  That it guards something: a checkpoint taken around it (raw buffers of rank 0,
+    counters by hand) resumes without any complaint, the replicas agree with each other, verify_replicas() is clean, and the
+    parameters after two more steps are NOT the uninterrupted run's (measured: max |d| 2.1e-2 with the fp32 store, 2.7e-2 with the bf16 store, at lr 1e-2)."""
+    port = _free_port()
+    mp.spawn(_sharded_resume_worker, args=(SH_WORLD, port, str(tmp_path), gather, False), nprocs=SH_WORLD, join=True)
+    got = [torch.load(tmp_path / f"got{r}.pt") for r in range(SH_WORLD)]
+    for g in got[1:]:
+        for k in SH_BUFS:
+            assert torch.equal(got[0][k], g[k]), k

@@ -355,3 +355,85 @@ def test_partial_master_guard_survives_replay_two_ranks_sharing_one_gpu_gloo(tmp
     assert sorted(r0) == ["compute_after_replay", "master_after_record", "master_after_replay"]
     for k in r0:
         assert torch.equal(r0[k], r1[k]), k
+
+
+# ---------------------------------------------------------------- a sharded plan-mode run stopped and resumed
+def _sharded_resume_worker(rank, world, port, out_dir, gather):
+    import torch.distributed as dist
+    from test_continuity_cpu import SH_BUFS, SH_CUT, SH_STEPS, resume_sharded, save_checkpoint, sharded_bufs, sharded_step, sharded_trainer
+    from xlxmert_amd.engine import reserve_streams
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), XL_COMM="torch")
+    dev = "cuda:0"
+    torch.cuda.set_device(dev)
+    reserve_streams(dev)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    kw = dict(dev=dev, plan=True, drop_grads=False)
+
+    def refused(fn):
+        try:
+            fn()
+        except RuntimeError as e:
+            return "gather_state" in str(e)
+        return False
+
+    # the uninterrupted run; batches of period 2: warm (b0), record (b1), record or replay (b0), REPLAY (b1: recorded for certain)
+    ref = sharded_trainer(gather, 3, **kw)
+    ref.ops.set_gemm_wgrad_slabs(1)
+    assert ref.plan_mode
+    for t in range(SH_STEPS):
+        if t == SH_STEPS - 1:
+            ref.gather_state()                               # (the guard comes down: the replay alone must raise it again)
+            assert not ref.store.moments_partial and ref.state()["t"] == t
+        n_plans = len(ref._plans)
+        sharded_step(ref, t, rank, cycle=2)
+    ref.sync()
+    assert len(ref._plans) == n_plans and n_plans in (1, 2) and ref.t == SH_STEPS, "the last step was to be a replay"
+    assert ref.store.moments_partial, "the partial-moments guard was not armed by the REPLAYED step"
+    assert refused(ref.state) and refused(ref.store.moments)
+    want = sharded_bufs(ref)
+    ref.close()
+    # cut after the recorded step, checkpoint from rank 0, fresh trainers: step 3 runs eagerly (warm), step 4 records
+    tr = sharded_trainer(gather, 3, **kw)
+    tr.ops.set_gemm_wgrad_slabs(1)
+    for t in range(SH_CUT):
+        sharded_step(tr, t, rank, cycle=2)
+    tr.sync()
+    assert refused(tr.state) and refused(tr.store.moments)
+    tr.gather_state()
+    path = os.path.join(out_dir, "ckpt.pt")
+    if rank == 0:
+        save_checkpoint(tr, path)
+    tr.close()
+    dist.barrier()
+    tr2 = resume_sharded(gather, rank, path, **kw)
+    tr2.ops.set_gemm_wgrad_slabs(1)
+    assert (tr2.t, tr2.micro, int(tr2.step_dev.item())) == (SH_CUT, SH_CUT, SH_CUT)
+    for t in range(SH_CUT, SH_STEPS):
+        sharded_step(tr2, t, rank, cycle=2)
+    tr2.sync()
+    assert len(tr2._plans) == 1 and tr2.store.moments_partial
+    got = sharded_bufs(tr2)
+    assert tr2.verify_replicas() == []
+    for k in SH_BUFS:
+        assert torch.equal(got[k], want[k]), (gather, rank, k, differing(got[k], want[k]))
+    tr2.close()
+    torch.save(got, os.path.join(out_dir, f"got{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("gather", ["fp32", "bf16"])
+def test_sharded_plan_run_resumes_bit_for_bit_two_ranks_sharing_one_gpu_gloo(tmp_path, gather):
+    """tests/test_continuity_cpu.py's sharded resume on the real kernels with plan=True, two ranks on one GPU over gloo (fp32 store
+    with the fp32 gather, bf16 store with the bf16 gather; K-split weight gradients through slabs): two steps, gather_state(), rank 0
+    saves, fresh trainers resume and run two more -- the third eagerly, the fourth recording, where the uninterrupted run records
+    and REPLAYS.  Compute copy, gathered master weights and both moments bit-equal on both ranks.  state() and ParamStore.moments()
+    raise until gather_state(), also after the replayed step."""
+    import torch.multiprocessing as mp
+    from test_continuity_cpu import SH_BUFS
+    from test_trainer_cpu import _free_port
+    world, port = 2, _free_port()
+    mp.spawn(_sharded_resume_worker, args=(world, port, str(tmp_path), gather), nprocs=world, join=True)
+    r0, r1 = torch.load(tmp_path / "got0.pt"), torch.load(tmp_path / "got1.pt")
+    for k in SH_BUFS:
+        assert torch.equal(r0[k], r1[k]), k

@@ -2,6 +2,8 @@
 one process per GPU, NCCL backend, DistributedDataParallel): every rank draws its own minibatch, the gradients meet through the
 bucketed exchange, the replicas must stay bit-identical and equal ONE AdamW step on the mean of the oracle's per-rank gradients.
 
+Three and four ranks run on the one-GPU rig only (RCCL above two ranks needs a node nobody has handed this suite yet).
+
 Two rigs, one worker:
   * two GPUs, RCCL over xGMI (backend nccl) -- through both issuers (the library's own binding xl_comm_*, and torch.distributed),
     fp32 and bf16 buckets, eager and plan replay, both collectives (all-reduce; reduce-scatter -> shard AdamW -> all-gather).
@@ -117,14 +119,16 @@ def _worker_gather(rank, world, port, out_dir, backend, issuer):
     dist.destroy_process_group()
 
 
-def _run_gather(tmp_path, backend, issuer):
+def _run_gather(tmp_path, backend, issuer, world=2):
     import torch.multiprocessing as mp
-    from test_trainer_cpu import _free_port
-    world, port = 2, _free_port()
+    from test_trainer_cpu import _free_port, _load_ranks
+    port = _free_port()
     mp.spawn(_worker_gather, args=(world, port, str(tmp_path), backend, issuer), nprocs=world, join=True)
-    r0, r1 = torch.load(tmp_path / "g0.pt"), torch.load(tmp_path / "g1.pt")
-    for k in r0:
-        assert torch.equal(r0[k], r1[k]), k
+    ranks = _load_ranks(tmp_path, "g", world)
+    r0 = ranks[0]
+    for r1 in ranks[1:]:
+        for k in r0:
+            assert torch.equal(r0[k], r1[k]), k
     for plan in (False, True):
         for what in ("compute", "fp32_read", "master"):
             assert torch.equal(r0[f"fp32:{plan}:{what}"], r0[f"bf16:{plan}:{what}"]), (plan, what)
@@ -136,23 +140,34 @@ def test_bf16_all_gather_two_ranks_sharing_one_gpu_gloo(tmp_path):
     _run_gather(tmp_path, "gloo", "torch")
 
 
+def test_bf16_all_gather_four_ranks_sharing_one_gpu_gloo(tmp_path):
+    """the same on four ranks: the casts, xl_adamw and take_f32 / put_f32 on windows at offsets rank * (hi - lo) / 4 -- a quarter and
+    three quarters of a slice, never run on the device by the two-rank tests -- bit for bit on every rank"""
+    _run_gather(tmp_path, "gloo", "torch", world=4)
+
+
 @two_gpus
 @pytest.mark.parametrize("issuer", ["rccl", "torch"])
 def test_bf16_all_gather_two_gpus_rccl(tmp_path, issuer):
     _run_gather(tmp_path, "nccl", issuer)
 
 
-def _run_and_check(tmp_path, backend, issuer, comm_bf16, collective):
+_eager_fp32 = {}         # (world, collective) -> rank 0's parameters after the three eager steps, fp32 buckets, gloo rig: printed figures only
+
+
+def _run_and_check(tmp_path, backend, issuer, comm_bf16, collective, world=2):
     import torch.multiprocessing as mp
-    from test_trainer_cpu import TINY, _free_port, oracle_cfg, oracle_grads
+    from test_trainer_cpu import TINY, _free_port, _load_ranks, _mean_grads, oracle_cfg, oracle_grads
     from xlxmert_amd.config import XLxmertConfig
     from xlxmert_amd.trainer import linear_schedule, synthetic_batch
-    world, port = 2, _free_port()
+    port = _free_port()
     mp.spawn(_worker, args=(world, port, str(tmp_path), backend, issuer, comm_bf16, collective), nprocs=world, join=True)
-    r0, r1 = torch.load(tmp_path / "w0.pt"), torch.load(tmp_path / "w1.pt")
-    for part in ("step1", "eager", "plan"):
-        for k in r0[part]:
-            assert torch.equal(r0[part][k], r1[part][k]), (part, k)
+    ranks = _load_ranks(tmp_path, "w", world)
+    r0 = ranks[0]
+    for r1 in ranks[1:]:
+        for part in ("step1", "eager", "plan"):
+            for k in r0[part]:
+                assert torch.equal(r0[part][k], r1[part][k]), (part, k)
     # a replayed plan runs the step the eager trainer runs (fp32 atomics: not bit for bit)
     for k in r0["eager"]:
         assert (r0["eager"][k] - r0["plan"][k]).abs().max().item() < (5e-5 if not comm_bf16 else 2e-2), k
@@ -162,11 +177,21 @@ def _run_and_check(tmp_path, backend, issuer, comm_bf16, collective):
     sd = O.make_state_dict(oracle_cfg(cfg), 3)
     gs = [oracle_grads(cfg, sd, synthetic_batch(cfg, 2, 8, 4, seed=500 + r))[0] for r in range(world)]
     names = sorted(gs[0])
-    _, clipped = O.clip_grad_norm([(gs[0][k] + gs[1][k]) / 2 for k in names], 1.0)
+    _, clipped = O.clip_grad_norm(_mean_grads(gs, names), 1.0)
     lr = 1e-2 * linear_schedule(0, 0, 10)
+    worst = 0.0
     for k, g in zip(names, clipped):
         p, _, _ = O.adamw_update(sd[k], g, torch.zeros_like(g), torch.zeros_like(g), 1, lr)
+        worst = max(worst, (r0["step1"][k] - p).abs().max().item())
         assert (r0["step1"][k] - p).abs().max().item() < 5e-5, (k, (r0["step1"][k] - p).abs().max().item())
+    vs_plan = max((r0["eager"][k] - r0["plan"][k]).abs().max().item() for k in r0["eager"])
+    print(f"{backend} world {world} {collective}: worst |parameter - oracle| after step 1 {worst:.3e}; eager against plan after three steps {vs_plan:.3e}")
+    if backend == "gloo":
+        _eager_fp32[(world, collective)] = r0["eager"]
+        both = [_eager_fp32.get((world, c)) for c in ("allreduce", "rs+ag")]
+        if None not in both:
+            d = max((both[0][k] - both[1][k]).abs().max().item() for k in both[0])
+            print(f"gloo world {world}: worst |rs+ag - allreduce| after three eager steps, fp32 buckets {d:.3e}")
 
 
 @pytest.mark.parametrize("collective", ["allreduce", "rs+ag"])
@@ -174,6 +199,14 @@ def _run_and_check(tmp_path, backend, issuer, comm_bf16, collective):
 def test_two_ranks_sharing_one_gpu_gloo(tmp_path, comm_bf16, collective):
     """the worker of the two-GPU tests on the one-GPU rig (gloo; torch.distributed issues the collectives)"""
     _run_and_check(tmp_path, "gloo", "torch", comm_bf16, collective)
+
+
+@pytest.mark.parametrize("collective", ["allreduce", "rs+ag"])
+def test_three_ranks_sharing_one_gpu_gloo(tmp_path, collective):
+    """three ranks, fp32 buckets: a sum of three addends, shard windows at a third and two thirds of a slice (xl_adamw, xl_sumsq on
+    offsets that are multiples of 256 elements and of nothing larger), eager and plan: step 1 against one AdamW step on the mean of
+    three oracle gradients, eager against plan, every rank against rank 0 -- the two-rank bounds"""
+    _run_and_check(tmp_path, "gloo", "torch", False, collective, world=3)
 
 
 @two_gpus

@@ -220,6 +220,7 @@ class ParamStore:
         self._task_flags = {}
         self._kept = set()
         self.master_partial = False     # sharded exchange, gather='bf16': the master matrices are whole on their owner only (trainer)
+        self.moments_partial = False    # sharded exchange, either gather mode: so are the Adam moments (trainer; moments() refuses)
         # frozen centroid codebook (vis_emb.weight == obj_predict_head.out_cluster.weight, ref modeling.py:140-151)
         self.centroids = None          # fp32 [K, F]
         self.centroids_c = None        # compute dtype
@@ -369,6 +370,14 @@ class ParamStore:
         if self.exp_avg is None:
             self.exp_avg = torch.zeros(self.n_used, dtype=torch.float32, device=self.device)
             self.exp_avg_sq = torch.zeros(self.n_used, dtype=torch.float32, device=self.device)
+
+    def moments(self):
+        """(exp_avg, exp_avg_sq) for a reader outside the step (checkpoints, comparisons).  The sharded exchange leaves each rank's
+        moments current on its own shards only: refused until PretrainStep.gather_state() has made them whole."""
+        if self.moments_partial:
+            raise RuntimeError("the Adam moments are current on the owning rank only (sharded exchange): call "
+                               "PretrainStep.gather_state() on EVERY rank before reading them (checkpoints)")
+        return self.exp_avg, self.exp_avg_sq
 
     def load_named(self, sd, strict=False):
         """Copy tensors of a reference-layout state dict into the master buffer (keys not on the path are ignored)."""

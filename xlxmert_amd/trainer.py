@@ -48,6 +48,30 @@ def linear_schedule(step, warmup_steps, total_steps):
     return max(0.0, float(total_steps - step) / float(max(1, total_steps - warmup_steps)))
 
 
+def split_slice(lo, hi, world):
+    """how the finished slice [lo, hi) of the gradient buffer goes out in the sharded exchange: [("rs" | "ar", lo, hi), ...] in buffer
+    order -- its largest prefix that splits into `world` equal pieces of whole 256-element optimizer chunks is reduce-scattered, the
+    remainder (< 256 * world elements; all of a slice shorter than that) all-reduced: a replicated tail every rank updates itself."""
+    gran = 256 * world
+    n = (hi - lo) // gran * gran
+    out = []
+    if n:
+        out.append(("rs", lo, lo + n))
+    if lo + n < hi:
+        out.append(("ar", lo + n, hi))
+    return out
+
+
+def owned_range(kind, lo, hi, rank, world):
+    """(lo, hi) of the part of split_slice's segment (kind, lo, hi) that rank `rank`'s optimizer pass covers: the rank-th of `world`
+    equal pieces of a reduce-scattered segment (where RCCL's in-place reduce-scatter leaves this rank's sum and its all-gather reads
+    this rank's contribution), all of a replicated tail."""
+    if kind != "rs":
+        return lo, hi
+    per = (hi - lo) // world
+    return lo + rank * per, lo + (rank + 1) * per
+
+
 class PretrainStep:
     def __init__(self, cfg: XLxmertConfig, batch_size, text_len=20, n_grids=64, dtype=torch.bfloat16, device=None,
                  lr=1e-4, weight_decay=0.0, warmup_ratio=0.05, total_steps=100000, clip_grad_norm=1.0,
@@ -308,7 +332,7 @@ class PretrainStep:
             st.centroids_c.copy_(st.centroids)
         self.t = int(self.step_dev.item())
         self.micro = max(self.micro, self.t)
-        st.master_partial = False                # (rank 0's whole master copy is on every rank now)
+        st.master_partial = st.moments_partial = False       # (rank 0's whole master copy and moments are on every rank now)
         self.engine.sync_compute_weights()
 
     def verify_replicas(self):
@@ -381,16 +405,11 @@ class PretrainStep:
     def _send(self, lo, hi):
         """the finished slice [lo, hi) of the gradient buffer goes out.  Sharded exchange: its largest prefix that splits into
         `world` equal pieces of whole 256-element optimizer chunks is reduce-scattered, the remainder (< 256 * world elements)
-        all-reduced -- a replicated tail every rank updates itself."""
+        all-reduced -- a replicated tail every rank updates itself (split_slice)."""
         if self.sharded:
-            gran = 256 * self.world
-            n = (hi - lo) // gran * gran
-            if n:
-                self._issue("rs", lo, lo + n)
-                self._segments.append(("rs", lo, lo + n))
-            if lo + n < hi:
-                self._issue("ar", lo + n, hi)
-                self._segments.append(("ar", lo + n, hi))
+            for kind, a, b in split_slice(lo, hi, self.world):
+                self._issue(kind, a, b)
+                self._segments.append((kind, a, b))
         else:
             self._issue("ar", lo, hi)
         self._slices.append((lo, hi))
@@ -419,8 +438,8 @@ class PretrainStep:
             self._works.append(None)
             return
         stream = torch.cuda.current_stream() if self.device.type == "cuda" else None      # the stream that finished the slice
-        per = (hi - lo) // self.world
-        mine = piece[self.rank * per:(self.rank + 1) * per]
+        a, b = owned_range("rs", lo, hi, self.rank, self.world)
+        mine = buf[a:b]
         in_place = dist.get_backend() == "nccl"          # (RCCL's in-place layout: recv = send + rank * count)
 
         def issue():
@@ -440,14 +459,7 @@ class PretrainStep:
         reduce-scattered slice and all of every replicated tail (everything, in "allreduce" mode)."""
         if not self.sharded:
             return [(0, self.store.n_used)]
-        out = []
-        for kind, lo, hi in self._segments:
-            if kind == "rs":
-                per = (hi - lo) // self.world
-                out.append((lo + self.rank * per, lo + (self.rank + 1) * per))
-            else:
-                out.append((lo, hi))
-        return out
+        return [owned_range(kind, lo, hi, self.rank, self.world) for kind, lo, hi in self._segments]
 
     def _on_grad_ready(self, lo, hi, flush=False, lane="v"):
         ln = self._lanes.get(lane)
@@ -656,9 +668,16 @@ class PretrainStep:
         """the trainer's own part of what a resumed run needs: the host counters `t` and `micro` (the dropout seeds derive from
         `micro`), the device-side update counter `step_dev` (the schedule and the bias corrections read it; an int) and, with
         task="all", `chunk_steps` (the per-tensor update counts; a CPU int32 tensor).  Synchronises with the device.
-        The caller saves next to it: store.master, store.exp_avg, store.exp_avg_sq and the codebook (store.centroids, which is
-        not part of `master`).  To resume: copy the three buffers back in place, set_centroids(codebook), load_state(state),
-        then engine.sync_compute_weights()."""
+        The caller saves next to it: store.master, the Adam moments (store.moments() = exp_avg, exp_avg_sq) and the codebook
+        (store.centroids, which is not part of `master`).  To resume: copy the three buffers back in place, set_centroids(codebook),
+        load_state(state), then engine.sync_compute_weights().
+        Sharded exchange (collective="rs+ag", world > 1): a rank's moments -- and with gather="bf16" its master matrices -- are current
+        on its own shards only, so a checkpoint written from one rank's buffers would resume (world - 1) / world of the parameters
+        from stale moments without anything noticing (sync_replicas() broadcasts them; the replicas agree with each other).  Call
+        gather_state() on EVERY rank first: state() raises a RuntimeError until then, as store.moments() and store.named_state() do."""
+        if self.store.moments_partial:
+            raise RuntimeError("the Adam moments are current on the owning rank only (sharded exchange): call "
+                               "PretrainStep.gather_state() on EVERY rank before state() / a checkpoint")
         self.sync()
         out = {"t": self.t, "micro": self.micro, "step_dev": int(self.step_dev.item())}
         if self.chunk_steps is not None:
@@ -747,6 +766,10 @@ class PretrainStep:
         re-executes the recorded C-ABI calls only, never the Python of the body it was recorded from."""
         if self.gather_bf16 and self.world > 1:
             self.store.master_partial = True
+        # ... and with either gather mode a rank's Adam moments are current on its own shards only (the step gathers parameters, never
+        # moments): state() and ParamStore.moments() refuse until gather_state()
+        if self.sharded and self.world > 1:
+            self.store.moments_partial = True
 
     # ---- sharded optimizer (collective="rs+ag"): shard-local norm + one scalar all-reduce, AdamW over this rank's shards,
     # all-gather of the updated compute weights slice by slice in the order the next forward needs them
@@ -838,8 +861,7 @@ class PretrainStep:
                     if hooked:
                         ops.event_record(self._seg_events[i], self._comm_stream)
             else:
-                per = (hi - lo) // W
-                self._host_op(lambda piece=piece, per=per: dist.all_gather_into_tensor(piece, piece[r * per:(r + 1) * per].clone()))
+                self._host_op(lambda piece=piece, mine=piece[a - lo:b - lo]: dist.all_gather_into_tensor(piece, mine.clone()))
                 if side is not None:
                     self._host_op(lambda t=side[1]: dist.all_reduce(t, op=dist.ReduceOp.SUM))
                     ops.put_f32(st.master[lo:hi], side[0], side[1])
@@ -869,12 +891,11 @@ class PretrainStep:
         for kind, lo, hi in self._segments:
             if kind != "rs":
                 continue
-            per = (hi - lo) // W
+            a, b = owned_range(kind, lo, hi, r, W)
             for buf in (st.exp_avg, st.exp_avg_sq) + ((st.master,) if self.gather_bf16 else ()):      # (fp32 gather: the master weights are gathered by every step)
-                piece = buf[lo:hi]
-                dist.all_gather_into_tensor(piece, piece[r * per:(r + 1) * per].clone())
+                dist.all_gather_into_tensor(buf[lo:hi], buf[a:b].clone())
         self.sync()
-        st.master_partial = False
+        st.master_partial = st.moments_partial = False
 
     def _optimizer_launches(self):
         if self.sharded and self._segments:
